@@ -11,9 +11,13 @@ JSON line.  Workloads (BASELINE.json configs):
   cfg2            cl_vae --use_x_prev, batch 512/GPU, latent 4, 2 classes (fp32 path)
 Weak scaling: per-GPU work is fixed, the global batch grows with N.
 
-The timed region is exactly K steps between a barrier + torch.cuda.synchronize() on both sides.  When K steps take less
-than 50 ms (the driver's K = 20 at 0.4 ms is 8 ms: one clock-state hiccup of the device moves it by 5-10 %), the region is
-repeated as 5..9 such blocks and the line carries the MEDIAN block (`timed_blocks`: every block, its min and max).
+The timed region is exactly K steps between a barrier + torch.cuda.synchronize() on both sides; `ms_per_step` is its time
+over K (the slowest rank's, N > 1).  Short regions are noisy (one clock-state hiccup of the device moves 8 ms by 5-10 %):
+choose K from a first run's `ms_per_step`.
+`--dump-outputs DIR` writes what the timed path computed in its last timed step as DIR/<name>.npy (float32 / float64, at
+most 64 MB in all; see dump_outputs): training -- the five loss terms, the updated weights and the step's gradients;
+generation -- the generated frames of the last timed run.  Inputs, weights and noise are seeded, so the same arguments give
+the same inputs in every run and two builds can be compared output for output.
 A default single-GPU run (`python bench.py`, workload cfg3) appends `also`: the other BASELINE workloads -- cfg5, cfg2
 fp32 / bf16, generation of 1 and 1024 sequences -- measured right after the headline by a child process (`bench.py
 --also-only`; a few seconds each: value, ms per step, dominant-kernel fraction), so that those numbers are witnessed by
@@ -312,6 +316,8 @@ def bench_generate(args, w, dev, rank, world):
         torch.cuda.synchronize()
         d1 = time.perf_counter() - t0
         dt = d1 if dt is None else min(dt, d1)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'frames': out})       # the last run's
     frames = world * N * (args.steps + 16)
     if rank == 0:
         return ({"metric": "generated piano-roll frames/sec (sample)", "value": round(frames / dt, 1),
@@ -381,6 +387,8 @@ def bench_generate_vae(args, w, dev, rank, world):
         torch.cuda.synchronize()
         d1 = time.perf_counter() - t0
         dt = d1 if dt is None else min(dt, d1)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'frames': out})       # the last run's
     if rank == 0:
         return ({"metric": "generated piano-roll frames/sec (sample)", "value": round(world * N * args.steps / dt, 1),
                           "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -438,39 +446,59 @@ def launch_selftest(args):
         dist.destroy_process_group()
 
 
-def timed_blocks(run, barrier, steps, world, dev):
-    """K = `steps` steps between barrier + synchronize, as 1 block, or 5..9 blocks when a block is shorter than 50 ms.
-    Returns (seconds of the median block, [ms per step of every block], per-rank ms per step of the median block)."""
+def timed_region(run, barrier, steps, world, dev):
+    """Exactly `steps` steps between barrier + synchronize.  Returns (seconds of the slowest rank, per-rank ms per step)."""
     import torch
     import torch.distributed as dist
     from clvae_amd.parallel import meta_device
-    mdev = meta_device(dev)
+    barrier()
+    t0 = time.perf_counter()
+    run(steps)
+    barrier()
+    every = [time.perf_counter() - t0]
+    if world > 1:
+        mine = torch.tensor(every, dtype=torch.float64, device=meta_device(dev))
+        gathered = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(gathered, mine)
+        every = [float(t.item()) for t in gathered]
+    return max(every), [round(1e3 * x / steps, 4) for x in every]
 
-    def one():
-        barrier()
-        t0 = time.perf_counter()
-        run(steps)
-        barrier()
-        dt = time.perf_counter() - t0
-        if world > 1:
-            mine = torch.tensor([dt], dtype=torch.float64, device=mdev)
-            every = [torch.zeros_like(mine) for _ in range(world)]
-            dist.all_gather(every, mine)
-            return [float(t.item()) for t in every]
-        return [dt]
 
-    blocks = [one()]
-    first = max(blocks[0])
-    if first < 0.05:
-        n = int(min(9, max(5, np.ceil(0.05 / max(first, 1e-6)))))
-        if world > 1:                      # every rank must run the same number of blocks
-            t = torch.tensor([n], dtype=torch.int32, device=mdev)
-            dist.broadcast(t, src=0)
-            n = int(t.item())
-        blocks += [one() for _ in range(n - 1)]
-    worst = [max(b) for b in blocks]                         # a block takes as long as its slowest rank
-    mid = int(np.argsort(worst)[len(worst) // 2])
-    return worst[mid], [round(1e3 * x / steps, 4) for x in worst], [round(1e3 * x / steps, 4) for x in blocks[mid]]
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: the whole dump, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """arrays {name: torch tensor} -> path/<name>.npy, float64 tensors as float64 and all others as float32.  When they hold
+    more than DUMP_BYTES, the smaller ones are written whole and the larger ones share what is left as a fixed sample of
+    their rows along the last axis: rows np.random.default_rng(0).choice(n_rows, k, replace=False), sorted, written as a
+    [k, last axis] array (the same rows in every run of the same shapes)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES - 1024 * len(arrays)           # room for the .npy headers
+    order = sorted(arrays, key=lambda k: arrays[k].numel())
+    for i, name in enumerate(order):
+        a = arrays[name].detach()
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        share = left // (len(order) - i)
+        if a.numel() * a.element_size() > share:
+            rows = a.reshape(-1, a.shape[-1])
+            k = share // (rows.shape[1] * rows.element_size())
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], k, replace=False))
+            a = rows[torch.as_tensor(idx, device=rows.device)]
+        a = a.cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), a)
+        left -= a.nbytes
+
+
+def train_outputs(eng):
+    """What the last training step leaves its caller: the five loss terms (vae, kl_z, kl_w, w_rec, acc), the updated
+    weights and the step's gradients, by the Keras layer names ('/' -> '.')."""
+    out = {'losses': eng.scal[:5].double()}
+    for name, _ in eng.P.logical:
+        key = name.replace('/', '.')
+        out['weights.' + key] = eng.P.p(name)
+        out['grads.' + key] = eng.P.g(name)
+    return out
 
 
 def kernel_time_pass(eng, ts_args, batch, reps, label_off=False):
@@ -663,9 +691,11 @@ def roofline_object(args, w, wl_name, eng, recs, recs_nolabel, reps, value_per_g
     return roofline
 
 
-def measure_train(args, wl_name, dev, rank, world, steps, warmup, bf16=False, reps=40, want_roofline=True, pmc=None):
+def measure_train(args, wl_name, dev, rank, world, steps, warmup, bf16=False, reps=40, want_roofline=True, pmc=None,
+                  dump_dir=None):
     """One training workload: engine, synthetic windows resident in HBM, set-up (graph capture + the kernel-time pass),
-    warm-up, the timed blocks.  Returns the pieces of the JSON line."""
+    warm-up, the timed region (then, with dump_dir, rank 0's train_outputs written there).  Returns the pieces of the
+    JSON line."""
     import torch
     import torch.distributed as dist
     from clvae_amd.trainer import TrainStep
@@ -722,7 +752,9 @@ def measure_train(args, wl_name, dev, rank, world, steps, warmup, bf16=False, re
     run(warmup)
     if os.environ.get('CLV_BENCH_FAULT_RANK') == str(rank):        # tests: one rank dies between warm-up and the timed region
         raise RuntimeError("CLV_BENCH_FAULT_RANK: injected failure of rank %d" % rank)
-    dt, block_ms, rank_ms = timed_blocks(run, barrier, steps, world, dev)
+    dt, rank_ms = timed_region(run, barrier, steps, world, dev)
+    if dump_dir and rank == 0:      # before anything below steps again
+        dump_outputs(dump_dir, train_outputs(eng))
     allreduce = allreduce_microbench(ts, dev) if world > 1 else None
     # what the host spends per step issuing it (staging launch + graph replays / plain launches / collectives), device idle
     # or not: 50 steps issued back to back, clock stopped BEFORE the synchronize
@@ -737,7 +769,7 @@ def measure_train(args, wl_name, dev, rank, world, steps, warmup, bf16=False, re
     if recs is not None:
         roofline = roofline_object(args, w, wl_name, eng, recs, recs_nolabel, reps, value / world, bf16,
                                    kernel_times=args.kernel_times, pmc=pmc)
-    return dict(w=w, eng=eng, ts=ts, value=value, dt=dt, block_ms=block_ms, rank_ms=rank_ms, allreduce=allreduce, loss=loss,
+    return dict(w=w, eng=eng, ts=ts, value=value, dt=dt, rank_ms=rank_ms, allreduce=allreduce, loss=loss,
                 roofline=roofline, host_us=round(host_us, 1))
 
 
@@ -789,7 +821,7 @@ def also_list(args, dev):
             r = m['roofline'] or {}
             e = {"workload": name + ('_bf16' if bf16 else ''), "metric": "piano-roll timesteps/sec (train)",
                  "value": round(m['value'], 1), "unit": "timesteps/s", "ms_per_step": round(1e3 * m['dt'] / steps, 4),
-                 "steps": steps, "warmup": warmup, "timed_blocks_ms_per_step": m['block_ms'],
+                 "steps": steps, "warmup": warmup,
                  "dtype": "bf16" if bf16 else "f32", "final_loss": round(float(m['loss']['total']), 4),
                  "config": "%s batch %d x seq_len %d, latent %d" % (m['w']['model'], m['w']['B'], m['w']['T'], m['w']['L']),
                  "roofline": {k: r.get(k) for k in ('kernel', 'frac', 'achieved', 'peak', 'unit', 'avg_launch_us', 'executes_on',
@@ -833,6 +865,8 @@ def main():
                     help='do not measure roofline.traffic with two rocprofv3 PMC child passes (a default single-GPU training run does); '
                          'the committed summary under profiles/ is read instead')
     ap.add_argument('--also-only', action='store_true', help='print only the `also` list (what a default run starts as its child)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the timed path computed in its last timed step to DIR/<name>.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ:
@@ -876,7 +910,7 @@ def main():
             print(json.dumps(g))
         return
     m = measure_train(args, args.workload, dev, rank, world, args.steps, args.warmup, bf16=args.bf16,
-                      want_roofline=not args.no_roofline, pmc=pmc)
+                      want_roofline=not args.no_roofline, pmc=pmc, dump_dir=args.dump_outputs)
     eng, ts = m['eng'], m['ts']
 
     cpu = None
@@ -901,10 +935,6 @@ def main():
                                    "Adam-WN, hipGraph=%s" % (args.workload, w['model'], B, T, w['L'], w['C'],
                                                              not args.no_graph),
                        "global_batch": world * B, "seq_len": T, "parallelism": "dp%d" % world},
-            "timed_blocks": {"ms_per_step": m['block_ms'], "min": min(m['block_ms']), "max": max(m['block_ms']),
-                             "reported": "median block" if len(m['block_ms']) > 1 else "the one block",
-                             "rule": "every block = exactly --steps steps between barrier + synchronize; more than one block "
-                                     "only when a block is shorter than 50 ms"},
             "final_loss": round(float(m['loss']['total']), 4),
             "roofline": m['roofline'], "cpu_baseline": cpu,
             "devices": devices, "rccl": rccl if world > 1 else None,

@@ -6,7 +6,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REF_DATA = "/root/reference/data/input"
 
 
 def golden(name):

@@ -40,3 +40,31 @@ def test_default_bench_line_is_whole():
     also = d.get('also')
     assert isinstance(also, list) and len(also) >= 6, also
     assert not [a for a in also if 'error' in a], also
+
+
+def test_dump_outputs_are_the_same_in_two_runs(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's loss terms, updated weights and gradients (one file per Keras
+    layer tensor), finite, and bit for bit the same in two runs with the same arguments (seeded inputs, deterministic step)."""
+    pytest.importorskip("torch")
+    import numpy as np
+    import clvae_amd  # noqa: F401
+    from clvae_amd import _lib
+    _lib.require_gpu()
+    env = dict(os.environ)
+    env.pop('CLV_LIB', None)
+    dirs = [str(tmp_path / d) for d in ('a', 'b')]
+    for d in dirs:
+        pr = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4', '--warmup', '2', '--no-cpu-baseline',
+                             '--no-pmc-traffic', '--no-also', '--dump-outputs', d], cwd=ROOT, env=env,
+                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert pr.returncode == 0, pr.stderr[-2000:]
+        assert json.loads(pr.stdout.strip().splitlines()[-1])['steps'] == 4
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert 'losses.npy' in names and 'weights.hW.kernel.npy' in names and 'grads.hW.kernel.npy' in names
+    assert len([n for n in names if n.startswith('weights.')]) == len([n for n in names if n.startswith('grads.')]) > 10
+    for n in names:
+        a, b = (np.load(os.path.join(d, n)) for d in dirs)
+        assert a.dtype == (np.float64 if n == 'losses.npy' else np.float32), n
+        assert np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, b, err_msg=n)

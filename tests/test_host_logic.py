@@ -404,3 +404,27 @@ def test_ctypes_signatures_have_the_headers_argument_counts():
                 assert ctypes.sizeof(t) == 8, (name, a, t)
             elif re.match(r"(const\s+)?(int|int32_t|uint32_t|unsigned)\b", a):
                 assert ctypes.sizeof(t) == 4 and t is not ctypes.c_float, (name, a, t)
+
+
+# ---------------------------------------------------------------- bench.py --
+def test_bench_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 stays float64, everything else is float32; over the budget the small arrays are
+    written whole and the large one is cut to the seeded sample of its rows that dump_outputs documents."""
+    import torch
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 200000)
+    g = torch.Generator().manual_seed(0)
+    big = torch.rand(64, 50, 88, generator=g)                       # 1.1 MB of frames
+    arrs = {'losses': torch.arange(5, dtype=torch.float64), 'counts': torch.arange(7, dtype=torch.int32),
+            'weights.h.kernel': torch.randn(88, 96, generator=g), 'frames': big}
+    bench.dump_outputs(str(tmp_path), arrs)
+    assert sorted(os.listdir(tmp_path)) == sorted(n + '.npy' for n in arrs)
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)) <= bench.DUMP_BYTES
+    got = {n: np.load(os.path.join(tmp_path, n + '.npy')) for n in arrs}
+    assert got['losses'].dtype == np.float64 and np.array_equal(got['losses'], np.arange(5))
+    assert got['counts'].dtype == np.float32 and np.array_equal(got['counts'], np.arange(7))
+    assert np.array_equal(got['weights.h.kernel'], arrs['weights.h.kernel'].numpy())
+    rows = big.reshape(-1, 88).numpy()
+    k = got['frames'].shape[0]
+    assert got['frames'].shape == (k, 88) and 0 < k < rows.shape[0]
+    np.testing.assert_array_equal(got['frames'], rows[np.sort(np.random.default_rng(0).choice(rows.shape[0], k, replace=False))])

@@ -7,7 +7,7 @@ import pytest
 
 import clvae_amd  # noqa: F401
 from clvae_amd.utils import pianoroll as PR
-from helpers import REF_DATA, golden, make_synthetic_pickle, write_jsb_pickle
+from helpers import golden, make_synthetic_pickle, write_jsb_pickle
 
 G1 = golden("g1_pianodata.npz")
 CASES = [('Cs', 100, 1, dict(return_y_next=True, squeeze_x=True, squeeze_y=True)),

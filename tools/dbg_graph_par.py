@@ -1,7 +1,7 @@
 """Do independent branches of a captured hipGraph run concurrently?  Two latency-bound kernels (one workgroup wave
 each), captured (a) back to back on one stream, (b) forked onto a side stream and joined."""
-import sys, time, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, time, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import clvae_amd
 from clvae_amd import ops
 dev = torch.device('cuda:0')

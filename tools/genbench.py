@@ -1,5 +1,5 @@
-import sys, time, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, time, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import clvae_amd
 from clvae_amd.engine import VrnnEngine
 from clvae_amd.initializers import init_weights

@@ -1,6 +1,7 @@
 """Build-container / any-CPU tool (no GPU): how far do two correct trajectories of the JSB_all run drift apart?  fp64 oracle vs the same oracle in float32 (what Keras' floatx computes)."""
-import sys, time, numpy as np
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys, time, numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 from helpers import write_jsb_pickle
 from oracle import clvae_oracle as O
 from oracle import philox as OP

@@ -1,5 +1,5 @@
-import torch, sys
-sys.path.insert(0, '/root/repo/tests')
+import os, sys, torch
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), 'tests'))
 nan = float('nan')
 blocks = [torch.full((64 << 20,), nan, dtype=torch.float32, device='cuda') for _ in range(3)]
 blocks += [torch.full((n,), nan, dtype=torch.float32, device='cuda') for n in (1 << 22, 1 << 20, 1 << 18) for _ in range(8)]
