@@ -79,6 +79,21 @@ TABLES = {
     ],
 }
 
+# the two scoring tools of THIS implementation (the reference has none: its cl_vrnn/train.py builds the test split and
+# never uses it): importance-weighted log-likelihood and Keras evaluate() of a trained model on one split
+_EVAL_FLAGS = [
+    Flag(('run_name',), str, None, 'tag for current run'),
+    Flag(('-i', '--model_file'), str, '', 'trained model weights (.h5, with its .json next to it)'),
+    Flag(('--train_file',), str, '../data/input/JSB Chorales_Cs.pickle', 'file of training data (.pickle)'),
+    Flag(('--split',), str, 'test', 'split to score: test, valid or train'),
+    Flag(('-k',), int, 100, 'importance samples per window'),
+    Flag(('--seed',), int, 0, 'noise key of the importance samples'),
+    Flag(('--out',), str, '', 'write the results as JSON to this file'),
+]
+TABLES['cl_vae.evaluate'] = list(_EVAL_FLAGS)
+TABLES['cl_vrnn.evaluate'] = list(_EVAL_FLAGS)
+SPLIT_CHOICES = ('test', 'valid', 'train')
+
 # switches of THIS implementation (not in the reference): where the frame loop of sample.py runs
 # cl_vae/train.py only, next to the reference's flags
 BF16_FLAGS = [
@@ -97,6 +112,8 @@ def parser_for(tool, extra=()):
     for f in list(TABLES[tool]) + list(extra):
         if f.kind == ON:
             p.add_argument(*f.names, action=ON, help=f.help)
+        elif f.names == ('--split',):
+            p.add_argument(*f.names, type=f.kind, default=f.default, choices=SPLIT_CHOICES, help=f.help)
         elif f.names[0].startswith('-'):
             p.add_argument(*f.names, type=f.kind, default=f.default, help=f.help)
         else:
@@ -162,3 +179,24 @@ class TrainPlan:
                          validation_data=(x_va, [P.y_valid, w_valid, w_valid, P.y_valid]))
         at = best_epoch(hist.history['val_loss'], self.first_epoch if best_from is None else best_from)
         return {k: v[at] for k, v in hist.history.items()}
+
+
+def score_split(model, x, y, args, margs):
+    """The common tail of cl_vae/evaluate.py and cl_vrnn/evaluate.py: the importance-weighted log-likelihood and Keras
+    evaluate() of `model` on one split's windows (x, y as fit() takes them), printed and, with --out, written as JSON.
+    The model's noise key is --seed (evaluate() draws from it), so two runs with the same flags write the same file."""
+    import json
+    model.seed = int(args.seed)
+    # load_model rebuilds the layers only; the label prior is part of p(x) and of the w_kl loss
+    model.engine.cfg['w_log_var_prior'] = float(margs.get('w_log_var_prior', 0.0))
+    res = model.log_likelihood(x, y, k=args.k, seed=args.seed)
+    res['evaluate'] = dict(zip(model.metrics_names, model.evaluate(x, y)))
+    res.update(split=args.split, model_file=args.model_file, seed=int(args.seed))
+    print("%s split: %d windows, K = %d: log-likelihood %.4f nats per window (%.4f per frame), ELBO %.4f, ESS %.2f"
+          % (args.split, res['n_windows'], res['k'], res['log_likelihood'], res['log_likelihood_per_frame'], res['elbo'],
+             res['ess']))
+    print(" - ".join("%s: %.4f" % kv for kv in res['evaluate'].items()))
+    if args.out:
+        with open(args.out, 'w') as f:
+            json.dump(res, f, indent=1, sort_keys=True)
+    return res

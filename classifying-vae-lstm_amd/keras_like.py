@@ -381,6 +381,49 @@ class Model:
             dist.all_reduce(acc)
         return self._logs_from(acc, n // B, prefix)
 
+    # -- scoring ----------------------------------------------------------------
+    @property
+    def metrics_names(self):
+        """Keras 2.0: the order of evaluate()'s list -- the weighted total, the four output losses, the label accuracy."""
+        return ['loss'] + [n + '_loss' for n in self.output_names] + [self.acc_name]
+
+    def _scoring_data(self, x, y):
+        dev = self.engine.device
+        cur, hist, w_true = self._split_inputs(x, y)
+        tgt = self._target_of(cur, y)
+        d_cur, d_hist = self._data_to_dev(cur, hist, dev)
+        d_tgt = None if tgt is None else self._data_to_dev(tgt, None, dev)[0]
+        return int(cur.shape[0]), d_cur, d_hist, _to_dev(w_true, dev), d_tgt
+
+    def evaluate(self, x, y, batch_size=None, verbose=0):
+        """Keras' evaluate(): [loss, the four output losses, label accuracy] (metrics_names) over the data, exactly the
+        validation pass of fit() (evaluate_device: batch-size chunks, sampling noise on, no update).  Like validation_data,
+        the number of samples must be a multiple of the model's batch size."""
+        B = self.engine.B
+        rank, world = _dp()
+        if batch_size is not None and int(batch_size) not in (B, B * world):
+            raise ValueError("model was built with batch_size %d per process, got batch_size %d" % (B, int(batch_size)))
+        n, d_cur, d_hist, d_w, d_tgt = self._scoring_data(x, y)
+        if n % B:
+            raise ValueError("evaluation samples %d not a multiple of batch_size %d" % (n, B))
+        logs = self.evaluate_device(d_cur, d_hist, d_w, d_tgt)
+        out = [float(logs[m]) for m in self.metrics_names]
+        if verbose and rank == 0:
+            print(" - ".join("%s: %.4f" % kv for kv in zip(self.metrics_names, out)))
+        return out
+
+    def log_likelihood(self, x, y, k=100, seed=0, per_window=False, use_graph=True):
+        """Importance-weighted estimate of log p(x) per window with k samples from the model's encoder:
+        {'log_likelihood' (mean over windows, nats), 'log_likelihood_per_frame' (/ T), 'elbo', 'ess', 'n_windows', 'k'}
+        and, with per_window, 'windows': {'log_p', 'elbo', 'ess'} arrays.  x, y as for fit(); the labels only feed the label
+        loss of the forward pass, which is not part of p(x).  Any number of windows (the last chunk is padded); the
+        noise is keyed by `seed`, the sample and the window, so the result does not depend on the batch size or the number
+        of ranks.  use_graph=False runs the samples as plain launches (same kernels, same result)."""
+        from .likelihood import estimate_device, summarize
+        n, d_cur, d_hist, d_w, d_tgt = self._scoring_data(x, y)
+        per = estimate_device(self, d_cur, d_hist, d_w, n, k=k, seed=seed, d_target=d_tgt, use_graph=use_graph)
+        return summarize(per, self.engine.cfg.get('T', 1), k, per_window_arrays=per_window)
+
 
 def _dp():
     """(rank, world) of the default process group, (0, 1) without one."""

@@ -658,6 +658,20 @@ def i32_add(counter, v=1):
     check(_lib.lib().clv_i32_add(_ptr(counter), int(v), _stream()), "clv_i32_add")
 
 
+def iw_accumulate(R, T, L, C1, rownll, zargs, eps_z, wargs, eps_w, w_log_var_prior, nvalid, state, step_dev=None):
+    """clv_iw_accumulate: fold one importance sample of rows < nvalid into the fp64 state [R, 4]; step_dev (device int32,
+    optional) is advanced by one after the launch's work."""
+    check(_lib.lib().clv_iw_accumulate(int(R), int(T), int(L), int(C1), _ptr(rownll), _ptr(zargs), _ptr(eps_z),
+                                       _ptr(wargs) if C1 else None, _ptr(eps_w) if C1 else None, float(w_log_var_prior),
+                                       int(nvalid), _ptr(state), _ptr(step_dev), _stream()), "clv_iw_accumulate")
+
+
+def iw_finish(R, nvalid, K, state, log_p, elbo, ess):
+    """clv_iw_finish: per-window log_p, elbo, ess (fp64 [>= nvalid]) from the state after K samples."""
+    check(_lib.lib().clv_iw_finish(int(R), int(nvalid), int(K), _ptr(state), _ptr(log_p), _ptr(elbo), _ptr(ess), _stream()),
+          "clv_iw_finish")
+
+
 def dropout_rows(R, T, n, X, ldx, U, ldu, rate, out, ldo, beta=0.0):
     """out[r, :n] = beta * out + X[r, :n] * mask(U[r // T, :n]), mask(u) = (u >= rate) / (1 - rate) (clv_dropout_rows)."""
     check(_lib.lib().clv_dropout_rows(R, T, n, _ptr(X), ldx, _ptr(U), ldu, float(rate), float(beta), _ptr(out), ldo, _stream()),

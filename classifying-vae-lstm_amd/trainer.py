@@ -18,6 +18,15 @@ from . import ops
 from .parallel import GradAllReduce, eps_first_index, meta_device
 
 
+# Philox streams of the noise draws (stream ids are uint32; every draw is further keyed by seed, step and global row):
+#   0 / 1    eps_W / eps_Z of the training steps (noise_spec, stream_offset 0)
+#   2 / 3    the LSTM input-dropout masks of a training step (VrnnEngine.forward)
+#   4 + 2j, 5 + 2j   validation chunk j (Model.evaluate_device); 2000 + 2j, 2001 + 2j: predict() chunk j
+# and, reserved for the importance-weighted likelihood (likelihood.py; step = sample k, first index from the
+# GLOBAL window index), the last pair of the range, which no other draw reaches:
+IW_STREAM_W, IW_STREAM_Z = 0xFFFFFFFE, 0xFFFFFFFF
+
+
 class DevWindows:
     """Device side of utils.pianoroll.Windows: row i = store[starts[i] + t0 : ... + T] (store uint8 or float32 [F, D],
     starts int64 [n]); the batch gather reads the overlapping windows straight from the store."""

@@ -775,6 +775,25 @@ int clv_bernoulli_sample(int64_t n, const float* p, const float* u, float* x, vo
 int clv_dropout_rows(int R, int T, int n, const float* X, int ldx, const float* U, int ldu, float rate, float beta,
                      float* out, int ldo, void* stream);
 
+/* ------------------------------------------------- importance-weighted likelihood --
+ * The K-sample importance-sampling estimate of log p(x) per window (there is no such figure in the
+ * reference, whose cl_vrnn/train.py builds the test split and never scores it).  Sample k runs the inference forward pass
+ * with eps_W / eps_Z drawn for it; clv_iw_accumulate turns what that pass leaves into the window's log weight
+ *   l = - sum_t rownll_t + sum_{t,l} 0.5 (lvz + eps_z^2 - z^2) + sum_c 0.5 (lvw + eps_w^2 - pr - s^2 / exp(pr)),
+ *   z = mz + exp(lvz/2) eps_z,  s = mw + exp(lvw/2) eps_w,  pr = w_log_var_prior
+ * (log p(x|z,w) + log p(z) - log q(z|x,w) + log p(s) - log q(s|x), in fp64) and folds it into the fp64 state [R,4] =
+ * (m, s1, s2, sum_l) of its window: m' = max(m, l), s1 = s1 e^{m-m'} + e^{l-m'}, s2 = s2 e^{2(m-m')} + e^{2(l-m')},
+ * sum_l += l.  The caller fills the state with (-inf, 0, 0, 0) before the first sample; a NaN weight makes the window NaN.
+ * Layouts as the engines hold them: rownll [R*T], zargs [R*T,2L] (mean | log_var), eps_z [R*T,L], wargs [R,2*C1]
+ * (mean | log_var), eps_w [R,C1]; C1 == 0: no label term (wargs / eps_w may be NULL).  Rows >= nvalid (the padding of a
+ * last chunk) are neither read nor written.  step_dev != NULL: the launch advances that device counter by one after its
+ * work (the eps draw of the next replay of a captured sample reads it).  One wave per window, no atomics.
+ * clv_iw_finish: per window r < nvalid, log_p = m + log(s1) - log K, elbo = sum_l / K, ess = s1^2 / s2 (fp64 outputs). */
+int clv_iw_accumulate(int R, int T, int L, int C1, const float* rownll, const float* zargs, const float* eps_z,
+                      const float* wargs, const float* eps_w, float w_log_var_prior, int nvalid, double* state,
+                      int32_t* step_dev, void* stream);
+int clv_iw_finish(int R, int nvalid, int K, const double* state, double* log_p, double* elbo, double* ess, void* stream);
+
 /* ----------------------------------------------------------------- graphs --
  * thin wrappers so a host without HIP bindings can capture a step once and
  * replay it (launch-bound inner loops: SURVEY.md 7.1 step 8). */

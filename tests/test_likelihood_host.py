@@ -1,0 +1,93 @@
+"""CPU checks of the importance-weighted likelihood surface: the two evaluate CLIs' flags and the C ABI of the
+accumulate / finish entry points (header, ctypes binding, argument checks)."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import clvae_amd  # noqa: E402,F401
+from clvae_amd import _lib  # noqa: E402
+
+NEW = ('clv_iw_accumulate', 'clv_iw_finish')
+
+
+@pytest.mark.parametrize('which', ['cl_vae', 'cl_vrnn'])
+def test_evaluate_parsers_have_the_documented_flags(which):
+    import importlib
+    mod = importlib.import_module('clvae_amd.%s.evaluate' % which)
+    p = mod.build_parser()
+    a = p.parse_args(['run1'])
+    assert a.run_name == 'run1'
+    assert a.model_file == '' and a.split == 'test' and a.k == 100 and a.seed == 0 and a.out == ''
+    assert a.train_file.endswith('.pickle')
+    a = p.parse_args(['r', '-i', 'm.h5', '--train_file', 'd.pickle', '--split', 'valid', '-k', '7', '--seed', '3',
+                      '--out', 'o.json'])
+    assert (a.model_file, a.train_file, a.split, a.k, a.seed, a.out) == ('m.h5', 'd.pickle', 'valid', 7, 3, 'o.json')
+    a = p.parse_args(['r', '--model_file', 'n.h5', '--split', 'train'])
+    assert (a.model_file, a.split) == ('n.h5', 'train')
+    with pytest.raises(SystemExit):
+        p.parse_args(['r', '--split', 'holdout'])
+
+
+def test_reference_tables_keep_their_flags():
+    from clvae_amd import cli
+    for tool in ('cl_vae.train', 'cl_vrnn.train', 'cl_vae.sample', 'cl_vrnn.sample'):
+        names = [f.names for f in cli.TABLES[tool]]
+        assert ('--split',) not in names and ('-k',) not in names and ('--out',) not in names, tool
+
+
+def test_header_and_signatures_agree_on_the_new_entry_points():
+    hdr = open(os.path.join(ROOT, "include", "clvae.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    protos = dict(re.findall(r"\b(clv_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr))
+    for name in NEW:
+        assert name in protos and name in _lib.SIGNATURES, name
+        args = [a.strip() for a in protos[name].split(",")]
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert restype is ctypes.c_int
+        assert len(args) == len(argtypes), name
+        for a, t in zip(args, argtypes):
+            if "*" in a:
+                assert t is ctypes.c_void_p, (name, a)
+            elif a.startswith("float"):
+                assert t is ctypes.c_float, (name, a)
+            else:
+                assert ctypes.sizeof(t) == 4 and t is not ctypes.c_float, (name, a)
+    assert "double* state" in protos['clv_iw_accumulate'] and "const double* state" in protos['clv_iw_finish']
+    assert re.search(r"#define CLV_ABI_VERSION 600\b", open(os.path.join(ROOT, "include", "clvae.h")).read())
+    assert _lib.ABI_VERSION == 600
+
+
+def test_new_entry_points_refuse_bad_arguments_before_touching_the_device():
+    """NULL pointers, zero sizes, nvalid outside [1, R] and K < 1 give an error code; no device is needed to get it."""
+    prog = (
+        "import sys, ctypes as C\n"
+        "sys.path.insert(0, %r)\n"
+        "import clvae_amd\n"
+        "from clvae_amd import _lib\n"
+        "L = _lib.lib()\n"
+        "P = C.c_void_p(16)\n"       # never dereferenced: every call below fails its argument check
+        "acc = L.clv_iw_accumulate\n"
+        "fin = L.clv_iw_finish\n"
+        "r = [acc(0, 1, 1, 1, P, P, P, P, P, 0.0, 1, P, None, None),\n"
+        "     acc(4, 1, 1, 1, P, P, P, P, P, 0.0, 0, P, None, None),\n"
+        "     acc(4, 1, 1, 1, P, P, P, P, P, 0.0, 5, P, None, None),\n"
+        "     acc(4, 1, 1, 1, None, P, P, P, P, 0.0, 4, P, None, None),\n"
+        "     acc(4, 1, 1, 2, P, P, P, None, None, 0.0, 4, P, None, None),\n"
+        "     acc(4, 1, 0, 0, P, P, P, None, None, 0.0, 4, P, None, None),\n"
+        "     acc(4, 1, 1, 0, P, P, P, None, None, 0.0, 4, None, None, None),\n"
+        "     fin(4, 4, 0, P, P, P, P, None),\n"
+        "     fin(4, 5, 1, P, P, P, P, None),\n"
+        "     fin(4, 4, 1, P, None, P, P, None)]\n"
+        "print(r)\n" % ROOT)
+    out = subprocess.run([sys.executable, "-c", prog], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    codes = eval(out.stdout.strip().splitlines()[-1])
+    assert codes == [-1] * len(codes), codes
