@@ -201,6 +201,8 @@ def test_cl_vae_without_hidden_layers_matches_oracle(dev, use_x_prev):
     (4, 32, 32, 10, True, 'hard_sigmoid'),      # config 5 latent size
     (1, 3, 1, 2, True, 'hard_sigmoid'),         # the smallest of everything: one sample, one latent, two classes
     (1, 1, 1, 2, False, 'sigmoid'),
+    (3, 2, 4, 6, True, 'hard_sigmoid'),         # T = 2; L = 4: top of the pair forward's Z = 1 and backward's ZP = 8 variants
+    (2, 7, 6, 4, False, 'sigmoid'),             # L = 6 at odd T: the backward's 16-column variant, one step of skew tail
 ])
 def test_cl_vrnn_step_matches_oracle(dev, B, Tn, L, Cn, use_x_prev, gate, pair):
     """pair=True: both LSTMs + latent head in one persistent launch (csrc/lstm_pair.hip) where supported."""
@@ -400,7 +402,8 @@ def test_cl_vrnn_fit_with_dropout_draws_its_masks_from_philox(dev):
 
 @pytest.mark.parametrize("exact_frames", [False, True])
 @pytest.mark.parametrize("B,Tn,L", [(256, 128, 2),         # BASELINE config 3 (and 4 per GPU): what bench.py times
-                                    (1024, 256, 32)])      # config 5 per GPU
+                                    (1024, 256, 32),       # config 5 per GPU
+                                    (1024, 32, 2)])        # the pair kernels at 1024 rows: four workgroups per CU
 def test_cl_vrnn_full_size_step_matches_oracle(dev, B, Tn, L, exact_frames):
     """One step at the sizes the benchmark runs, against the fp64 oracle on the same weights, frames and noise: ELBO
     and every loss term to 1e-3, per-note logits, both LSTMs' states, every gradient tensor.
