@@ -170,6 +170,8 @@ SIGNATURES = {
     "clv_vrnn_generate": (_i, [_i] * 9 + [_u64] + [_p] * 18),
     "clv_vae_generate_supported": (_i, [_i, _i, _i, _i]),
     "clv_vae_generate": (_i, [_i] * 8 + [_u64] + [_p] * 13),
+    "clv_vrnn_generate_clamped": (_i, [_i] * 9 + [_u64] + [_p] * 19),
+    "clv_vae_generate_clamped": (_i, [_i] * 8 + [_u64] + [_p] * 14),
     "clv_label_fwd": (_i, [_i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p]),
     "clv_label_bwd": (_i, [_i, _i, _p, _p, _i, _p, _p, _p, _p, _f, _f, _f, _f, _p, _p, _i, _p]),
     "clv_vae_fused_supported": (_i, [_i, _i, _i, _i, _i]),
@@ -209,6 +211,7 @@ SIGNATURES = {
     "clv_iw_accumulate": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _i, _p, _p, _p]),
     "clv_iw_finish": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
     "clv_bernoulli_sample": (_i, [_i64, _p, _p, _p, _p]),
+    "clv_bernoulli_sample_clamped": (_i, [_i64, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "clv_dropout_rows": (_i, [_i, _i, _i, _p, _i, _p, _i, _f, _f, _p, _i, _p]),
     "clv_graph_begin_capture": (_i, [_p]),
     "clv_graph_end_capture": (_i, [_p, C.POINTER(_p)]),

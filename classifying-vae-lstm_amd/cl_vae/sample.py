@@ -8,7 +8,8 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
-from clvae_amd.cli import DEVICE_LOOP_FLAGS, parser_for  # noqa: E402
+from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, parser_for  # noqa: E402
+from clvae_amd.harmonize import harmonize  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
@@ -25,7 +26,9 @@ class Sampler:
         self.w_enc = M.make_w_encoder(self.model, m['original_dim'])
         self.z_enc = M.make_z_encoder(self.model, m['original_dim'], m['n_classes'], dims)
         self.dec = M.make_decoder(self.model, dims, m['n_classes'], use_x_prev=m['use_x_prev'])
-        self.data = PianoData(args.train_file, batch_size=1, seq_length=args.t, squeeze_x=True)
+        # --harmonize: windows of the seed frame and the t frames whose voice is kept
+        self.data = PianoData(args.train_file, batch_size=1, seq_length=args.t + 1 if voice_of(args) else args.t,
+                              squeeze_x=True)
 
     def pick_seed(self):
         """(first frame of a random test window, its key's one-hot or None with --infer_w); one np.random draw"""
@@ -51,6 +54,23 @@ class Sampler:
             write_sample(roll, self.args.sample_dir, name, True)
         return list(rolls)
 
+    def harmonize_on_device(self, names):
+        """--harmonize: frame 0 of a random test window is the seed, the chosen voice of its next t frames the
+        constraint; writes <name>.mid (the harmonization) and <name>_source.mid (the original frames)."""
+        picks = [np.random.choice(range(len(self.data.x_test))) for _ in names]
+        wins = [np.asarray(self.data.x_test[i]).reshape(self.args.t + 1, -1) for i in picks]
+        seeds, sources = np.stack([w[0] for w in wins]), np.stack([w[1:] for w in wins])
+        if self.args.infer_w:
+            ws = [M.sample_w(self.w_enc.predict(s[None, :]), add_noise=False) for s in seeds]
+        else:
+            ws = [to_categorical(self.data.test_song_keys[i], self.margs['n_classes']) for i in picks]
+        rolls = harmonize(self.model, seeds, sources, np.vstack(ws), voice=voice_of(self.args),
+                          seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior)
+        for roll, src, name in zip(rolls, sources, names):
+            write_sample(roll, self.args.sample_dir, name, True)
+            write_sample(src, self.args.sample_dir, name + '_source', True)
+        return list(rolls)
+
 
 def make_sample(P, dec_model, w_enc_model, z_enc_model, args, margs):
     """One sample from explicit sub-models (the reference's helper, :8-19)."""
@@ -62,15 +82,23 @@ def make_sample(P, dec_model, w_enc_model, z_enc_model, args, margs):
     return roll
 
 
+def voice_of(args):
+    """--harmonize's voice, or None (also for parsers without the flag)"""
+    return getattr(args, 'harmonize', None)
+
+
 def on_device(args):
     """Where the frame loop runs: like the reference (host loop, np.random) for every -n unless --device_loop asks for
-    the device-side loop (Philox noise: other samples for the same np.random.seed, so it is opt-in)."""
-    return bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False)
+    the device-side loop (Philox noise: other samples for the same np.random.seed, so it is opt-in); --harmonize
+    always runs there."""
+    return bool(voice_of(args)) or (bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
 
 
 def sample(args):
     s = Sampler(args)
     names = ['%s_%d' % (args.run_name, i) for i in range(args.n)]
+    if voice_of(args):
+        return s.harmonize_on_device(names)
     return s.many_on_device(names) if on_device(args) else [s.one(nm) for nm in names]
 
 
@@ -79,4 +107,4 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    sample(parser_for('cl_vae.sample', DEVICE_LOOP_FLAGS).parse_args())
+    sample(parser_for('cl_vae.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS).parse_args())

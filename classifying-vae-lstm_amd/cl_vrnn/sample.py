@@ -8,7 +8,8 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
-from clvae_amd.cli import DEVICE_LOOP_FLAGS, parser_for  # noqa: E402
+from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, parser_for  # noqa: E402
+from clvae_amd.harmonize import harmonize  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
@@ -30,6 +31,9 @@ def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None)
     half_speed = 'jsb' in args.train_file.lower()
     picks = seed_windows(P, args.c, args.n)
     label_of = lambda i: None if args.infer_w else to_categorical(P.test_song_keys[i], margs['n_classes'])
+    voice = getattr(args, 'harmonize', None)
+    if voice:
+        return harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice, half_speed)
     if model is not None and len(picks):
         ws = [label_of(i) for i in picks]
         if args.infer_w:
@@ -46,6 +50,25 @@ def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None)
     return rolls
 
 
+def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice, half_speed):
+    """--harmonize: windows of 2t frames; the first t are the teacher-forced seed, the chosen voice of the next t the
+    constraint.  Writes <run>_<j>.mid (the harmonization), <run>_<j>_source.mid (the original frames) and the seed."""
+    t = args.t
+    if not len(picks):
+        return []
+    seeds = np.stack([np.asarray(P.x_test[i])[:t] for i in picks])
+    sources = np.stack([np.asarray(P.x_test[i])[t:2 * t] for i in picks])
+    ws = [label_of(i) for i in picks]
+    if args.infer_w:
+        ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in seeds]
+    rolls = list(harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0)))
+    for j, (i, roll) in enumerate(zip(picks, rolls)):
+        write_sample(roll, args.sample_dir, '%s_%d' % (args.run_name, j), half_speed)
+        write_sample(sources[j], args.sample_dir, '%s_%d_source' % (args.run_name, j), half_speed)
+        write_sample(seeds[j], args.sample_dir, '%s%d_seed_%d' % (args.run_name, j, i), half_speed)
+    return rolls
+
+
 def sample(args):
     model, _, margs = M.load_model(args.model_file, optimizer='adam')
     dims = (margs['intermediate_dim'], margs['latent_dim'])
@@ -53,9 +76,11 @@ def sample(args):
     z_enc = M.make_z_encoder(model, margs['original_dim'], margs['n_classes'], dims)
     dec = M.make_decoder(model, margs['original_dim'], margs['intermediate_dim'], margs['latent_dim'],
                          margs['n_classes'], margs['use_x_prev'])
-    P = PianoData(args.train_file, batch_size=1, seq_length=args.t, squeeze_x=False)
+    voice = getattr(args, 'harmonize', None)
+    # --harmonize: windows of the seed's t frames and the t frames whose voice is kept
+    P = PianoData(args.train_file, batch_size=1, seq_length=2 * args.t if voice else args.t, squeeze_x=False)
     # the reference's host loop (np.random) for every -n; --device_loop opts into the device-side loop (Philox noise)
-    on_device = bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False)
+    on_device = bool(voice) or (bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
     return gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
 
 
@@ -64,4 +89,4 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    sample(parser_for('cl_vrnn.sample', DEVICE_LOOP_FLAGS).parse_args())
+    sample(parser_for('cl_vrnn.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS).parse_args())

@@ -106,6 +106,13 @@ DEVICE_LOOP_FLAGS = [
     Flag(('--seed',), int, 0, 'noise key of the device-side loop'),
 ]
 
+# harmonization (not in the reference): keep one voice of test frames and generate the others (implies --device_loop)
+HARMONIZE_CHOICES = ('top', 'bottom')
+HARMONIZE_FLAGS = [
+    Flag(('--harmonize',), str, None, 'keep the top or bottom voice of the -t test frames after the seed and generate '
+                                      'the other voices (clamped sampling on the device; implies --device_loop)'),
+]
+
 
 def parser_for(tool, extra=()):
     p = argparse.ArgumentParser()
@@ -114,6 +121,8 @@ def parser_for(tool, extra=()):
             p.add_argument(*f.names, action=ON, help=f.help)
         elif f.names == ('--split',):
             p.add_argument(*f.names, type=f.kind, default=f.default, choices=SPLIT_CHOICES, help=f.help)
+        elif f.names == ('--harmonize',):
+            p.add_argument(*f.names, type=f.kind, default=f.default, choices=HARMONIZE_CHOICES, help=f.help)
         elif f.names[0].startswith('-'):
             p.add_argument(*f.names, type=f.kind, default=f.default, help=f.help)
         else:

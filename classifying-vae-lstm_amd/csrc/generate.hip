@@ -41,6 +41,7 @@ struct GenArgs {
   const float* bo;              // [88]
   float* Xs;                    // [N,nsteps,88]
   float* xhat;                  // [N,S+nsteps,88] or null
+  const uint8_t* clamp;         // [N,nsteps,88] (CL instances): row j constrains Xs[n,j], drawn at step S+j
 };
 
 // slice_matvec with half the live registers: the h slice is consumed in two halves of 12 (the kernel is at its
@@ -80,7 +81,9 @@ __device__ __forceinline__ void frame_masks(const float* xbuf, int lane, float& 
 // ZW = false: latent_dim <= 16, the head rides in the surplus lane groups of the encoder's last wave (4 barriers per
 // frame).  ZW = true: latent_dim <= 32, every encoder lane group < 2L owns one head column (22 more registers), the
 // head's outputs meet in LDS and L lanes draw z (5 barriers per frame).
-template <int GATE, bool ZW>
+// CL = true: clamped ancestral sampling: the note drawn at step t >= S is replaced by clamp[n, t-S, u] where that byte is 0
+// or 1 (any other byte leaves the draw); the clamped frame is stored and fed back as the next input.  CL = false folds away.
+template <int GATE, bool ZW, bool CL>
 __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   constexpr int GN_LQ = (ZW ? GN_LWIDE : GN_LMAX) / PK;
   extern __shared__ __attribute__((aligned(16))) float Kxl[];            // encoder input kernel [88][352], then Wo [88][88]
@@ -90,6 +93,8 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   __shared__ float zargs_l[2 * GN_LWIDE];
   __shared__ float xbuf[128];
   __shared__ float wbuf[GN_CMAX];
+  __shared__ float bo_l[CL ? 128 : 1];          // CL: the output bias, read in phase 4 instead of held in a register
+  __shared__ uint8_t cbuf[CL ? 128 : 1];        // CL: the constraint byte of the current step, one per writer lane
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool enc = wave < GN_NW;
@@ -119,6 +124,8 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   if (tid < GN_LWIDE) zbuf[tid] = 0.f;
   if (tid < 128) xbuf[tid] = (a.S > 0 && tid < LH) ? a.x_seed[((size_t)n * a.S) * LH + tid] : 0.f;
   if (tid < a.C) wbuf[tid] = a.w[(size_t)n * a.C + tid];
+  if (CL && tid < LH) bo_l[tid] = a.bo[tid];
+  if (CL && a.S == 0 && tid < LH) cbuf[tid] = a.clamp[(size_t)n * a.nsteps * LH + tid];      // step 0's row
   __syncthreads();
 
   // recurrent kernel slice of this lane's unit (gate pairs), per-sequence bias W.K_w + b of its gate s
@@ -176,7 +183,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
       }
   }
   if (enc) {
-    bor = a.bo[u];
+    if (!CL) bor = a.bo[u];
     const float bzv = a.bz[max(zcol(s), 0)];
     bzr = lat_ok ? bzv : 0.f;
   }
@@ -190,6 +197,8 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   const bool zdraw = ZW ? (tid < L) : (lat_ok && s < 2);            // lanes that own a latent's eps
   const uint64_t zidx = (uint64_t)n * L + (ZW ? tid : lat);
   float e_cur = zdraw ? philox_normal_at(zidx, a.k0, a.k1, 0u, 0u) : 0.f;
+  const uint32_t crow = CL ? ((uint32_t)n * (uint32_t)a.nsteps - (uint32_t)a.S) * (uint32_t)LH : 0u;   // clamp row of step 0
+  float seed_carry = 0.f;                         // CL: the constraint byte requested one frame ago
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1;
     float x0, x1;
@@ -197,7 +206,14 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     frame_masks(xbuf, lane, x0, x1, m0, m1);       // xbuf = input frame of step t (seed frame or last sample)
     float u_cur = 0.f;
     float seed_next = 0.f;                         // teacher forcing: next seed frame, requested a whole frame early
+    // CL: the constraint byte of the NEXT sampled step rides in the same register, which holds no seed frame where
+    // t+1 >= S; it is requested a whole frame early like the seed, and parked in LDS at the top of that next frame
+    // (this lane alone writes and reads cbuf[u]).  32-bit offset from the roll's base
+    if (CL && enc && writer && t >= a.S && t > 0) cbuf[u] = (uint8_t)__builtin_bit_cast(uint32_t, seed_carry);
     if (enc && writer && t + 1 < a.S) seed_next = a.x_seed[((size_t)n * a.S + t + 1) * LH + u];
+    if (CL && enc && writer && t + 1 >= a.S && t + 1 < T)
+      seed_next = __builtin_bit_cast(float, (uint32_t)a.clamp[crow + (uint32_t)(t + 1) * LH + (uint32_t)u]);
+    if (CL) seed_carry = seed_next;
     // ---- phase 1: encoder cell (enc waves) | decoder input-kernel rows from L2 (dec waves) ------------------------
     float xd = 0.f;
     if (enc) {
@@ -320,6 +336,12 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     } else {
       // encoder waves are idle here: draw this frame's Bernoulli uniforms and the next frame's latent noise
       if (writer) u_cur = philox_uniform_at((uint64_t)n * LH + u, a.k0, a.k1, 1u, (uint32_t)t);
+      // CL: a clamped note's uniform (drawn and discarded) becomes 2 (forced off: never <= p) or -1 (forced on: always
+      // <= p, p in [0, 1]), so phase 4 samples the constraint with no extra work; any other byte leaves the draw
+      if (CL && writer && t >= a.S) {
+        const uint32_t cb = cbuf[u];
+        u_cur = cb == 0u ? 2.f : (cb == 1u ? -1.f : u_cur);
+      }
       if (zdraw) e_cur = philox_normal_at(zidx, a.k0, a.k1, 0u, (uint32_t)(t + 1));
     }
     step_barrier();
@@ -340,7 +362,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
       float acc = acc0 + acc1;
       acc = reduce_slices<PK>(acc);
       if (writer) {
-        const float p = sigmoidf_(acc + bor);
+        const float p = sigmoidf_(acc + (CL ? bo_l[u] : bor));
         const float xs = u_cur <= p ? 1.f : 0.f;
         if (a.xhat) a.xhat[((size_t)n * T + t) * LH + u] = p;
         if (t >= a.S) a.Xs[((size_t)n * a.nsteps + (t - a.S)) * LH + u] = xs;
@@ -358,13 +380,12 @@ extern "C" int clv_vrnn_generate_supported(int D, int H, int L, int C) {
   return D == clv::LH && H == clv::LH && L >= 1 && L <= clv::GN_LWIDE && C >= 1 && C <= clv::GN_CMAX;
 }
 
-extern "C" int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
-                                 uint64_t seed, const float* x_seed, const float* w,
-                                 const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                                 const float* Wz, const float* bz,
-                                 const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                                 const float* U_dec, const float* Wo, const float* bo,
-                                 float* Xs, float* xhat, void* stream) {
+namespace {
+int vrnn_generate_launch(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior, uint64_t seed,
+                         const float* x_seed, const float* w, const float* Kx_enc, const float* Kw_enc, const float* b_enc,
+                         const float* U_enc, const float* Wz, const float* bz, const float* Kx_dec, const float* Kz,
+                         const float* Kw_dec, const float* b_dec, const float* U_dec, const float* Wo, const float* bo,
+                         const uint8_t* clamp, float* Xs, float* xhat, void* stream) {
   using namespace clv;
   if (!clv_vrnn_generate_supported(D, H, L, C) || N <= 0 || S < 0 || nsteps < 0 || S + nsteps <= 0) return CLV_EINVAL;
   if (gate_act != CLV_GATE_HARD_SIGMOID && gate_act != CLV_GATE_SIGMOID) return CLV_EINVAL;
@@ -372,15 +393,45 @@ extern "C" int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, 
       !U_dec || !Wo || !bo || (nsteps > 0 && !Xs))
     return CLV_EINVAL;
   if (((uintptr_t)Kx_enc) % 16 != 0) return CLV_EINVAL;
+  if (clamp && (uint64_t)N * nsteps * LH > UINT32_MAX) return CLV_EINVAL;      // the kernel addresses the roll in 32 bits
   hipStream_t s = (hipStream_t)stream;
   GenArgs a{N, S, nsteps, L, C, z_prior, Kx_dec != nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), x_seed, w,
-            Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat};
+            Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp};
   const size_t lds = (size_t)(LH * LG + LH * LH) * sizeof(float);
   const bool hard = gate_act == CLV_GATE_HARD_SIGMOID, wide = L > GN_LMAX;
-  void (*kern)(GenArgs) = hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true> : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false>)
-                               : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true> : vrnn_generate_kernel<CLV_GATE_SIGMOID, false>);
+  void (*kern)(GenArgs);
+  if (clamp)
+    kern = hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true> : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true>)
+                : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true> : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true>);
+  else
+    kern = hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, false> : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, false>)
+                : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, false> : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, false>);
   if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 156 * 1024)) return e;
-  ProfScope p("vrnn_generate", s);
+  ProfScope p(clamp ? "vrnn_generate_clamped" : "vrnn_generate", s);
   hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
   return launch_status();
+}
+}  // namespace
+
+extern "C" int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
+                                 uint64_t seed, const float* x_seed, const float* w,
+                                 const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                                 const float* Wz, const float* bz,
+                                 const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                                 const float* U_dec, const float* Wo, const float* bo,
+                                 float* Xs, float* xhat, void* stream) {
+  return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
+                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, nullptr, Xs, xhat, stream);
+}
+
+extern "C" int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
+                                         uint64_t seed, const float* x_seed, const float* w,
+                                         const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                                         const float* Wz, const float* bz,
+                                         const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                                         const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                                         float* Xs, float* xhat, void* stream) {
+  if (!clamp || nsteps <= 0) return CLV_EINVAL;
+  return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
+                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, Xs, xhat, stream);
 }

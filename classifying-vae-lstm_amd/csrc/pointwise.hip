@@ -443,6 +443,22 @@ __global__ void bernoulli_sample_kernel(int64_t n, const float* p, const float* 
   if (i < n) x[i] = (u[i] <= p[i]) ? 1.f : 0.f;
 }
 
+// sample_x under a constraint roll [R, nsteps, D] (R = n / D rows): step c = *step_dev (the counter the Philox draws of the
+// captured frame read); c >= S takes row c - S of every sequence: byte 0 / 1 forces the note, any other byte leaves the draw
+__global__ void bernoulli_sample_clamped_kernel(int64_t n, int D, int nsteps, int S, const float* p, const float* u,
+                                                const uint8_t* clamp, const int32_t* step_dev, float* x) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float xs = (u[i] <= p[i]) ? 1.f : 0.f;
+  const int k = *step_dev - S;
+  if (k >= 0 && k < nsteps) {
+    const int64_t r = i / D, j = i - r * D;
+    const uint8_t cb = clamp[(r * nsteps + k) * D + j];
+    if (cb <= 1) xs = (float)cb;
+  }
+  x[i] = xs;
+}
+
 }  // namespace clv
 
 using namespace clv;
@@ -539,6 +555,16 @@ extern "C" int clv_bernoulli_sample(int64_t n, const float* p, const float* u, f
   hipStream_t s = (hipStream_t)stream;
   ProfScope pr("bernoulli_sample", s);
   hipLaunchKernelGGL(bernoulli_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, p, u, x);
+  return launch_status();
+}
+
+extern "C" int clv_bernoulli_sample_clamped(int64_t n, int D, int nsteps, int S, const float* p, const float* u,
+                                            const uint8_t* clamp, const int32_t* step_dev, float* x, void* stream) {
+  if (n <= 0 || D <= 0 || nsteps <= 0 || S < 0 || n % D != 0 || !p || !u || !clamp || !step_dev || !x) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("bernoulli_sample_clamped", s);
+  hipLaunchKernelGGL(bernoulli_sample_clamped_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, D, nsteps, S, p, u,
+                     clamp, step_dev, x);
   return launch_status();
 }
 

@@ -36,6 +36,7 @@ struct VaeGenArgs {
   const float* bo;              // [88]
   float* Xs;                    // [N,nsteps,88]
   float* xhat;                  // [N,nsteps,88] or null
+  const uint8_t* clamp;         // [N,nsteps,88] (CL instance): row t constrains frame t
 };
 
 // sum over the notes that are on (two scalar masks: inputs 0..63 / 64..87) of row n of an LDS-resident [88][88] kernel,
@@ -58,6 +59,9 @@ __device__ __forceinline__ float gather_rows(const float* Kl, int j, unsigned lo
   return acc0 + acc1;
 }
 
+// CL = true: clamped ancestral sampling: the note drawn at frame t is replaced by clamp[n, t, o] where that byte is 0 or 1
+// (any other byte leaves the draw); the clamped frame is stored and is the next input.  CL = false folds away.
+template <bool CL>
 __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   extern __shared__ __attribute__((aligned(16))) float vg_lds[];
   float* Khl = vg_lds;                        // [88][88] frame rows of the z-encoder's hidden kernel
@@ -113,6 +117,8 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   for (int t = 0; t < a.nsteps; ++t) {
     // this frame's noise, drawn before anything depends on it
     const float u_cur = writer ? philox_uniform_at((uint64_t)n * LH + o, a.k0, a.k1, 1u, (uint32_t)t) : 2.f;
+    // this frame's constraint, requested three barriers before phase 4 uses it (2: free)
+    const uint32_t cb = (CL && writer) ? (uint32_t)a.clamp[((size_t)n * a.nsteps + t) * LH + o] : 2u;
     const bool zdraw = s == 0 && zslot && !(o_raw & 1);                 // the mean slot of latent l = o_raw / 2
     const float eps = zdraw ? philox_normal_at((uint64_t)n * L + (o_raw >> 1), a.k0, a.k1, 0u, (uint32_t)t) : 0.f;
     // 1. z-encoder hidden layer: relu(x_prev . K_h[frame rows] + (w . K_h[label rows] + b_h))
@@ -155,7 +161,8 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
       const float lg = reduce_slices<PK>(acc0 + acc1) + bor;
       if (writer) {
         const float p = sigmoidf_(lg);
-        const float xs = u_cur <= p ? 1.f : 0.f;
+        float xs = u_cur <= p ? 1.f : 0.f;
+        if (CL && cb <= 1u) xs = (float)cb;         // 0: forced off, 1: forced on, else free (the draw stands)
         if (a.xhat) a.xhat[((size_t)n * a.nsteps + t) * LH + o] = p;
         a.Xs[((size_t)n * a.nsteps + t) * LH + o] = xs;
         xbuf[(t + 1) & 1][o] = xs;
@@ -176,19 +183,39 @@ extern "C" int clv_vae_generate_supported(int D, int H, int L, int C) {
   return D == clv::LH && H == clv::LH && L >= 1 && L <= clv::VG_LMAX && C >= 1 && C <= clv::VG_CMAX;
 }
 
-extern "C" int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
-                                const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
-                                const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
-                                float* Xs, float* xhat, void* stream) {
+namespace {
+int vae_generate_launch(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
+                        const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz, const float* bz,
+                        const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp, float* Xs,
+                        float* xhat, void* stream) {
   using namespace clv;
   if (!clv_vae_generate_supported(D, H, L, C) || N <= 0 || nsteps <= 0) return CLV_EINVAL;
   if (!x_seed || !w || !Kh || !bh || !Kz || !bz || !Kd || !bd || !Ko || !bo || !Xs) return CLV_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   VaeGenArgs a{N, nsteps, L, C, z_prior, use_x_prev != 0, (uint32_t)seed, (uint32_t)(seed >> 32), x_seed, w, Kh, bh, Kz, bz, Kd, bd,
-               Ko, bo, Xs, xhat};
+               Ko, bo, Xs, xhat, clamp};
   const size_t lds = (size_t)(2 * LH * LH + VG_LMAX * LH) * sizeof(float);
-  if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(vae_generate_kernel), 96 * 1024)) return e;
-  ProfScope p("vae_generate", s);
-  hipLaunchKernelGGL(vae_generate_kernel, dim3(N), dim3(VG_NT), lds, s, a);
+  void (*kern)(VaeGenArgs) = clamp ? vae_generate_kernel<true> : vae_generate_kernel<false>;
+  if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 96 * 1024)) return e;
+  ProfScope p(clamp ? "vae_generate_clamped" : "vae_generate", s);
+  hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
   return launch_status();
+}
+}  // namespace
+
+extern "C" int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
+                                const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
+                                const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
+                                float* Xs, float* xhat, void* stream) {
+  return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
+                             nullptr, Xs, xhat, stream);
+}
+
+extern "C" int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
+                                        uint64_t seed, const float* x_seed, const float* w, const float* Kh, const float* bh,
+                                        const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
+                                        const float* bo, const uint8_t* clamp, float* Xs, float* xhat, void* stream) {
+  if (!clamp) return CLV_EINVAL;
+  return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
+                             clamp, Xs, xhat, stream);
 }

@@ -1,6 +1,7 @@
 """Sampling on the device: the frame loops of generate_sample (cl_vae/model.py:9-42, cl_vrnn/model.py:9-60) for N sequences
 at once, and the stateful single-step sub-models of cl_vrnn (cl_vrnn/model.py:116-162).  Mixins of engine.VaeEngine /
 engine.VrnnEngine: they use the engines' buffers, parameters and forward pieces."""
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -11,16 +12,37 @@ def _f(device, *shape):
     return torch.zeros(*shape, dtype=torch.float32, device=device)
 
 
+def clamp_roll(clamp, N, nsteps, D, device):
+    """A constraint roll for generate(clamp=...): uint8 [N, nsteps, D], one row per returned frame; 0 forces the note off,
+    1 forces it on, any other value (harmonize.FREE = 255) leaves it free.  numpy or torch in, contiguous device tensor out;
+    ValueError on a wrong shape or dtype."""
+    if clamp is None:
+        return None
+    if isinstance(clamp, torch.Tensor):
+        if clamp.dtype != torch.uint8:
+            raise ValueError("clamp must be uint8, got %s" % clamp.dtype)
+    else:
+        clamp = np.asarray(clamp)
+        if clamp.dtype != np.uint8:
+            raise ValueError("clamp must be uint8, got %s" % clamp.dtype)
+        clamp = torch.from_numpy(np.ascontiguousarray(clamp))
+    if tuple(clamp.shape) != (int(N), int(nsteps), int(D)):
+        raise ValueError("clamp must have shape %s, got %s" % ((int(N), int(nsteps), int(D)), tuple(clamp.shape)))
+    return clamp.to(device).contiguous()
+
+
 class VaeGenerate:
-    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None):
+    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None):
         """N independent sequences of `nsteps` frames on the device: the frame loop of cl_vae/model.py:28-41
         (z-encoder on the last frame, z ~ N(mean, exp(lv)) or N(0, 1), decoder on (w, z, frame before last),
         x ~ Bernoulli); eps and u come from the Philox streams 0 / 1 at step = frame index.  x_seed [N,D], w [N,C] device
         tensors.  persistent=True (default where the shapes allow): the whole loop is ONE kernel, a workgroup per
         sequence (csrc/vae_generate.hip; any N); otherwise the layer chain captured once as a hipGraph and replayed per
-        frame (N <= batch size).  Same noise, same samples either way."""
+        frame (N <= batch size).  Same noise, same samples either way.  clamp: constraint roll [N,nsteps,D] (clamp_roll;
+        row t constrains frame t, which is then fed back like a sampled one: clamped ancestral sampling)."""
         cfg, d = self.cfg, self.device
         N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
+        clamp = clamp_roll(clamp, N, nsteps, D, d)
         if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
             P = self.P
             f = dict(dtype=torch.float32, device=d)
@@ -28,7 +50,7 @@ class VaeGenerate:
             ops.vae_generate(N, nsteps, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], z_prior, seed,
                              x_seed.to(**f).contiguous(), w.to(**f).contiguous(), P.p('h/kernel'), P.p('h/bias'),
                              P.p('zargs/kernel'), P.p('zargs/bias'), P.p('decoder_h/kernel'), P.p('decoder_h/bias'),
-                             P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs, xhat_out)
+                             P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs, xhat_out, clamp=clamp)
             return Xs
         if N > self.B:
             raise ValueError("%d sequences exceed the engine's batch size %d" % (N, self.B))
@@ -47,7 +69,10 @@ class VaeGenerate:
             ops.gauss_fwd(N, L, self.zargs, eps, self.z, L, None)
             self.decode(w, self.z, hist if cfg['use_x_prev'] else None, N, act=ACT_SIGMOID)
             ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
-            ops.bernoulli_sample(N * D, self.logits, u, x_next)
+            if clamp is None:
+                ops.bernoulli_sample(N * D, self.logits, u, x_next)
+            else:
+                ops.bernoulli_sample_clamped(N * D, D, nsteps, 0, self.logits, u, clamp, counter, x_next)
             ops.i32_add(counter, 1)
             hist.copy_(x_in)            # the decoder's history lags the encoder input by one frame
             x_in.copy_(x_next)
@@ -111,17 +136,25 @@ class VrnnGenerate:
         g(st['hs'], P.p('X_decoded_mean/kernel'), st['xhat'], B, D, H, bias=P.p('X_decoded_mean/bias'),
           act=ACT_SIGMOID, ws=ws)
 
-    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None):
+    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None):
         """Autoregressive generation of N independent sequences on the device.  persistent=True (default where the
         shapes allow): the whole frame loop is ONE kernel, a workgroup per sequence (csrc/generate.hip); otherwise the
         per-frame chain below, captured once and replayed per frame.  Same Philox noise either way.
-        xhat_out [N,S+nsteps,D] (persistent path only) receives every frame's note probabilities."""
+        xhat_out [N,S+nsteps,D] (persistent path only) receives every frame's note probabilities.
+        clamp: constraint roll [N,nsteps,D] (engine_generate.clamp_roll): row j constrains the returned frame Xs[:, j],
+        drawn at step S+j; the bridge sample of step S-1 stays free (clamped ancestral sampling).  The
+        persistent kernel addresses the roll in 32 bits: a roll of 2^32 bytes or more takes the frame chain."""
         cfg = self.cfg
+        clamp = clamp_roll(clamp, int(x_seed.shape[0]), nsteps, cfg['D'], self.device)
+        if clamp is not None and nsteps == 0:
+            clamp = None                # nothing is returned, so nothing is constrained
+        if clamp is not None and clamp.numel() >= 2 ** 32:
+            persistent = False
         if persistent and ops.vrnn_generate_supported(cfg['D'], cfg['H'], cfg['L'], cfg['C']):
-            return self._generate_persistent(x_seed, w, nsteps, seed, z_prior, xhat_out)
-        return self._generate_frames(x_seed, w, nsteps, seed, use_graph, z_prior)
+            return self._generate_persistent(x_seed, w, nsteps, seed, z_prior, xhat_out, clamp)
+        return self._generate_frames(x_seed, w, nsteps, seed, use_graph, z_prior, clamp)
 
-    def _generate_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out):
+    def _generate_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp=None):
         cfg, P, d = self.cfg, self.P, self.device
         D, H, L, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.off
         N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
@@ -132,10 +165,10 @@ class VrnnGenerate:
                           P.p('encoder_h/recurrent_kernel'), P.p('Zargs/kernel'), P.p('Zargs/bias'),
                           P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
                           rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
-                          P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out)
+                          P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out, clamp=clamp)
         return Xs
 
-    def _generate_frames(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False):
+    def _generate_frames(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, clamp=None):
         """Batched autoregressive generation on the device (the hot loop of cl_vrnn/model.py:47-59 for N
         independent sequences at once, noise from Philox instead of np.random).
         x_seed [N,S,D] device tensor (teacher-forced frames, S may be 0), w [N,C]; returns Xs [N,nsteps,D].
@@ -160,7 +193,10 @@ class VrnnGenerate:
             ops.gauss_fwd(N, L, st['zargs'], eps, z, L, None)
             self.dec_step(z, x_prev if cfg['use_x_prev'] else None, w, st)
             ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
-            ops.bernoulli_sample(N * D, st['xhat'], u, x_next)
+            if clamp is None:
+                ops.bernoulli_sample(N * D, st['xhat'], u, x_next)
+            else:               # the row of step counter - S: none for the seed steps and the bridge
+                ops.bernoulli_sample_clamped(N * D, D, nsteps, S, st['xhat'], u, clamp, counter, x_next)
             ops.i32_add(counter, 1)
             x_prev.copy_(x_next)
 

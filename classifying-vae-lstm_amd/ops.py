@@ -356,22 +356,34 @@ def vrnn_generate_supported(D, H, L, Cn):
 
 
 def vrnn_generate(N, S, nsteps, D, H, L, Cn, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
-                  Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None):
-    check(_lib.lib().clv_vrnn_generate(N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed), _ptr(x_seed),
-                                       _ptr(w), _ptr(Kx_enc), _ptr(Kw_enc), _ptr(b_enc), _ptr(U_enc), _ptr(Wz), _ptr(bz),
-                                       _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec), _ptr(U_dec), _ptr(Wo), _ptr(bo),
-                                       _ptr(Xs), _ptr(xhat), _stream()), "clv_vrnn_generate")
+                  Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None):
+    """cl_vrnn frame loop for N sequences in one persistent launch (csrc/generate.hip); clamp: uint8 [N,nsteps,D]
+    constraint roll (clv_vrnn_generate_clamped) or None."""
+    args = [N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed), _ptr(x_seed), _ptr(w), _ptr(Kx_enc),
+            _ptr(Kw_enc), _ptr(b_enc), _ptr(U_enc), _ptr(Wz), _ptr(bz), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec),
+            _ptr(U_dec), _ptr(Wo), _ptr(bo)]
+    if clamp is None:
+        check(_lib.lib().clv_vrnn_generate(*args, _ptr(Xs), _ptr(xhat), _stream()), "clv_vrnn_generate")
+    else:
+        check(_lib.lib().clv_vrnn_generate_clamped(*args, _ptr(clamp), _ptr(Xs), _ptr(xhat), _stream()),
+              "clv_vrnn_generate_clamped")
 
 
 def vae_generate_supported(D, H, L, Cn):
     return bool(_lib.lib().clv_vae_generate_supported(D, H, L, Cn))
 
 
-def vae_generate(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs, xhat=None):
-    """cl_vae frame loop for N sequences in one persistent launch (csrc/vae_generate.hip)."""
-    check(_lib.lib().clv_vae_generate(N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed), _ptr(x_seed),
-                                      _ptr(w), _ptr(Kh), _ptr(bh), _ptr(Kz), _ptr(bz), _ptr(Kd), _ptr(bd), _ptr(Ko), _ptr(bo),
-                                      _ptr(Xs), _ptr(xhat), _stream()), "clv_vae_generate")
+def vae_generate(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs, xhat=None,
+                 clamp=None):
+    """cl_vae frame loop for N sequences in one persistent launch (csrc/vae_generate.hip); clamp: uint8 [N,nsteps,D]
+    constraint roll (clv_vae_generate_clamped) or None."""
+    args = [N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed), _ptr(x_seed), _ptr(w), _ptr(Kh),
+            _ptr(bh), _ptr(Kz), _ptr(bz), _ptr(Kd), _ptr(bd), _ptr(Ko), _ptr(bo)]
+    if clamp is None:
+        check(_lib.lib().clv_vae_generate(*args, _ptr(Xs), _ptr(xhat), _stream()), "clv_vae_generate")
+    else:
+        check(_lib.lib().clv_vae_generate_clamped(*args, _ptr(clamp), _ptr(Xs), _ptr(xhat), _stream()),
+              "clv_vae_generate_clamped")
 
 
 def lstm_pair_supported(L, H=88):
@@ -680,6 +692,12 @@ def dropout_rows(R, T, n, X, ldx, U, ldu, rate, out, ldo, beta=0.0):
 
 def bernoulli_sample(n, p, u, x):
     check(_lib.lib().clv_bernoulli_sample(n, _ptr(p), _ptr(u), _ptr(x), _stream()), "clv_bernoulli_sample")
+
+
+def bernoulli_sample_clamped(n, D, nsteps, S, p, u, clamp, step_dev, x):
+    """bernoulli_sample under the constraint roll clamp [n/D, nsteps, D] (uint8): row *step_dev - S, none before step S."""
+    check(_lib.lib().clv_bernoulli_sample_clamped(n, D, nsteps, S, _ptr(p), _ptr(u), _ptr(clamp), _ptr(step_dev), _ptr(x),
+                                                  _stream()), "clv_bernoulli_sample_clamped")
 
 
 class Graph:

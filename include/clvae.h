@@ -405,6 +405,20 @@ int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, int C, int 
                       const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                       const float* U_dec, const float* Wo, const float* bo,
                       float* Xs, float* xhat, void* stream);
+/* ... under a CONSTRAINT ROLL (clamped ancestral sampling): clamp [N,nsteps,D] uint8, one row per returned
+ * frame; byte 0 forces the note off, 1 forces it on, any other byte (Python: FREE = 255) leaves it free.  The draw is made
+ * as above (u is drawn for a clamped note too and discarded), then the constraint replaces it; the clamped frame is
+ * stored to Xs and fed back as the next input.  xhat keeps the model's own probabilities.  BRIDGE RULE: with S > 0 the
+ * sample drawn at step S-1 feeds step S but is not returned; it stays unconstrained, and row j applies to the sample drawn
+ * at step S+j, Xs[n,j].  An all-free roll gives bit for bit the frames of clv_vrnn_generate.  nsteps >= 1, clamp != NULL,
+ * N*nsteps*D < 2^32. */
+int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
+                              uint64_t seed, const float* x_seed, const float* w,
+                              const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                              const float* Wz, const float* bz,
+                              const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                              const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                              float* Xs, float* xhat, void* stream);
 
 /* ------------------------------------------------- cl_vae generation, persistent --
  * cl_vae/model.py:9-42 (generate_sample's frame loop) for N independent sequences, one workgroup per sequence for its
@@ -421,6 +435,13 @@ int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_pr
                      const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
                      const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
                      float* Xs, float* xhat, void* stream);
+/* ... under a constraint roll clamp [N,nsteps,D] uint8 (encoding as clv_vrnn_generate_clamped): row t constrains frame t,
+ * which is then the next input (and the decoder's history one frame later).  xhat keeps the model's own probabilities; an
+ * all-free roll gives bit for bit the frames of clv_vae_generate.  clamp != NULL. */
+int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
+                             const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
+                             const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
+                             const uint8_t* clamp, float* Xs, float* xhat, void* stream);
 
 /* ------------------------------------------------------------ pointwise --
  * logistic-normal label sample + its two losses, one thread per row:
@@ -767,6 +788,11 @@ int clv_philox_normal2(float* out0, int64_t n0, uint32_t stream_id0, uint64_t fi
 int clv_i32_add(int32_t* counter, int32_t v, void* stream);
 /* x[i] = (u[i] <= p[i]) ? 1 : 0   -- sample_x */
 int clv_bernoulli_sample(int64_t n, const float* p, const float* u, float* x, void* stream);
+/* ... under a constraint roll clamp [n/D, nsteps, D] uint8 (encoding as clv_vrnn_generate_clamped), for the per-frame
+ * chains replayed from one captured graph: with c = *step_dev (the device step counter of the frame's Philox draws), c >= S
+ * applies row c - S of every sequence, c < S (teacher-forced steps and the bridge) and c >= S + nsteps apply none. */
+int clv_bernoulli_sample_clamped(int64_t n, int D, int nsteps, int S, const float* p, const float* u, const uint8_t* clamp,
+                                 const int32_t* step_dev, float* x, void* stream);
 /* Input dropout of an LSTM in the training phase (get_model(dropout=p): cl_vrnn/model.py:164,198,227; Keras 2.0.0
  * recurrent.py, implementation 0: one mask per gate and sample, constant over the time steps, K.dropout(ones, p) =
  * floor(1 - p + u) / (1 - p)):   out[r, c] = beta * out[r, c] + X[r, c] * m(U[r / T, c]),   m(u) = (u >= rate) / (1 - rate),
