@@ -1,4 +1,4 @@
-"""Shared test helpers (no GPU needed)."""
+"""Shared test helpers (no GPU needed, except by Bufs)."""
 import os
 import pickle
 
@@ -89,3 +89,45 @@ def write_jsb_pickle(which, path):
 
 def write_jsb_cs_pickle(path):
     return write_jsb_pickle('Cs', path)
+
+
+CANARY = 4321.0
+TAIL = 64               # canary elements behind every output buffer
+CANARY_U8, FILL_U8 = 0x5A, 0xA5       # uint8 buffers: canary behind, FILL inside (no NaN byte; the tests never expect 0xA5)
+
+
+class Bufs:
+    """output buffers of a kernel test: NaN (uint8: FILL_U8) inside, CANARY behind and in the padding columns of strided ones"""
+
+    def __init__(self, dev):
+        self.dev, self.all = dev, []
+
+    def out(self, *shape, pad_cols=0, dtype=None):
+        import torch
+        dtype = dtype or torch.float32
+        u8 = dtype == torch.uint8
+        canary = CANARY_U8 if u8 else CANARY
+        n = int(np.prod(shape))
+        raw = torch.full((n + TAIL,), canary, dtype=dtype, device=self.dev)
+        v = raw[:n].view(*shape)
+        v.fill_(FILL_U8 if u8 else float('nan'))
+        if pad_cols:
+            v[..., shape[-1] - pad_cols:] = canary
+        self.all.append((raw, n, shape, pad_cols, canary))
+        return v
+
+    def inp(self, a):
+        """an input that the kernel also overwrites (the gate buffers): canary tail checked like an output's"""
+        import torch
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        raw = torch.full((a.size + TAIL,), CANARY, dtype=torch.float32, device=self.dev)
+        raw[:a.size] = torch.as_tensor(a.reshape(-1), device=self.dev)
+        self.all.append((raw, a.size, a.shape, 0, CANARY))
+        return raw[:a.size].view(*a.shape)
+
+    def check_canaries(self):
+        for raw, n, shape, pad, canary in self.all:
+            r = raw.cpu().numpy()
+            assert (r[n:] == canary).all(), ("write behind a buffer", shape)
+            if pad:
+                assert (r[:n].reshape(shape)[..., shape[-1] - pad:] == canary).all(), ("padding column written", shape)

@@ -30,12 +30,11 @@ torch = pytest.importorskip("torch")
 from oracle import clvae_oracle as O
 from oracle import philox as OP
 import pair_reference as PR
+from helpers import Bufs
 
 pytestmark = pytest.mark.gpu
 
 H, G4 = PR.H, PR.G4
-CANARY = 4321.0
-TAIL = 64               # canary floats behind every output buffer
 KL_SCALE = 0.37
 DELTA = 1e-4            # hard-sigmoid coefficients against the fp64 forward: elements this close to a kink are left out
 SLICE_RTOL, SLICE_ATOL = PR.SLICE_RTOL, PR.SLICE_ATOL       # per-slice bounds: see pair_reference.py
@@ -59,38 +58,6 @@ def T(a, dev):
 
 def N(t):
     return t.detach().cpu().numpy().astype(np.float64)
-
-
-class Bufs:
-    """output buffers: NaN inside, CANARY behind (and in the padding columns of strided ones)"""
-
-    def __init__(self, dev):
-        self.dev, self.all = dev, []
-
-    def out(self, *shape, pad_cols=0):
-        n = int(np.prod(shape))
-        raw = torch.full((n + TAIL,), CANARY, dtype=torch.float32, device=self.dev)
-        v = raw[:n].view(*shape)
-        v.fill_(float('nan'))
-        if pad_cols:
-            v[..., shape[-1] - pad_cols:] = CANARY
-        self.all.append((raw, n, shape, pad_cols))
-        return v
-
-    def inp(self, a):
-        """an input that the kernel also overwrites (the gate buffers): canary tail checked like an output's"""
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        raw = torch.full((a.size + TAIL,), CANARY, dtype=torch.float32, device=self.dev)
-        raw[:a.size] = torch.as_tensor(a.reshape(-1), device=self.dev)
-        self.all.append((raw, a.size, a.shape, 0))
-        return raw[:a.size].view(*a.shape)
-
-    def check_canaries(self):
-        for raw, n, shape, pad in self.all:
-            r = raw.cpu().numpy()
-            assert (r[n:] == CANARY).all(), ("write behind a buffer", shape)
-            if pad:
-                assert (r[:n].reshape(shape)[..., shape[-1] - pad:] == CANARY).all(), ("padding column written", shape)
 
 
 def sliced(got, ref, axes, name, exclude=None, rtol=SLICE_RTOL):
