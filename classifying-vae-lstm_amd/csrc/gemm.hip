@@ -73,9 +73,9 @@ struct TileLoader {
   static constexpr int LD = LdsStride<BMN>::value;
 
   // Fast path (vec: 16-byte aligned base, ld % 4 == 0): every thread issues its float4 loads unconditionally
-  // from clamped, always-valid addresses and masks afterwards.  Loads under per-lane branches (the general path
-  // below) make the compiler wait for each of them where it was issued, which serialises the prefetch of the
-  // next k-tile with the MFMAs of the current one.
+  // from clamped addresses inside the allocation (not always inside the operand: see keep_if) and masks
+  // afterwards.  Loads under per-lane branches (the general path below) make the compiler wait for each of them
+  // where it was issued, which serialises the prefetch of the next k-tile with the MFMAs of the current one.
   // mk[i]: validity bits of r[i]'s 4 components; the masking itself happens in store(), i.e. AFTER the MFMAs of
   // the current tile: touching a loaded value right here would make the wave wait for the load before computing.
   __device__ static void load(float4 (&r)[PER], int (&mk)[PER], const float* __restrict__ p, int ld, int dim_mn,
@@ -234,14 +234,21 @@ struct TileLoader {
     }
   }
 
+  // x, or +0 with every bit cleared: a byte permute (v_perm_b32; selector byte 0x0c reads as 0x00) whose selector
+  // depends on the mask.  Arithmetic, not a select: with selects the compiler turns the masked load back into a load
+  // under a branch.  And not x * 0, which is NaN for a NaN or Inf x: a vector of the fast path may cover elements
+  // that are not part of the operand (a k-contiguous operand with K % 4 != 0 and ld > K reads its row's padding
+  // columns K .. ld-1, which may hold anything).
+  __device__ static float keep_if(float x, int keep) {
+    const unsigned u = __float_as_uint(x);
+    return __uint_as_float(__builtin_amdgcn_perm(u, u, keep ? 0x03020100u : 0x0c0c0c0cu));
+  }
   __device__ static void store(const float4 (&rr)[PER], const int (&mk)[PER], float* lds, int tid) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       int idx = tid + i * 256;
-      // arithmetic masks (operands are finite: a clamped address always points at real data); with selects the
-      // compiler turns the masked load back into a load under a branch
-      float4 r_i = make_float4(rr[i].x * ((mk[i] & 1) ? 1.f : 0.f), rr[i].y * ((mk[i] & 2) ? 1.f : 0.f),
-                               rr[i].z * ((mk[i] & 4) ? 1.f : 0.f), rr[i].w * ((mk[i] & 8) ? 1.f : 0.f));
+      float4 r_i = make_float4(keep_if(rr[i].x, mk[i] & 1), keep_if(rr[i].y, mk[i] & 2),
+                               keep_if(rr[i].z, mk[i] & 4), keep_if(rr[i].w, mk[i] & 8));
       if (mk[i] & 0xF0) {          // implicit ones row (GemmProb.ones == 2)
         if (mk[i] & 16) r_i.x = 1.f;
         if (mk[i] & 32) r_i.y = 1.f;
