@@ -18,10 +18,16 @@ choose K from a first run's `ms_per_step`.
 most 64 MB in all; see dump_outputs): training -- the five loss terms, the updated weights and the step's gradients;
 generation -- the generated frames of the last timed run.  Inputs, weights and noise are seeded, so the same arguments give
 the same inputs in every run and two builds can be compared output for output.
-A default single-GPU run (`python bench.py`, workload cfg3) appends `also`: the other BASELINE workloads -- cfg5, cfg2
-fp32 / bf16, generation of 1 and 1024 sequences -- measured right after the headline by a child process (`bench.py
---also-only`; a few seconds each: value, ms per step, dominant-kernel fraction), so that those numbers are witnessed by
-whoever runs the line and nothing an extra does can cost the headline (it is on stderr before the child starts).
+A plain run does only what the headline needs: set-up (the graph capture; at N > 1 the weight-gradient grid trial; the
+kernel-time pass's eager steps, untimed, see measure_train), warm-up, the timed region, the dump, the line.  Everything else
+it can measure runs with `--full` alone, as it always has: `roofline` (the same pass with HIP events around every launch,
+HBM traffic and SQ counters from rocprofv3 PMC child passes),
+`cpu_baseline`, `host_issue_us_per_step`, `allreduce_alone` (N > 1) and, on a cfg3 single-GPU run, `also`: the other
+BASELINE workloads -- cfg5, cfg2 fp32 / bf16, generation of 1 and 1024 sequences -- measured right after the headline by a
+child process (`bench.py --also-only`; a few seconds each: value, ms per step, dominant-kernel fraction), so that those
+numbers are witnessed by whoever runs the line and nothing an extra does can cost the headline (it is on stderr before the
+child starts).  In a plain line those keys are null (`also` is absent).  None of the extras runs between the warm-up and the
+dump, so a plain and a `--full` run of the same arguments time and dump the same steps.
 CLV_BENCH_SHARE_GPU=1 puts every rank of `--gpus N` on cuda:0 with gloo between them: the whole world > 1 code path on a
 one-GPU box (tests/test_gpu_bench_dp.py), never a scaling measurement (the line says `shared_device`).
 """
@@ -242,7 +248,7 @@ def measure_pmc_traffic(workload, bf16=False, timeout_s=(150, 60, 60)):
             limit = timeout_s[ipass]
             out = os.path.join(tmp, counter)
             cmd = [rp, '--pmc'] + pmc_list + ['--kernel-trace', '-d', out, '-o', 't', '--output-format', 'csv', '--',
-                   sys.executable, os.path.abspath(__file__), '--workload', workload, '--steps', '6', '--warmup', '3',
+                   sys.executable, os.path.abspath(__file__), '--workload', workload, '--steps', '6', '--warmup', '3', '--full',
                    '--no-cpu-baseline', '--no-roofline', '--no-graph', '--no-also', '--no-pmc-traffic'] + (['--bf16'] if bf16 else [])
             env = dict(os.environ, TMPDIR='/tmp')
             pr = subprocess.Popen(cmd, cwd='/tmp', env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
@@ -501,10 +507,10 @@ def train_outputs(eng):
     return out
 
 
-def kernel_time_pass(eng, ts_args, batch, reps, label_off=False):
+def kernel_time_pass(eng, ts_args, batch, reps, label_off=False, timed=True):
     """Per-kernel HIP-event times of `reps` eager steps of the same shapes on the launch stream; parameters and optimizer
     state are put back afterwards.  label_off: the label path's backward as a launch of its own (what the pair backward
-    kernel costs WITHOUT that epilogue)."""
+    kernel costs WITHOUT that epilogue).  timed=False: the same steps without the events; returns None."""
     import torch
     from clvae_amd import ops
     from clvae_amd.trainer import TrainStep
@@ -518,12 +524,17 @@ def kernel_time_pass(eng, ts_args, batch, reps, label_off=False):
     # read as bytes -- are then those of the replayed graph, not those of a float batch staged once
     ts_e.bind_batches(batch[0], batch[1], batch[2], idx=None, period=1, stride=int(batch[0].shape[0]))
     ts_e.step(); torch.cuda.synchronize()
-    ops.prof_enable(True)
+    recs = None
+    if timed:
+        ops.prof_enable(True)
     for _ in range(reps):
         ts_e.step()
-        ops.prof_empty_scope()          # what a bracket of the profiler's events costs by itself ("event_pair")
-    recs = ops.prof_collect()
-    ops.prof_enable(False)
+        if timed:
+            ops.prof_empty_scope()      # what a bracket of the profiler's events costs by itself ("event_pair")
+    if timed:
+        recs = ops.prof_collect()
+        ops.prof_enable(False)
+    torch.cuda.synchronize()
     for t_, sv in zip(eng.P.state_tensors(), saved):
         t_.copy_(sv)
     if label_off:
@@ -571,7 +582,7 @@ def roofline_object(args, w, wl_name, eng, recs, recs_nolabel, reps, value_per_g
         avg_s = ms / n * 1e-3
         achieved = (flop_per_timestep(w) * B / (n / reps)) / avg_s / 1e12
     # HBM bytes per launch of the dominant kernels and per step: MEASURED in this run when main() made the two PMC passes
-    # (measure_pmc_traffic: the default single-GPU run does), else read from the newest committed PMC summary of the SAME
+    # (measure_pmc_traffic: a --full single-GPU run does), else read from the newest committed PMC summary of the SAME
     # workload (tools/round_profile.sh -> profiles/<tag>_pmc_traffic_<workload>.json).  Either way the summary's dominant
     # kernels must be the kernels this run just timed (same names, as many instances), or `traffic` stays null; a
     # committed summary also says whether it was measured on this tree's kernel sources (`traffic_sources_match`).
@@ -692,10 +703,11 @@ def roofline_object(args, w, wl_name, eng, recs, recs_nolabel, reps, value_per_g
 
 
 def measure_train(args, wl_name, dev, rank, world, steps, warmup, bf16=False, reps=40, want_roofline=True, pmc=None,
-                  dump_dir=None):
-    """One training workload: engine, synthetic windows resident in HBM, set-up (graph capture + the kernel-time pass),
-    warm-up, the timed region (then, with dump_dir, rank 0's train_outputs written there).  Returns the pieces of the
-    JSON line."""
+                  dump_dir=None, extras=True, pre_steps=True):
+    """One training workload: engine, synthetic windows resident in HBM, set-up (graph capture + the kernel-time pass: timed
+    when want_roofline, untimed when only pre_steps), warm-up, the timed region (then, with dump_dir, rank 0's train_outputs
+    written there); with extras, the all-reduce microbenchmark (N > 1) and the host issue time afterwards.  Returns the pieces
+    of the JSON line."""
     import torch
     import torch.distributed as dist
     from clvae_amd.trainer import TrainStep
@@ -725,29 +737,33 @@ def measure_train(args, wl_name, dev, rank, world, steps, warmup, bf16=False, re
         torch.cuda.synchronize()
 
     # Set-up, before the W warm-up steps: (1) the step's hipGraph is captured (an eager step, the capture, a first
-    # replay); (2) on rank 0 the roofline object's per-kernel HIP-event timing: eager steps of the same shapes on the same
-    # stream -- its steps are rank 0's alone, so parameters and optimizer state are put back afterwards.  The warm-up and
-    # the timed region follow at once, on a device that has been running this workload.
+    # replay); (2) on rank 0 the eager steps of the kernel-time pass: steps of the same shapes on the same stream -- its steps
+    # are rank 0's alone, so parameters and optimizer state are put back afterwards.  With want_roofline they carry the roofline
+    # object's per-kernel HIP-event timing; without, they run untimed (pre_steps): every headline was timed after them, and a
+    # timed region that starts without them reads ~1 % slower at 20 warm-up steps.  The warm-up and the timed region follow at
+    # once, on a device that has been running this workload.
     run(3)
     barrier()
     if world > 1:          # coarse or fine weight-gradient grid: measured here, on this node, next to the real collectives
         ts.tune_dp_schedule()
         barrier()
     recs = recs_nolabel = None
-    if rank == 0 and want_roofline:
+    if rank == 0 and (want_roofline or pre_steps):
         batch = (X_all[:B], Xp_all[:B], w_all[:B])
-        recs = kernel_time_pass(eng, dict(seed=1234, rank=rank, world=1), batch, reps)
+        timed = bool(want_roofline)
+        recs = kernel_time_pass(eng, dict(seed=1234, rank=rank, world=1), batch, reps, timed=timed)
         if w['model'] == 'cl_vae':
             # a launch-bound step (three launches of 5-40 us, issued eagerly here): when the host falls behind, the interval
             # between a bracket's two events contains the wait for the launch itself (seen once: 70.8 us where rocprofv3 and every
             # other pass say 40-42).  Three passes, the one with the shortest fused-step bracket counts.
             tot = lambda rs: sum(r[2] for r in rs if r[0] in ('vae_fused_step', 'gemm_f32'))
             for _ in range(2):
-                again = kernel_time_pass(eng, dict(seed=1234, rank=rank, world=1), batch, reps)
-                if tot(again) < tot(recs):
+                again = kernel_time_pass(eng, dict(seed=1234, rank=rank, world=1), batch, reps, timed=timed)
+                if timed and tot(again) < tot(recs):
                     recs = again
         if getattr(eng, 'fuse_pair', False) and getattr(eng, 'label_in_pair', False):
-            recs_nolabel = kernel_time_pass(eng, dict(seed=1234, rank=rank, world=1), batch, max(reps // 2, 4), label_off=True)
+            recs_nolabel = kernel_time_pass(eng, dict(seed=1234, rank=rank, world=1), batch, max(reps // 2, 4), label_off=True,
+                                            timed=timed)
     barrier()
     run(warmup)
     if os.environ.get('CLV_BENCH_FAULT_RANK') == str(rank):        # tests: one rank dies between warm-up and the timed region
@@ -755,22 +771,24 @@ def measure_train(args, wl_name, dev, rank, world, steps, warmup, bf16=False, re
     dt, rank_ms = timed_region(run, barrier, steps, world, dev)
     if dump_dir and rank == 0:      # before anything below steps again
         dump_outputs(dump_dir, train_outputs(eng))
-    allreduce = allreduce_microbench(ts, dev) if world > 1 else None
-    # what the host spends per step issuing it (staging launch + graph replays / plain launches / collectives), device idle
-    # or not: 50 steps issued back to back, clock stopped BEFORE the synchronize
-    barrier()
-    t0 = time.perf_counter()
-    run(50)
-    host_us = 1e6 * (time.perf_counter() - t0) / 50
-    barrier()
-    loss = eng.losses()
+    loss = eng.losses()             # the last timed step's
+    allreduce = host_us = None
+    if extras:
+        allreduce = allreduce_microbench(ts, dev) if world > 1 else None
+        # what the host spends per step issuing it (staging launch + graph replays / plain launches / collectives), device idle
+        # or not: 50 steps issued back to back, clock stopped BEFORE the synchronize
+        barrier()
+        t0 = time.perf_counter()
+        run(50)
+        host_us = round(1e6 * (time.perf_counter() - t0) / 50, 1)
+        barrier()
     value = world * B * T * steps / dt
     roofline = None
     if recs is not None:
         roofline = roofline_object(args, w, wl_name, eng, recs, recs_nolabel, reps, value / world, bf16,
                                    kernel_times=args.kernel_times, pmc=pmc)
     return dict(w=w, eng=eng, ts=ts, value=value, dt=dt, rank_ms=rank_ms, allreduce=allreduce, loss=loss,
-                roofline=roofline, host_us=round(host_us, 1))
+                roofline=roofline, host_us=host_us)
 
 
 def also_in_child(timeout_s=600):
@@ -804,7 +822,7 @@ def also_in_child(timeout_s=600):
 
 
 def also_list(args, dev):
-    """The other BASELINE workloads on one GPU.  Runs inside `bench.py --also-only`: the child process a default run starts
+    """The other BASELINE workloads on one GPU.  Runs inside `bench.py --also-only`: the child process a --full cfg3 run starts
     right after its headline (also_in_child)."""
     import copy
     import gc
@@ -856,18 +874,23 @@ def main():
     ap.add_argument('--bf16', action='store_true',
                     help='cfg2: the Dense products of the fused cl_vae step on the bf16 matrix cores (fp32 accumulate)')
     ap.add_argument('--no-persistent', action='store_true', help='generation: per-frame hipGraph replay instead of the persistent kernel')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-also', action='store_true', help='skip the `also` list (the other workloads after a default cfg3 run)')
-    ap.add_argument('--kernel-times', action='store_true', help='print per-kernel event times to stderr')
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything besides the headline too: roofline (with the PMC child passes), CPU baseline, '
+                         'host issue time, all-reduce alone (N > 1), the `also` list (cfg3, one GPU); a plain run does none of it')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip cpu_baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='--full: skip roofline (and its PMC child passes)')
+    ap.add_argument('--no-also', action='store_true', help='--full: skip the `also` list (the other workloads after a cfg3 run)')
+    ap.add_argument('--kernel-times', action='store_true', help="--full: print the roofline pass's per-kernel event times to stderr")
     ap.add_argument('--selftest-launch', action='store_true', help='launcher / rendezvous check on CPU (gloo), no timing')
     ap.add_argument('--no-pmc-traffic', action='store_true',
-                    help='do not measure roofline.traffic with two rocprofv3 PMC child passes (a default single-GPU training run does); '
-                         'the committed summary under profiles/ is read instead')
-    ap.add_argument('--also-only', action='store_true', help='print only the `also` list (what a default run starts as its child)')
+                    help='--full: do not measure roofline.traffic with rocprofv3 PMC child passes (a --full single-GPU training '
+                         'run does); the committed summary under profiles/ is read instead')
+    ap.add_argument('--also-only', action='store_true', help='print only the `also` list (what a --full cfg3 run starts as its child)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help="write what the timed path computed in its last timed step to DIR/<name>.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
+    if args.kernel_times and not args.full:
+        ap.error("--kernel-times prints the times of the roofline pass, which only --full runs")
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -878,8 +901,8 @@ def main():
     pmc = None
     w0 = WORKLOADS[args.workload]
     profiled = 'rocprof' in os.environ.get('LD_PRELOAD', '').lower() or any(k.startswith('ROCPROF') for k in os.environ)
-    if (args.gpus == 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_pmc_traffic and not args.no_roofline
-            and not args.also_only and not w0.get('generate') and not args.no_graph and not profiled):
+    if (args.full and args.gpus == 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and not args.no_pmc_traffic
+            and not args.no_roofline and not args.also_only and not w0.get('generate') and not args.no_graph and not profiled):
         t0 = time.perf_counter()
         pmc = measure_pmc_traffic(args.workload, bf16=args.bf16)
         print("pmc traffic passes: %.1f s%s" % (time.perf_counter() - t0, "; " + pmc['error'] if 'error' in pmc else ""), file=sys.stderr)
@@ -910,11 +933,12 @@ def main():
             print(json.dumps(g))
         return
     m = measure_train(args, args.workload, dev, rank, world, args.steps, args.warmup, bf16=args.bf16,
-                      want_roofline=not args.no_roofline, pmc=pmc, dump_dir=args.dump_outputs)
+                      want_roofline=args.full and not args.no_roofline, pmc=pmc, dump_dir=args.dump_outputs,
+                      extras=args.full, pre_steps=not args.no_roofline)
     eng, ts = m['eng'], m['ts']
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w)
 
     devices = [torch.cuda.get_device_name(local)]
@@ -954,7 +978,7 @@ def main():
                                     "the host -- a run of the world > 1 code path on a one-GPU box, NOT a scaling measurement"
                                     % world)
             out["backend"] = dist.get_backend() if world > 1 else None
-        if world == 1 and args.workload == 'cfg3' and not args.bf16 and not args.no_also and not args.no_graph:
+        if args.full and world == 1 and args.workload == 'cfg3' and not args.bf16 and not args.no_also and not args.no_graph:
             # the headline is out (stderr, flushed) before any extra workload runs, and the extras run in a child process
             print("headline (repeated on stdout with `also`): " + json.dumps(out), file=sys.stderr, flush=True)
             del m, eng, ts

@@ -49,9 +49,9 @@ def last_json(text):
 
 
 def test_bench_with_two_ranks_runs_its_whole_world_gt_1_path(dev):
-    """`python bench.py --gpus 2 --steps 5` outside a process group: the launcher starts two ranks (both on cuda:0), and
-    rank 0's line carries what only the world > 1 branches produce."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"],
+    """`python bench.py --gpus 2 --steps 5 --full` outside a process group: the launcher starts two ranks (both on cuda:0),
+    and rank 0's line carries what only the world > 1 branches produce."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full"],
                        capture_output=True, text=True, timeout=900, env=clean_env())
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)
@@ -75,6 +75,22 @@ def test_bench_with_two_ranks_runs_its_whole_world_gt_1_path(dev):
     assert 4 * (1133462 + 88) <= ar["tail_bucket_bytes"] + ar["main_bucket_bytes"] <= 4 * (1133462 + 88) + 16 * 16
     assert d["roofline"] is not None and d["roofline"]["frac"] > 0       # rank 0's kernel-time pass ran next to rank 1
     assert d["cpu_baseline"] is None                                     # N = 1 only
+    assert np.isfinite(d["final_loss"]) and "also" not in d
+
+
+def test_plain_bench_with_two_ranks_times_the_same_schedule_and_nothing_else(dev):
+    """`python bench.py --gpus 2 --steps 5` without --full: the weight-gradient grid is still tried before the warm-up (the
+    timed steps run the schedule it picks), but nothing is reported besides the headline: no roofline, no all-reduce alone."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2"],
+                       capture_output=True, text=True, timeout=600, env=clean_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = last_json(r.stdout)
+    assert d["n_gpus"] == 2 and d["steps"] == 5 and d["warmup"] == 2 and d["config"]["parallelism"] == "dp2"
+    assert d["value"] == pytest.approx(2 * 256 * 128 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    assert len(d["ms_per_step_by_rank"]) == 2 and max(d["ms_per_step_by_rank"]) == pytest.approx(d["ms_per_step"], rel=1e-3)
+    assert d["dp_schedule"]["wgrad_grid_trials"]["chosen"] in ("coarse", "fine")
+    for k in ("roofline", "cpu_baseline", "allreduce_alone", "host_issue_us_per_step"):
+        assert d[k] is None, k
     assert np.isfinite(d["final_loss"]) and "also" not in d
 
 
