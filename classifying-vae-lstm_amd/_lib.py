@@ -21,6 +21,7 @@ _sz = C.c_size_t
 _i64 = C.c_int64
 _u64 = C.c_uint64
 _u32 = C.c_uint32
+_d = C.c_double
 
 
 class VaeStepOpts(C.Structure):
@@ -210,6 +211,10 @@ SIGNATURES = {
     "clv_i32_add": (_i, [_p, C.c_int32, _p]),
     "clv_iw_accumulate": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _i, _p, _p, _p]),
     "clv_iw_finish": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
+    "clv_smc_sample": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "clv_smc_resample": (_i, [_i, _i, _i, _i, _u64, _i64, _d] + [_p] * 9),
+    "clv_smc_gather": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "clv_smc_backtrack": (_i, [_i, _i, _i, _i, _i, _u64, _i64, _i, _p, _p, _p, _p, _p, _p]),
     "clv_bernoulli_sample": (_i, [_i64, _p, _p, _p, _p]),
     "clv_bernoulli_sample_clamped": (_i, [_i64, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "clv_dropout_rows": (_i, [_i, _i, _i, _p, _i, _p, _i, _f, _f, _p, _i, _p]),

@@ -17,7 +17,7 @@ import torch
 
 from .. import ops, sampling
 from ..engine import VaeEngine
-from ..engine_generate import clamp_roll
+from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy
 from ..initializers import init_weights
 from ..keras_like import Layer, Model, get_value
 
@@ -58,14 +58,23 @@ def generate_sample(dec_model, w_enc_model, z_enc_model, x_seed, nsteps, w_val=N
     return frames
 
 
-def generate_samples_device(model, x_seeds, nsteps, w_vals, seed=0, use_z_prior=False, clamp=None):
+def generate_samples_device(model, x_seeds, nsteps, w_vals, seed=0, use_z_prior=False, clamp=None, particles=None,
+                            resample_threshold=0.5, return_evidence=False):
     """N sequences at once with the frame loop on the device (VaeEngine.generate: one captured hipGraph replayed per
     frame, Philox noise instead of np.random: same distribution, different draws).  x_seeds [N,D], w_vals [N,C];
     returns [N,nsteps,D] float64 like generate_sample does per sequence.  clamp: numpy / torch uint8 [N,nsteps,D]
-    constraint roll (0 off, 1 on, harmonize.FREE free): row t constrains frame t (clamped ancestral sampling)."""
+    constraint roll (0 off, 1 on, harmonize.FREE free): row t constrains frame t (clamped ancestral sampling).
+    particles=P: particle-filter sampling given every constraint (VaeEngine.generate_smc; resampling below an
+    ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64."""
     e = model.engine
     t = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32), device=e.device)
     xs = t(x_seeds)
+    if particles is not None:
+        smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, e.cfg['D'], e.device)
+        return smc_samples_numpy(e, xs, t(w_vals), nsteps, seed, use_z_prior, clamp, particles, resample_threshold,
+                                 return_evidence)
+    if return_evidence:
+        raise ValueError("return_evidence needs particles")
     clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), e.cfg['D'], e.device)
     return e.generate(xs, t(w_vals), int(nsteps), seed=int(seed), z_prior=use_z_prior, clamp=clamp).cpu().numpy() \
         .astype(np.float64)

@@ -9,7 +9,7 @@ if __package__ in (None, ''):
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
 from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, parser_for  # noqa: E402
-from clvae_amd.harmonize import harmonize  # noqa: E402
+from clvae_amd.harmonize import harmonize, print_evidence  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
@@ -21,7 +21,8 @@ class Sampler:
     def __init__(self, args):
         self.args = args
         self.model, _, self.margs = M.load_model(args.model_file, no_x_prev=args.no_x_prev,
-                                                 batch_size=max(1, args.n if on_device(args) else 1))
+                                                 batch_size=max(1, args.n * (getattr(args, 'particles', None) or 1)
+                                                                if on_device(args) else 1))
         m, dims = self.margs, (self.margs['intermediate_dim'], self.margs['latent_dim'])
         self.w_enc = M.make_w_encoder(self.model, m['original_dim'])
         self.z_enc = M.make_z_encoder(self.model, m['original_dim'], m['n_classes'], dims)
@@ -64,8 +65,13 @@ class Sampler:
             ws = [M.sample_w(self.w_enc.predict(s[None, :]), add_noise=False) for s in seeds]
         else:
             ws = [to_categorical(self.data.test_song_keys[i], self.margs['n_classes']) for i in picks]
-        rolls = harmonize(self.model, seeds, sources, np.vstack(ws), voice=voice_of(self.args),
-                          seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior)
+        particles = getattr(self.args, 'particles', None)
+        out = harmonize(self.model, seeds, sources, np.vstack(ws), voice=voice_of(self.args),
+                        seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior, particles=particles,
+                        return_evidence=particles is not None)
+        rolls = out[0] if particles is not None else out
+        if particles is not None:
+            print_evidence(names, out[1], self.args.t)
         for roll, src, name in zip(rolls, sources, names):
             write_sample(roll, self.args.sample_dir, name, True)
             write_sample(src, self.args.sample_dir, name + '_source', True)

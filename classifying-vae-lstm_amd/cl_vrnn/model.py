@@ -17,7 +17,7 @@ import torch
 
 from .. import sampling
 from ..engine import VrnnEngine, vrnn_param_shapes
-from ..engine_generate import clamp_roll
+from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy
 from ..initializers import glorot_uniform, init_weights, orthogonal
 from ..keras_like import Layer, Model, get_value
 from ..utils.pianoroll import Windows
@@ -235,16 +235,24 @@ class Encoder:
         return [Zargs[..., :L], Zargs[..., L:], W]
 
 
-def generate_samples_device(model, x_seeds, nsteps, w_vals, seed=0, z_prior=False, clamp=None):
+def generate_samples_device(model, x_seeds, nsteps, w_vals, seed=0, z_prior=False, clamp=None, particles=None,
+                            resample_threshold=0.5, return_evidence=False):
     """Batched, device-resident counterpart of generate_sample: N seeds at once, the whole frame loop as
     replays of one captured hipGraph, Philox noise instead of np.random (so the draws differ from the numpy
     path, the distribution does not).  x_seeds [N,S,88] (S >= 0 teacher-forced frames), w_vals [N,C].
     Returns the free-running part [N,nsteps,88] as a numpy array, like generate_sample does per seed.
     clamp: numpy / torch uint8 [N,nsteps,88] constraint roll (0 off, 1 on, harmonize.FREE free): row j constrains
-    returned frame j (clamped ancestral sampling; the unreturned bridge sample of step S-1 stays free)."""
+    returned frame j (clamped ancestral sampling; the unreturned bridge sample of step S-1 stays free).
+    particles=P: particle-filter sampling given every constraint (VrnnEngine.generate_smc; resampling below
+    an ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64."""
     e = model.engine
     xs = torch.as_tensor(np.ascontiguousarray(np.asarray(x_seeds), dtype=np.float32), device=e.device)
     w = torch.as_tensor(np.ascontiguousarray(np.asarray(w_vals), dtype=np.float32), device=e.device)
+    if particles is not None:
+        smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, e.cfg['D'], e.device)
+        return smc_samples_numpy(e, xs, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence)
+    if return_evidence:
+        raise ValueError("return_evidence needs particles")
     clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), e.cfg['D'], e.device)
     return e.generate(xs, w, int(nsteps), seed=int(seed), z_prior=z_prior, clamp=clamp).cpu().numpy().astype(np.float64)
 

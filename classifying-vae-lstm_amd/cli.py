@@ -111,11 +111,27 @@ HARMONIZE_CHOICES = ('top', 'bottom')
 HARMONIZE_FLAGS = [
     Flag(('--harmonize',), str, None, 'keep the top or bottom voice of the -t test frames after the seed and generate '
                                       'the other voices (clamped sampling on the device; implies --device_loop)'),
+    Flag(('--particles',), int, None, 'with --harmonize: sample given the whole voice with a particle filter of this many '
+                                      'particles per sample (DESIGN.md 11) and print log p(voice) per frame'),
 ]
 
 
+class _Parser(argparse.ArgumentParser):
+    """argparse with the one rule between flags: --particles only with --harmonize"""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        particles = getattr(ns, 'particles', None)
+        if particles is not None:
+            if not getattr(ns, 'harmonize', None):
+                self.error('--particles needs --harmonize')
+            if particles < 1:
+                self.error('--particles must be >= 1')
+        return ns, rest
+
+
 def parser_for(tool, extra=()):
-    p = argparse.ArgumentParser()
+    p = _Parser()
     for f in list(TABLES[tool]) + list(extra):
         if f.kind == ON:
             p.add_argument(*f.names, action=ON, help=f.help)

@@ -1,0 +1,281 @@
+// smc.hip -- particle-filter sampling under a constraint roll (sequential Monte Carlo).
+//
+// G melodies own P particle rows each, r = m * P + p (R = G * P rows in one launch).  Per generated frame, replayed from
+// one captured graph, the frame chain of the engine runs unchanged up to x_hat; then
+//   clv_smc_sample    one wave per row: Bernoulli draw + constraint (as clv_bernoulli_sample_clamped, roll row m = r / P),
+//                     the frame's log weight increment l_r in fp64, the frame as uint8 into the per-step history;
+//   clv_smc_resample  one workgroup per melody: log Z, normalized log weights, ESS, systematic resampling, ancestors A_t;
+//   clv_smc_gather    the rows of the state buffers permuted by A_t (through a scratch buffer: a gather is not in place);
+// and once at the end clv_smc_backtrack draws the returned paths from the final weights and walks the lineage.
+// Every output element has one owner and no kernel uses atomics, so every result is bitwise reproducible.
+#include "common.h"
+#include "philox.h"
+
+namespace clv {
+
+constexpr uint32_t SMC_STREAM = 0xFFFFFFFDu;        // trainer.py's stream map, next to the IW pair
+constexpr int SMC_MAX_P = 1024;                      // particles per melody: one workgroup holds them
+constexpr int SMC_MAX_BUFS = 8;
+constexpr float SMC_CLIP_LO = 1e-7f, SMC_CLIP_HI = 1.0f - 1e-7f;   // Keras float32 BCE clip (BCE_CLIP_* on the logits)
+
+__device__ __forceinline__ double smc_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double smc_wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// workgroup-wide sum / max of one value per thread (a fixed order: butterfly in the wave, then the waves in turn)
+__device__ double block_sum(double v, double* red) {
+  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  v = smc_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int i = 0; i < nw; ++i) s += red[i];
+  __syncthreads();
+  return s;
+}
+__device__ double block_max(double v, double* red) {
+  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  v = smc_wave_max(v);
+  if ((threadIdx.x & 63) == 0) red[w] = v;
+  __syncthreads();
+  double s = red[0];
+  for (int i = 1; i < nw; ++i) s = fmax(s, red[i]);
+  __syncthreads();
+  return s;
+}
+
+// cum[p] = sum_{q <= p} v_q over the workgroup (wave scan, then the wave totals)
+__device__ void block_inclusive_scan(double v, double* cum, double* red) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  if (lane == 63) red[w] = v;
+  __syncthreads();
+  double base = 0.0;
+  for (int i = 0; i < w; ++i) base += red[i];
+  cum[threadIdx.x] = base + v;
+  __syncthreads();
+}
+
+// systematic resampling: draw i of n takes the first particle p with n * cum[p] > u0 + i (the last one if none)
+__device__ __forceinline__ int systematic_pick(const double* cum, int P, double n, double x) {
+  int lo = 0, hi = P - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (n * cum[mid] > x) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ double smc_uniform(uint64_t seed, int64_t melody, int step) {
+  return (double)philox_uniform_at((uint64_t)melody, (uint32_t)seed, (uint32_t)(seed >> 32), SMC_STREAM, (uint32_t)step);
+}
+
+constexpr int SMC_ROWS = 4;        // rows (waves) per workgroup of the row kernels
+
+__global__ __launch_bounds__(64 * SMC_ROWS) void smc_sample_kernel(int R, int D, int P, int nsteps, int S, const float* p,
+                                                                  const float* u, const uint8_t* clamp,
+                                                                  const int32_t* step_dev, float* x, double* ell,
+                                                                  uint8_t* hist) {
+  const int row = blockIdx.x * SMC_ROWS + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= R) return;
+  const int k = *step_dev - S;
+  const bool on = k >= 0 && k < nsteps;
+  const int64_t base = (int64_t)row * D;
+  const uint8_t* cr = clamp + ((int64_t)(row / P) * nsteps + (on ? k : 0)) * D;
+  uint8_t* hr = hist + ((int64_t)(on ? k : 0) * R + row) * D;
+  double l = 0.0;
+  for (int j = lane; j < D; j += 64) {
+    const float pj = p[base + j], uj = u[base + j];
+    const uint8_t cb = on ? cr[j] : (uint8_t)255;
+    float xs = (uj <= pj) ? 1.f : 0.f;
+    if (cb <= 1) {
+      xs = (float)cb;
+      const float q = fminf(fmaxf(pj, SMC_CLIP_LO), SMC_CLIP_HI);
+      l += cb ? log((double)q) : log(1.0 - (double)q);
+    }
+    x[base + j] = xs;
+    if (on) hr[j] = (uint8_t)xs;
+  }
+  if (on) {
+    l = smc_wave_sum(l);
+    if (lane == 0) ell[row] = l;
+  }
+}
+
+__global__ __launch_bounds__(SMC_MAX_P) void smc_resample_kernel(int P, int nsteps, int S, uint64_t seed, int64_t m0,
+                                                                 double tau, const double* ell, double* logW, double* logZ,
+                                                                 double* ess, int32_t* nres, int32_t* flag, int32_t* anc,
+                                                                 const int32_t* step_dev, int R) {
+  __shared__ double red[SMC_MAX_P / 64];
+  __shared__ double cum[SMC_MAX_P];
+  const int k = *step_dev - S;
+  if (k < 0 || k >= nsteps) return;             // seed steps and the bridge carry no weight (uniform exit: no barrier hit)
+  const int m = blockIdx.x, p = threadIdx.x;
+  const bool mine = p < P;
+  const int64_t r = (int64_t)m * P + p;
+  const double logP = log((double)P);
+  // step 0 starts from uniform weights, log Z = 0 and no resamples: nothing to initialise before the first replay
+  const double lw = mine ? (k == 0 ? -logP : logW[r]) + ell[r] : -INFINITY;
+  const double M = block_max(lw, red);
+  const double a = mine ? exp(lw - M) : 0.0;
+  const double s1 = block_sum(a, red);
+  const double s2 = block_sum(a * a, red);
+  const double lse = M + log(s1);
+  const double wn = lw - lse;                   // normalized log weight after this frame
+  const double e = s1 * s1 / s2;                // = 1 / sum exp(2 wn); exactly P for uniform weights
+  const bool resample = e < tau * (double)P;
+  if (resample) {
+    block_inclusive_scan(mine ? exp(wn) : 0.0, cum, red);
+    if (mine) {
+      const double u0 = smc_uniform(seed, m0 + m, k + S);
+      anc[(int64_t)k * R + r] = m * P + systematic_pick(cum, P, (double)P, u0 + (double)p);
+      logW[r] = -logP;
+    }
+  } else if (mine) {
+    anc[(int64_t)k * R + r] = (int32_t)r;
+    logW[r] = wn;
+  }
+  if (p == 0) {
+    logZ[m] = (k == 0 ? 0.0 : logZ[m]) + lse;
+    ess[(int64_t)m * nsteps + k] = e;
+    nres[m] = (k == 0 ? 0 : nres[m]) + (resample ? 1 : 0);
+    flag[m] = resample ? 1 : 0;
+  }
+}
+
+struct SmcBufs {
+  float* buf[SMC_MAX_BUFS];
+  int width[SMC_MAX_BUFS];        // floats per row
+  int64_t off[SMC_MAX_BUFS];      // the buffer's slab in the scratch buffer (floats)
+  int n;
+};
+
+// TO_SCRATCH: scratch row r = buffer row A_t[r]; otherwise buffer row r = scratch row r.  Only melodies that resampled
+// at this step move (flag); every other row keeps its state.
+template <bool TO_SCRATCH>
+__global__ __launch_bounds__(64 * SMC_ROWS) void smc_gather_kernel(int R, int P, int nsteps, int S, SmcBufs b, float* scratch,
+                                                                  const int32_t* anc, const int32_t* flag,
+                                                                  const int32_t* step_dev) {
+  const int row = blockIdx.x * SMC_ROWS + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= R) return;
+  const int k = *step_dev - S;
+  if (k < 0 || k >= nsteps || !flag[row / P]) return;
+  const int64_t src = TO_SCRATCH ? (int64_t)anc[(int64_t)k * R + row] : (int64_t)row;
+  for (int i = 0; i < b.n; ++i) {
+    const int w = b.width[i];
+    float* s = scratch + b.off[i] + (int64_t)row * w;
+    if (TO_SCRATCH) {
+      const float* in = b.buf[i] + src * w;
+      for (int j = lane; j < w; j += 64) s[j] = in[j];
+    } else {
+      float* out = b.buf[i] + src * w;
+      for (int j = lane; j < w; j += 64) out[j] = s[j];
+    }
+  }
+}
+
+__global__ __launch_bounds__(SMC_MAX_P) void smc_backtrack_kernel(int P, int nsteps, int D, int n_out, uint64_t seed,
+                                                                  int64_t m0, int step, const double* logW,
+                                                                  const int32_t* anc, const uint8_t* hist, float* Xs,
+                                                                  int32_t* picks, int R) {
+  __shared__ double red[SMC_MAX_P / 64];
+  __shared__ double cum[SMC_MAX_P];
+  const int m = blockIdx.x, p = threadIdx.x;
+  block_inclusive_scan(p < P ? exp(logW[(int64_t)m * P + p]) : 0.0, cum, red);
+  const double u0 = smc_uniform(seed, m0 + m, step);
+  const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  for (int o = threadIdx.x >> 6; o < n_out; o += nw) {
+    const int pick = systematic_pick(cum, P, (double)n_out, u0 + (double)o);
+    int64_t r = (int64_t)m * P + pick;
+    if (picks && lane == 0) picks[(int64_t)m * n_out + o] = pick;
+    float* out = Xs + ((int64_t)m * n_out + o) * nsteps * D;
+    for (int k = nsteps - 1; k >= 0; --k) {
+      r = anc[(int64_t)k * R + r];              // the row before step k's resampling: its frame k is the path's
+      const uint8_t* h = hist + ((int64_t)k * R + r) * D;
+      for (int j = lane; j < D; j += 64) out[(int64_t)k * D + j] = (float)h[j];
+    }
+  }
+}
+
+static inline int smc_block(int P) { return (P + 63) / 64 * 64; }
+
+}  // namespace clv
+
+using namespace clv;
+
+extern "C" int clv_smc_sample(int R, int D, int P, int nsteps, int S, const float* p, const float* u, const uint8_t* clamp,
+                              const int32_t* step_dev, float* x, double* ell, uint8_t* hist, void* stream) {
+  if (R <= 0 || D <= 0 || P <= 0 || R % P != 0 || nsteps <= 0 || S < 0 || !p || !u || !clamp || !step_dev || !x || !ell ||
+      !hist)
+    return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_sample", s);
+  hipLaunchKernelGGL(smc_sample_kernel, dim3((R + SMC_ROWS - 1) / SMC_ROWS), dim3(64 * SMC_ROWS), 0, s, R, D, P, nsteps, S,
+                     p, u, clamp, step_dev, x, ell, hist);
+  return launch_status();
+}
+
+extern "C" int clv_smc_resample(int G, int P, int nsteps, int S, uint64_t seed, int64_t m0, double tau, const double* ell,
+                                double* logW, double* logZ, double* ess, int32_t* nres, int32_t* flag, int32_t* anc,
+                                const int32_t* step_dev, void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || nsteps <= 0 || S < 0 || m0 < 0 || !(tau >= 0.0 && tau <= 1.0) || !ell ||
+      !logW || !logZ || !ess || !nres || !flag || !anc || !step_dev)
+    return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_resample", s);
+  hipLaunchKernelGGL(smc_resample_kernel, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, S, seed, m0, tau, ell, logW, logZ,
+                     ess, nres, flag, anc, step_dev, G * P);
+  return launch_status();
+}
+
+extern "C" int clv_smc_gather(int R, int P, int nsteps, int S, int nbuf, float* const* bufs, const int* widths,
+                              float* scratch, const int32_t* anc, const int32_t* flag, const int32_t* step_dev,
+                              void* stream) {
+  if (R <= 0 || P <= 0 || R % P != 0 || nsteps <= 0 || S < 0 || nbuf <= 0 || nbuf > SMC_MAX_BUFS || !bufs || !widths ||
+      !scratch || !anc || !flag || !step_dev)
+    return CLV_EINVAL;
+  SmcBufs b{};
+  int64_t off = 0;
+  for (int i = 0; i < nbuf; ++i) {
+    if (!bufs[i] || widths[i] <= 0) return CLV_EINVAL;
+    b.buf[i] = bufs[i];
+    b.width[i] = widths[i];
+    b.off[i] = off;
+    off += (int64_t)widths[i] * R;
+  }
+  b.n = nbuf;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_gather", s);
+  const dim3 grid((R + SMC_ROWS - 1) / SMC_ROWS), block(64 * SMC_ROWS);
+  hipLaunchKernelGGL(smc_gather_kernel<true>, grid, block, 0, s, R, P, nsteps, S, b, scratch, anc, flag, step_dev);
+  hipLaunchKernelGGL(smc_gather_kernel<false>, grid, block, 0, s, R, P, nsteps, S, b, scratch, anc, flag, step_dev);
+  return launch_status();
+}
+
+extern "C" int clv_smc_backtrack(int G, int P, int nsteps, int D, int n_out, uint64_t seed, int64_t m0, int step,
+                                 const double* logW, const int32_t* anc, const uint8_t* hist, float* Xs, int32_t* picks,
+                                 void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || nsteps <= 0 || D <= 0 || n_out <= 0 || m0 < 0 || step < 0 || !logW || !anc ||
+      !hist || !Xs)
+    return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_backtrack", s);
+  hipLaunchKernelGGL(smc_backtrack_kernel, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, D, n_out, seed, m0, step, logW, anc,
+                     hist, Xs, picks, G * P);
+  return launch_status();
+}

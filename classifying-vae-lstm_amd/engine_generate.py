@@ -1,6 +1,8 @@
 """Sampling on the device: the frame loops of generate_sample (cl_vae/model.py:9-42, cl_vrnn/model.py:9-60) for N sequences
 at once, and the stateful single-step sub-models of cl_vrnn (cl_vrnn/model.py:116-162).  Mixins of engine.VaeEngine /
 engine.VrnnEngine: they use the engines' buffers, parameters and forward pieces."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -29,6 +31,89 @@ def clamp_roll(clamp, N, nsteps, D, device):
     if tuple(clamp.shape) != (int(N), int(nsteps), int(D)):
         raise ValueError("clamp must have shape %s, got %s" % ((int(N), int(nsteps), int(D)), tuple(clamp.shape)))
     return clamp.to(device).contiguous()
+
+
+SmcResult = namedtuple('SmcResult', 'Xs log_evidence ess resamples')
+SmcResult.__doc__ = """generate_smc's outputs (device tensors): Xs [N, n_out, nsteps, D] fp32 frames, log_evidence [N] fp64 (log Z:
+the estimate of log p(constraints | seed, w)), ess [N, nsteps] fp64 (after each frame's reweighting), resamples [N] int32."""
+
+SMC_MAX_PARTICLES = 1024            # one workgroup of clv_smc_resample holds a melody's particles
+
+
+def smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, device):
+    """Validate generate_smc's arguments; returns the constraint roll as a device tensor (clamp_roll)."""
+    if clamp is None:
+        raise ValueError("particle sampling needs a constraint roll (clamp=...)")
+    if isinstance(particles, bool) or int(particles) != particles or not 1 <= particles <= SMC_MAX_PARTICLES:
+        raise ValueError("particles must be an integer in [1, %d], got %r" % (SMC_MAX_PARTICLES, particles))
+    tau = float(resample_threshold)
+    if not 0.0 <= tau <= 1.0:
+        raise ValueError("resample_threshold must lie in [0, 1], got %r" % (resample_threshold,))
+    if isinstance(n_out, bool) or int(n_out) != n_out or n_out < 1:
+        raise ValueError("n_out must be an integer >= 1, got %r" % (n_out,))
+    if int(nsteps) < 1:
+        raise ValueError("particle sampling needs nsteps >= 1, got %r" % (nsteps,))
+    return clamp_roll(clamp, N, nsteps, D, device)
+
+
+def smc_samples_numpy(engine, x_seed, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence):
+    """generate_samples_device(particles=P): one draw per melody, [N, nsteps, D] float64 (and log_evidence [N] float64)"""
+    r = engine.generate_smc(x_seed, w, int(nsteps), clamp, particles, resample_threshold, n_out=1, seed=int(seed),
+                            z_prior=z_prior)
+    Xs = r.Xs[:, 0].cpu().numpy().astype(np.float64)
+    return (Xs, r.log_evidence.cpu().numpy()) if return_evidence else Xs
+
+
+class _Smc:
+    """Device state of one chunk of G melodies x P particles: the weight increments, normalized log weights,
+    log Z, ESS, resample counts, ancestors A_t [nsteps, R] and the uint8 frame history [nsteps, R, D].  step() is the SMC
+    part of one frame (sample, resample, gather); finish() draws the returned paths."""
+
+    def __init__(self, G, P, nsteps, S, D, tau, seed, m0, clamp, device):
+        self.G, self.P, self.R, self.nsteps, self.S, self.D = G, P, G * P, nsteps, S, D
+        self.tau, self.seed, self.m0, self.clamp = tau, seed, m0, clamp
+        f64 = dict(dtype=torch.float64, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.ell, self.logW = torch.zeros(self.R, **f64), torch.zeros(self.R, **f64)
+        self.logZ, self.ess = torch.zeros(G, **f64), torch.zeros(G, nsteps, **f64)
+        self.nres, self.flag = torch.zeros(G, **i32), torch.zeros(G, **i32)
+        self.anc = torch.zeros(nsteps, self.R, **i32)
+        self.hist = torch.zeros(nsteps, self.R, D, dtype=torch.uint8, device=device)
+
+    def step(self, xhat, u, counter, x_next, gather):
+        ops.smc_sample(self.R, self.D, self.P, self.nsteps, self.S, xhat, u, self.clamp, counter, x_next, self.ell, self.hist)
+        ops.smc_resample(self.G, self.P, self.nsteps, self.S, self.seed, self.m0, self.tau, self.ell, self.logW, self.logZ,
+                         self.ess, self.nres, self.flag, self.anc, counter)
+        gather(self.anc, self.flag, counter)
+
+    def finish(self, n_out, Xs):
+        ops.smc_backtrack(self.G, self.P, self.nsteps, self.D, n_out, self.seed, self.m0, self.S + self.nsteps, self.logW,
+                          self.anc, self.hist, Xs)
+
+
+def _smc_chunks(N, P, cap, chunk):
+    """melody ranges [m0, m1): at most `chunk` melodies (default: all) and at most cap rows (None: no cap) per chunk"""
+    g = N if chunk is None else int(chunk)
+    if g < 1:
+        raise ValueError("chunk must be >= 1, got %r" % (chunk,))
+    if cap is not None:
+        if P > cap:
+            raise ValueError("%d particles exceed the engine's batch size %d" % (P, cap))
+        g = min(g, cap // P)
+    return [(m0, min(N, m0 + g)) for m0 in range(0, N, g)]
+
+
+def _smc_drive(chunks, run_chunk, N, nsteps, D, n_out, device):
+    f = dict(device=device)
+    out = SmcResult(torch.zeros(N, n_out, nsteps, D, dtype=torch.float32, **f), torch.zeros(N, dtype=torch.float64, **f),
+                    torch.zeros(N, nsteps, dtype=torch.float64, **f), torch.zeros(N, dtype=torch.int32, **f))
+    for m0, m1 in chunks:
+        smc = run_chunk(m0, m1)
+        smc.finish(n_out, out.Xs[m0:m1])
+        out.log_evidence[m0:m1].copy_(smc.logZ)
+        out.ess[m0:m1].copy_(smc.ess)
+        out.resamples[m0:m1].copy_(smc.nres)
+    return out
 
 
 class VaeGenerate:
@@ -88,6 +173,66 @@ class VaeGenerate:
                 frame()
             Xs[:, t].copy_(x_next)
         return Xs
+
+    def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
+                     z_prior=False, chunk=None):
+        """Particle-filter sampling under the constraint roll clamp [N, nsteps, D]: melody m runs P =
+        `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
+        probability of each frame's clamped notes and resampled (systematic, below an ESS of resample_threshold * P).
+        Row t of the roll constrains frame t.  Melodies are processed in chunks of at most batch-size rows (and at most
+        `chunk` melodies); the Philox keys follow the global row, so the result does not depend on the chunking.
+        x_seed [N, D], w [N, C] device tensors.  Returns SmcResult (Xs [N, n_out, nsteps, D])."""
+        cfg, d = self.cfg, self.device
+        N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
+        clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
+        P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
+        f = dict(dtype=torch.float32, device=d)
+        x_seed, w = x_seed.to(**f), w.to(**f)
+
+        def run_chunk(m0, m1):
+            G = m1 - m0
+            R, r0 = G * P, m0 * P
+            x_in = x_seed[m0:m1].repeat_interleave(P, 0).contiguous()
+            hist, x_next = x_in.clone(), torch.zeros(R, D, **f)
+            wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+            eps, u = torch.zeros(R, L, **f), torch.zeros(R, D, **f)
+            counter = torch.zeros(1, dtype=torch.int32, device=d)
+            smc = _Smc(G, P, nsteps, 0, D, tau, seed, m0, clamp[m0:m1], d)
+            gather = ops.SmcGather(R, P, nsteps, 0, [x_next, x_in])     # x_in becomes the decoder's history below
+
+            def frame():
+                self.encode_z(x_in, wr, R)
+                ops.philox_normal(eps, R * L, seed, 0, 0, r0 * L, step_dev=counter)
+                if z_prior:
+                    self.zargs[:R].zero_()
+                ops.gauss_fwd(R, L, self.zargs, eps, self.z, L, None)
+                self.decode(wr, self.z, hist if cfg['use_x_prev'] else None, R, act=ACT_SIGMOID)
+                ops.philox_uniform(u, R * D, seed, 0, 1, r0 * D, step_dev=counter)
+                smc.step(self.logits, u, counter, x_next, gather)
+                ops.i32_add(counter, 1)
+                hist.copy_(x_in)
+                x_in.copy_(x_next)
+
+            _replay(frame, nsteps, use_graph)
+            return smc
+
+        return _smc_drive(_smc_chunks(N, P, self.B, chunk), run_chunk, N, nsteps, D, int(n_out), d)
+
+
+def _replay(frame, nsteps, use_graph, before=None):
+    """run frame() nsteps times: step 0 eagerly (it sizes every workspace), then one captured graph replayed per step;
+    before(t) runs eagerly ahead of step t"""
+    graph = None
+    for t in range(nsteps):
+        if before is not None:
+            before(t)
+        if use_graph and t == 1:
+            with ops.Graph() as graph:
+                frame()
+        if graph is not None:
+            graph.launch()
+        else:
+            frame()
 
 
 class VrnnGenerate:
@@ -216,3 +361,52 @@ class VrnnGenerate:
             if t >= S:
                 Xs[:, t - S].copy_(x_next)
         return Xs
+
+    def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
+                     z_prior=False, chunk=None):
+        """Particle-filter sampling under the constraint roll clamp [N, nsteps, D]: melody m runs P =
+        `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
+        probability of each returned frame's clamped notes and resampled (systematic, below an ESS of
+        resample_threshold * P).  Row j of the roll constrains the sample of step S+j; the seed steps and the bridge carry
+        no constraint and no weight.  `chunk`: at most that many melodies per pass (the Philox keys follow the global row,
+        so the result does not depend on it).  x_seed [N, S, D], w [N, C] device tensors.  Returns SmcResult."""
+        cfg, d = self.cfg, self.device
+        N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
+        D, L = cfg['D'], cfg['L']
+        clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
+        P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
+        f = dict(dtype=torch.float32, device=d)
+        x_seed, w = x_seed.to(**f), w.to(**f)
+
+        def run_chunk(m0, m1):
+            G = m1 - m0
+            R, r0 = G * P, m0 * P
+            xs = x_seed[m0:m1].repeat_interleave(P, 0)
+            wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+            st = self.new_state(R)
+            x_prev, x_next = torch.zeros(R, D, **f), torch.zeros(R, D, **f)
+            eps, u, z = torch.zeros(R, L, **f), torch.zeros(R, D, **f), torch.zeros(R, L, **f)
+            counter = torch.zeros(1, dtype=torch.int32, device=d)
+            smc = _Smc(G, P, nsteps, S, D, tau, seed, m0, clamp[m0:m1], d)
+            gather = ops.SmcGather(R, P, nsteps, S, [st['h_enc'], st['c_enc'], st['h_dec'], st['c_dec'], x_next])
+
+            def frame():
+                self.enc_step(x_prev, wr, st)
+                ops.philox_normal(eps, R * L, seed, 0, 0, r0 * L, step_dev=counter)
+                if z_prior:
+                    st['zargs'].zero_()
+                ops.gauss_fwd(R, L, st['zargs'], eps, z, L, None)
+                self.dec_step(z, x_prev if cfg['use_x_prev'] else None, wr, st)
+                ops.philox_uniform(u, R * D, seed, 0, 1, r0 * D, step_dev=counter)
+                smc.step(st['xhat'], u, counter, x_next, gather)
+                ops.i32_add(counter, 1)
+                x_prev.copy_(x_next)
+
+            def before(t):
+                if t < S:
+                    x_prev.copy_(xs[:, t])
+
+            _replay(frame, S + nsteps, use_graph, before)
+            return smc
+
+        return _smc_drive(_smc_chunks(N, P, None, chunk), run_chunk, N, nsteps, D, int(n_out), d)

@@ -700,6 +700,48 @@ def bernoulli_sample_clamped(n, D, nsteps, S, p, u, clamp, step_dev, x):
                                                   _stream()), "clv_bernoulli_sample_clamped")
 
 
+def smc_sample(R, D, P, nsteps, S, p, u, clamp, step_dev, x, ell, hist):
+    """particle rows r < R (P per melody): x = clamped Bernoulli draw of p with roll row r // P of clamp [R/P, nsteps, D]
+    at step *step_dev - S; ell [R] fp64 = the frame's log weight increment; hist [nsteps, R, D] uint8."""
+    check(_lib.lib().clv_smc_sample(R, D, P, nsteps, S, _ptr(p), _ptr(u), _ptr(clamp), _ptr(step_dev), _ptr(x), _ptr(ell),
+                                    _ptr(hist), _stream()), "clv_smc_sample")
+
+
+def smc_resample(G, P, nsteps, S, seed, m0, tau, ell, logW, logZ, ess, nres, flag, anc, step_dev):
+    """per melody m < G: log Z, normalized log weights, ESS [G, nsteps], systematic resampling below tau * P, ancestors
+    anc [nsteps, G*P] of step *step_dev - S; m0 = global index of melody 0 (the resampling uniform's Philox index)."""
+    check(_lib.lib().clv_smc_resample(G, P, nsteps, S, int(seed), int(m0), float(tau), _ptr(ell), _ptr(logW), _ptr(logZ),
+                                      _ptr(ess), _ptr(nres), _ptr(flag), _ptr(anc), _ptr(step_dev), _stream()),
+          "clv_smc_resample")
+
+
+class SmcGather:
+    """clv_smc_gather over a fixed list of fp32 [R, width] buffers: the pointer list lives on the host (the launch copies
+    it into its arguments, so a captured graph keeps it) and the scratch buffer is allocated once."""
+
+    def __init__(self, R, P, nsteps, S, bufs):
+        self.R, self.P, self.nsteps, self.S = int(R), int(P), int(nsteps), int(S)
+        widths = [int(b.numel()) // self.R for b in bufs]
+        if any(w * self.R != b.numel() or not b.is_contiguous() or b.dtype != torch.float32 for w, b in zip(widths, bufs)):
+            raise ValueError("smc gather buffers must be contiguous float32 [R, width]")
+        self.bufs = list(bufs)
+        self._ptrs = (C.c_void_p * len(bufs))(*[b.data_ptr() for b in bufs])
+        self._widths = (C.c_int * len(bufs))(*widths)
+        self.scratch = torch.empty(sum(widths) * self.R, dtype=torch.float32, device=bufs[0].device)
+
+    def __call__(self, anc, flag, step_dev):
+        check(_lib.lib().clv_smc_gather(self.R, self.P, self.nsteps, self.S, len(self.bufs), C.cast(self._ptrs, C.c_void_p),
+                                        C.cast(self._widths, C.c_void_p), _ptr(self.scratch), _ptr(anc), _ptr(flag),
+                                        _ptr(step_dev), _stream()), "clv_smc_gather")
+
+
+def smc_backtrack(G, P, nsteps, D, n_out, seed, m0, step, logW, anc, hist, Xs, picks=None):
+    """n_out draws per melody from the final weights (Philox uniform at `step`, index m0 + m), lineage walked back through
+    anc: Xs [G, n_out, nsteps, D] fp32; picks [G, n_out] int32 (optional) = the drawn final particles."""
+    check(_lib.lib().clv_smc_backtrack(G, P, nsteps, D, n_out, int(seed), int(m0), int(step), _ptr(logW), _ptr(anc),
+                                       _ptr(hist), _ptr(Xs), _ptr(picks), _stream()), "clv_smc_backtrack")
+
+
 class Graph:
     """Capture the kernels enqueued inside the ``with`` block on the current stream; replay with launch()."""
 

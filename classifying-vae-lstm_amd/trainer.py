@@ -25,6 +25,9 @@ from .parallel import GradAllReduce, eps_first_index, meta_device
 # and, reserved for the importance-weighted likelihood (likelihood.py; step = sample k, first index from the
 # GLOBAL window index), the last pair of the range, which no other draw reaches:
 IW_STREAM_W, IW_STREAM_Z = 0xFFFFFFFE, 0xFFFFFFFF
+# and, for the particle filter's resampling uniforms (engine_generate.generate_smc; step = generation step,
+# index = GLOBAL melody; drawn inside csrc/smc.hip), the stream just below them:
+SMC_STREAM = 0xFFFFFFFD
 
 
 class DevWindows:

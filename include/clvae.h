@@ -820,6 +820,33 @@ int clv_iw_accumulate(int R, int T, int L, int C1, const float* rownll, const fl
                       int32_t* step_dev, void* stream);
 int clv_iw_finish(int R, int nvalid, int K, const double* state, double* log_p, double* elbo, double* ess, void* stream);
 
+/* ------------------------------------------------- particle-filter sampling (SMC) --
+ * Sampling under a constraint roll given ALL constraints: G melodies own P particle rows each, row
+ * r = m * P + p, R = G * P.  Every launch reads the generation step c = *step_dev (the frame chain's Philox counter) and
+ * works on step k = c - S only for 0 <= k < nsteps (seed steps and the bridge carry no constraint and no weight).
+ * clv_smc_sample: one wave per row.  x[r,j] = [u <= p] as clv_bernoulli_sample, then roll row m = r / P (clamp [G,nsteps,D],
+ *   NOT replicated per particle) forces byte 0 / 1; ell[r] = sum over the clamped notes of log q (fp64), q = clip(p, 1e-7,
+ *   1 - 1e-7) in float32 for a note forced on, 1 - that for one forced off; the frame as uint8 into hist [nsteps, R, D].
+ * clv_smc_resample: one workgroup per melody, P <= 1024.  With lw = logW + ell (logW = -log P at k = 0), in fp64:
+ *   logZ[m] += lse = logsumexp(lw), logW = lw - lse, ess[m,k] = (sum e^{lw-M})^2 / sum e^{2(lw-M)}; if ess < tau * P
+ *   systematic resampling with u0 = Philox uniform (stream 0xFFFFFFFD, step c, index m0 + m), logW = -log P, nres[m] += 1,
+ *   flag[m] = 1; anc [nsteps, R] row k holds each row's ancestor (the identity without resampling).  logZ, nres need no
+ *   initialisation (k = 0 starts them).  tau in [0, 1].
+ * clv_smc_gather: buffer rows r <- rows anc[k, r] of the nbuf <= 8 fp32 buffers bufs[i] [R, widths[i]] (host arrays of
+ *   device pointers, captured by value) of every melody with flag set, through scratch (sum_i widths[i] * R floats).
+ * clv_smc_backtrack: n_out draws per melody from the final weights logW by systematic resampling (u0 from step `step`,
+ *   index m0 + m); draw o walks anc back from nsteps-1 and writes its frames to Xs [G, n_out, nsteps, D] (fp32 0 / 1);
+ *   picks [G, n_out] (optional) receives the drawn particle.  No atomics anywhere: bitwise reproducible. */
+int clv_smc_sample(int R, int D, int P, int nsteps, int S, const float* p, const float* u, const uint8_t* clamp,
+                   const int32_t* step_dev, float* x, double* ell, uint8_t* hist, void* stream);
+int clv_smc_resample(int G, int P, int nsteps, int S, uint64_t seed, int64_t m0, double tau, const double* ell, double* logW,
+                     double* logZ, double* ess, int32_t* nres, int32_t* flag, int32_t* anc, const int32_t* step_dev,
+                     void* stream);
+int clv_smc_gather(int R, int P, int nsteps, int S, int nbuf, float* const* bufs, const int* widths, float* scratch,
+                   const int32_t* anc, const int32_t* flag, const int32_t* step_dev, void* stream);
+int clv_smc_backtrack(int G, int P, int nsteps, int D, int n_out, uint64_t seed, int64_t m0, int step, const double* logW,
+                      const int32_t* anc, const uint8_t* hist, float* Xs, int32_t* picks, void* stream);
+
 /* ----------------------------------------------------------------- graphs --
  * thin wrappers so a host without HIP bindings can capture a step once and
  * replay it (launch-bound inner loops: SURVEY.md 7.1 step 8). */
