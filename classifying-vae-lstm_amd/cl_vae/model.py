@@ -58,21 +58,27 @@ def generate_sample(dec_model, w_enc_model, z_enc_model, x_seed, nsteps, w_val=N
     return frames
 
 
-def generate_samples_device(model, x_seeds, nsteps, w_vals, seed=0, use_z_prior=False, clamp=None, particles=None,
-                            resample_threshold=0.5, return_evidence=False):
+def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_prior=False, clamp=None, particles=None,
+                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False):
     """N sequences at once with the frame loop on the device (VaeEngine.generate: one captured hipGraph replayed per
     frame, Philox noise instead of np.random: same distribution, different draws).  x_seeds [N,D], w_vals [N,C];
     returns [N,nsteps,D] float64 like generate_sample does per sequence.  clamp: numpy / torch uint8 [N,nsteps,D]
     constraint roll (0 off, 1 on, harmonize.FREE free): row t constrains frame t (clamped ancestral sampling).
     particles=P: particle-filter sampling given every constraint (VaeEngine.generate_smc; resampling below an
-    ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64."""
+    ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64.
+    w_prior (an engine_generate.WPrior, with particles and instead of w_vals): a w per particle drawn from it, the evidence
+    then log p(constraints | seed); return_key: also the key posterior [N,nsteps,C] and each path's w [N,C]."""
     e = model.engine
     t = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32), device=e.device)
     xs = t(x_seeds)
+    if (w_vals is None) == (w_prior is None):
+        raise ValueError("give exactly one of w_vals and w_prior")
+    if particles is None and (w_prior is not None or return_key):
+        raise ValueError("w_prior and return_key need particles")
     if particles is not None:
         smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, e.cfg['D'], e.device)
-        return smc_samples_numpy(e, xs, t(w_vals), nsteps, seed, use_z_prior, clamp, particles, resample_threshold,
-                                 return_evidence)
+        return smc_samples_numpy(e, xs, None if w_vals is None else t(w_vals), nsteps, seed, use_z_prior, clamp, particles,
+                                 resample_threshold, return_evidence, w_prior=w_prior, return_key=return_key)
     if return_evidence:
         raise ValueError("return_evidence needs particles")
     clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), e.cfg['D'], e.device)

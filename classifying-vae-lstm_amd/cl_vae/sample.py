@@ -9,7 +9,7 @@ if __package__ in (None, ''):
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
 from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, parser_for  # noqa: E402
-from clvae_amd.harmonize import harmonize, print_evidence  # noqa: E402
+from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
@@ -61,17 +61,23 @@ class Sampler:
         picks = [np.random.choice(range(len(self.data.x_test))) for _ in names]
         wins = [np.asarray(self.data.x_test[i]).reshape(self.args.t + 1, -1) for i in picks]
         seeds, sources = np.stack([w[0] for w in wins]), np.stack([w[1:] for w in wins])
-        if self.args.infer_w:
+        particles = getattr(self.args, 'particles', None)
+        infer_key = getattr(self.args, 'infer_key', None)
+        if infer_key:           # --infer_key: the filter weighs the keys by the voice, a key per particle
+            ws = None
+            self.model.engine.cfg['w_log_var_prior'] = float(self.margs.get('w_log_var_prior', 0.0))
+        elif self.args.infer_w:
             ws = [M.sample_w(self.w_enc.predict(s[None, :]), add_noise=False) for s in seeds]
         else:
             ws = [to_categorical(self.data.test_song_keys[i], self.margs['n_classes']) for i in picks]
-        particles = getattr(self.args, 'particles', None)
-        out = harmonize(self.model, seeds, sources, np.vstack(ws), voice=voice_of(self.args),
+        out = harmonize(self.model, seeds, sources, None if ws is None else np.vstack(ws), voice=voice_of(self.args),
                         seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior, particles=particles,
-                        return_evidence=particles is not None)
+                        return_evidence=particles is not None, **(dict(infer_key=infer_key) if infer_key else {}))
         rolls = out[0] if particles is not None else out
         if particles is not None:
             print_evidence(names, out[1], self.args.t)
+            if infer_key:
+                print_key_posterior(names, out[2], self.data.key_map)
         for roll, src, name in zip(rolls, sources, names):
             write_sample(roll, self.args.sample_dir, name, True)
             write_sample(src, self.args.sample_dir, name + '_source', True)

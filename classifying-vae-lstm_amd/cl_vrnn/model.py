@@ -235,8 +235,8 @@ class Encoder:
         return [Zargs[..., :L], Zargs[..., L:], W]
 
 
-def generate_samples_device(model, x_seeds, nsteps, w_vals, seed=0, z_prior=False, clamp=None, particles=None,
-                            resample_threshold=0.5, return_evidence=False):
+def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
+                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False):
     """Batched, device-resident counterpart of generate_sample: N seeds at once, the whole frame loop as
     replays of one captured hipGraph, Philox noise instead of np.random (so the draws differ from the numpy
     path, the distribution does not).  x_seeds [N,S,88] (S >= 0 teacher-forced frames), w_vals [N,C].
@@ -244,13 +244,21 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals, seed=0, z_prior=Fals
     clamp: numpy / torch uint8 [N,nsteps,88] constraint roll (0 off, 1 on, harmonize.FREE free): row j constrains
     returned frame j (clamped ancestral sampling; the unreturned bridge sample of step S-1 stays free).
     particles=P: particle-filter sampling given every constraint (VrnnEngine.generate_smc; resampling below
-    an ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64."""
+    an ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64.
+    w_prior (an engine_generate.WPrior, with particles and instead of w_vals): a w per particle drawn from it, the evidence
+    then log p(constraints | seed); return_key: also the key posterior [N,nsteps,C] and each path's w [N,C]."""
     e = model.engine
     xs = torch.as_tensor(np.ascontiguousarray(np.asarray(x_seeds), dtype=np.float32), device=e.device)
-    w = torch.as_tensor(np.ascontiguousarray(np.asarray(w_vals), dtype=np.float32), device=e.device)
+    if (w_vals is None) == (w_prior is None):
+        raise ValueError("give exactly one of w_vals and w_prior")
+    if particles is None and (w_prior is not None or return_key):
+        raise ValueError("w_prior and return_key need particles")
+    w = None if w_vals is None else torch.as_tensor(np.ascontiguousarray(np.asarray(w_vals), dtype=np.float32),
+                                                    device=e.device)
     if particles is not None:
         smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, e.cfg['D'], e.device)
-        return smc_samples_numpy(e, xs, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence)
+        return smc_samples_numpy(e, xs, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
+                                 w_prior=w_prior, return_key=return_key)
     if return_evidence:
         raise ValueError("return_evidence needs particles")
     clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), e.cfg['D'], e.device)

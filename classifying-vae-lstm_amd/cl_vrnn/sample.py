@@ -9,7 +9,7 @@ if __package__ in (None, ''):
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
 from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, parser_for  # noqa: E402
-from clvae_amd.harmonize import harmonize, print_evidence  # noqa: E402
+from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
@@ -58,15 +58,24 @@ def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice
         return []
     seeds = np.stack([np.asarray(P.x_test[i])[:t] for i in picks])
     sources = np.stack([np.asarray(P.x_test[i])[t:2 * t] for i in picks])
-    ws = [label_of(i) for i in picks]
-    if args.infer_w:
-        ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in seeds]
     particles = getattr(args, 'particles', None)
-    out = harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0), particles=particles,
-                    return_evidence=particles is not None)
+    infer_key = getattr(args, 'infer_key', None)
+    if infer_key:               # --infer_key: the filter weighs the keys by the voice, a key per particle
+        model.engine.cfg['w_log_var_prior'] = float(margs.get('w_log_var_prior', 0.0))      # load_model rebuilds layers only
+        out = harmonize(model, seeds, sources, None, voice=voice, seed=getattr(args, 'seed', 0), particles=particles,
+                        return_evidence=True, infer_key=infer_key)
+    else:
+        ws = [label_of(i) for i in picks]
+        if args.infer_w:
+            ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in seeds]
+        out = harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0),
+                        particles=particles, return_evidence=particles is not None)
     rolls = list(out[0] if particles is not None else out)
     if particles is not None:
-        print_evidence(['%s_%d' % (args.run_name, j) for j in range(len(rolls))], out[1], t)
+        names = ['%s_%d' % (args.run_name, j) for j in range(len(rolls))]
+        print_evidence(names, out[1], t)
+        if infer_key:
+            print_key_posterior(names, out[2], P.key_map)
     for j, (i, roll) in enumerate(zip(picks, rolls)):
         write_sample(roll, args.sample_dir, '%s_%d' % (args.run_name, j), half_speed)
         write_sample(sources[j], args.sample_dir, '%s_%d_source' % (args.run_name, j), half_speed)

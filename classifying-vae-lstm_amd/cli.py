@@ -113,11 +113,15 @@ HARMONIZE_FLAGS = [
                                       'the other voices (clamped sampling on the device; implies --device_loop)'),
     Flag(('--particles',), int, None, 'with --harmonize: sample given the whole voice with a particle filter of this many '
                                       'particles per sample (DESIGN.md 11) and print log p(voice) per frame'),
+    Flag(('--infer_key',), str, None, 'with --particles: infer the key from the voice while harmonizing, a key per '
+                                      'particle (DESIGN.md 12): discrete keys under a uniform prior, or continuous w under '
+                                      "the model's logistic-normal prior; prints the key posterior"),
 ]
+INFER_KEY_CHOICES = ('discrete', 'continuous')
 
 
 class _Parser(argparse.ArgumentParser):
-    """argparse with the one rule between flags: --particles only with --harmonize"""
+    """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -127,6 +131,8 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--particles needs --harmonize')
             if particles < 1:
                 self.error('--particles must be >= 1')
+        elif getattr(ns, 'infer_key', None):
+            self.error('--infer_key needs --particles')
         return ns, rest
 
 
@@ -139,6 +145,8 @@ def parser_for(tool, extra=()):
             p.add_argument(*f.names, type=f.kind, default=f.default, choices=SPLIT_CHOICES, help=f.help)
         elif f.names == ('--harmonize',):
             p.add_argument(*f.names, type=f.kind, default=f.default, choices=HARMONIZE_CHOICES, help=f.help)
+        elif f.names == ('--infer_key',):
+            p.add_argument(*f.names, type=f.kind, default=f.default, choices=INFER_KEY_CHOICES, help=f.help)
         elif f.names[0].startswith('-'):
             p.add_argument(*f.names, type=f.kind, default=f.default, help=f.help)
         else:

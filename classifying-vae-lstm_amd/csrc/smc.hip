@@ -7,6 +7,9 @@
 //   clv_smc_resample  one workgroup per melody: log Z, normalized log weights, ESS, systematic resampling, ancestors A_t;
 //   clv_smc_gather    the rows of the state buffers permuted by A_t (through a scratch buffer: a gather is not in place);
 // and once at the end clv_smc_backtrack draws the returned paths from the final weights and walks the lineage.
+// With a key prior every particle carries its own label row: clv_smc_init_w draws the rows once per chunk,
+// the gather moves them with the state, clv_smc_w_posterior (in the frame, after the gather) writes the weighted mean of
+// the rows, and clv_smc_take_w copies the rows of the returned paths.
 // Every output element has one owner and no kernel uses atomics, so every result is bitwise reproducible.
 #include "common.h"
 #include "philox.h"
@@ -14,6 +17,8 @@
 namespace clv {
 
 constexpr uint32_t SMC_STREAM = 0xFFFFFFFDu;        // trainer.py's stream map, next to the IW pair
+constexpr uint32_t SMC_W_STREAM = 0xFFFFFFFCu;      // the particles' keys: step 0 the categorical u0, step 1 the eps
+constexpr int SMC_MAX_C = 32;                        // classes of a label row (MAXC of the label kernels)
 constexpr int SMC_MAX_P = 1024;                      // particles per melody: one workgroup holds them
 constexpr int SMC_MAX_BUFS = 8;
 constexpr float SMC_CLIP_LO = 1e-7f, SMC_CLIP_HI = 1.0f - 1e-7f;   // Keras float32 BCE clip (BCE_CLIP_* on the logits)
@@ -210,6 +215,83 @@ __global__ __launch_bounds__(SMC_MAX_P) void smc_backtrack_kernel(int P, int nst
   }
 }
 
+// One workgroup per melody, thread p owns row r = m * P + p of wr [R, C].
+// mode 0 (categorical): cum = inclusive fp64 sums of probs[m] in class order; particle p takes the first class with
+// P * cum_c > u0 + p (systematic_pick: the last class if none) and writes its one-hot row.
+// mode 1 (logistic-normal): s_c = mean + exp(log_var / 2) * eps (float32, eps at the GLOBAL row), w = softmax([s, 0]).
+__global__ __launch_bounds__(SMC_MAX_P) void smc_init_w_kernel(int P, int C, int mode, uint64_t seed, int64_t m0,
+                                                               const double* probs, const float* mean,
+                                                               const float* log_var, float* wr) {
+  __shared__ double cum[SMC_MAX_C];
+  const int m = blockIdx.x, p = threadIdx.x;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  if (mode == 0) {
+    if (p == 0) {
+      const double* pm = probs + (int64_t)m * C;
+      double s = 0.0;
+      for (int c = 0; c < C; ++c) cum[c] = s += pm[c];
+    }
+    __syncthreads();
+    if (p >= P) return;
+    const double u0 = (double)philox_uniform_at((uint64_t)(m0 + m), k0, k1, SMC_W_STREAM, 0u);
+    const int key = systematic_pick(cum, C, (double)P, u0 + (double)p);
+    float* out = wr + ((int64_t)m * P + p) * C;
+    for (int c = 0; c < C; ++c) out[c] = c == key ? 1.f : 0.f;
+    return;
+  }
+  if (p >= P) return;
+  const int C1 = C - 1;
+  const uint64_t e0 = (uint64_t)((m0 + m) * P + p) * (uint64_t)C1;
+  const float* mu = mean + (int64_t)m * C1;
+  const float* lv = log_var + (int64_t)m * C1;
+  float s[SMC_MAX_C];
+  float M = 0.f;                                 // the appended zero takes part in the max
+  for (int c = 0; c < C1; ++c) {
+    s[c] = mu[c] + expf(0.5f * lv[c]) * philox_normal_at(e0 + c, k0, k1, SMC_W_STREAM, 1u);
+    M = fmaxf(M, s[c]);
+  }
+  s[C1] = 0.f;
+  float sum = 0.f;
+  for (int c = 0; c < C; ++c) sum += s[c] = expf(s[c] - M);
+  float* out = wr + ((int64_t)m * P + p) * C;
+  for (int c = 0; c < C; ++c) out[c] = s[c] / sum;
+}
+
+constexpr int SMC_POST_THREADS = 256;
+
+// out[m, k, c] = sum_p exp(logW[r]) * wr[r, c] from the weights and rows the next step starts from (after the gather).
+// The weights go through LDS once; then a wave per class: every lane sums its particles p = lane, lane + 64, ... in that
+// order, the lanes by the butterfly, and lane 0 owns the output element.
+__global__ __launch_bounds__(SMC_POST_THREADS) void smc_w_posterior_kernel(int P, int C, int nsteps, int S, const double* logW,
+                                                                           const float* wr, const int32_t* step_dev,
+                                                                           double* out) {
+  __shared__ double wexp[SMC_MAX_P];
+  const int k = *step_dev - S;
+  if (k < 0 || k >= nsteps) return;             // uniform exit before the barrier, as smc_resample_kernel
+  const int m = blockIdx.x;
+  const double* lw = logW + (int64_t)m * P;
+  for (int p = threadIdx.x; p < P; p += SMC_POST_THREADS) wexp[p] = exp(lw[p]);
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const float* rows = wr + (int64_t)m * P * C;
+  double* o = out + ((int64_t)m * nsteps + k) * C;
+  for (int c = threadIdx.x >> 6; c < C; c += SMC_POST_THREADS / 64) {
+    double a = 0.0;
+    for (int p = lane; p < P; p += 64) a += wexp[p] * (double)rows[(int64_t)p * C + c];
+    a = smc_wave_sum(a);
+    if (lane == 0) o[c] = a;
+  }
+}
+
+// w_out[m, o, :] = wr[m * P + picks[m, o], :]: the label row of the particle each returned path was drawn from
+__global__ void smc_take_w_kernel(int n, int P, int C, int n_out, const int32_t* picks, const float* wr, float* w_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int c = i % C, mo = i / C, m = mo / n_out;
+  const int pick = min(max(picks[mo], 0), P - 1);
+  w_out[i] = wr[((int64_t)m * P + pick) * C + c];
+}
+
 static inline int smc_block(int P) { return (P + 63) / 64 * 64; }
 
 }  // namespace clv
@@ -277,5 +359,42 @@ extern "C" int clv_smc_backtrack(int G, int P, int nsteps, int D, int n_out, uin
   ProfScope pr("smc_backtrack", s);
   hipLaunchKernelGGL(smc_backtrack_kernel, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, D, n_out, seed, m0, step, logW, anc,
                      hist, Xs, picks, G * P);
+  return launch_status();
+}
+
+extern "C" int clv_smc_init_w(int G, int P, int C, int mode, uint64_t seed, int64_t m0, const double* probs,
+                              const float* mean, const float* log_var, float* wr, void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || C < 2 || C > SMC_MAX_C || m0 < 0 || !wr) return CLV_EINVAL;
+  if (mode == 0 ? !probs : (mode != 1 || !mean || !log_var)) return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_init_w", s);
+  hipLaunchKernelGGL(smc_init_w_kernel, dim3(G), dim3(smc_block(P)), 0, s, P, C, mode, seed, m0, probs, mean, log_var, wr);
+  return launch_status();
+}
+
+extern "C" int clv_smc_w_posterior(int G, int P, int C, int nsteps, int S, const double* logW, const float* wr,
+                                   const int32_t* step_dev, double* out, void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || C < 2 || C > SMC_MAX_C || nsteps <= 0 || S < 0 || !logW || !wr || !step_dev ||
+      !out)
+    return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_w_posterior", s);
+  hipLaunchKernelGGL(smc_w_posterior_kernel, dim3(G), dim3(SMC_POST_THREADS), 0, s, P, C, nsteps, S, logW, wr, step_dev,
+                     out);
+  return launch_status();
+}
+
+extern "C" int clv_smc_take_w(int G, int P, int C, int n_out, const int32_t* picks, const float* wr, float* w_out,
+                              void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || C < 2 || C > SMC_MAX_C || n_out <= 0 || !picks || !wr || !w_out)
+    return CLV_EINVAL;
+  const int64_t n = (int64_t)G * n_out * C;
+  if ((int64_t)G * P > INT32_MAX || n > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_take_w", s);
+  hipLaunchKernelGGL(smc_take_w_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (int)n, P, C, n_out, picks, wr,
+                     w_out);
   return launch_status();
 }

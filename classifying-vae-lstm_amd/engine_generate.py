@@ -37,7 +37,76 @@ SmcResult = namedtuple('SmcResult', 'Xs log_evidence ess resamples')
 SmcResult.__doc__ = """generate_smc's outputs (device tensors): Xs [N, n_out, nsteps, D] fp32 frames, log_evidence [N] fp64 (log Z:
 the estimate of log p(constraints | seed, w)), ess [N, nsteps] fp64 (after each frame's reweighting), resamples [N] int32."""
 
+SmcKeyResult = namedtuple('SmcKeyResult', SmcResult._fields + ('w_posterior', 'w_out'))
+SmcKeyResult.__doc__ = """generate_smc(w_prior=...)'s outputs (DESIGN.md 12): SmcResult's four fields, log_evidence now the estimate
+of log p(constraints | seed) with the key marginalised out, then w_posterior [N, nsteps, C] fp64 (the weighted mean of the
+particles' label rows after each step: p(key | seed, constraints so far) for a categorical prior) and w_out [N, n_out, C]
+fp32 (the label row each returned path carried).  SmcResult itself keeps four fields: callers iterate over it."""
+
 SMC_MAX_PARTICLES = 1024            # one workgroup of clv_smc_resample holds a melody's particles
+SMC_MAX_CLASSES = 32                # SMC_MAX_C of csrc/smc.hip
+
+
+class WPrior:
+    """A prior over the label w of each of N melodies, from which generate_smc draws a w per particle.
+    categorical(probs [N, C]): a key per particle, w its one-hot row.  logistic_normal(mean, log_var [N, C-1]):
+    w = softmax([mean + exp(log_var / 2) * eps, 0]), the label path's own sample."""
+
+    def __init__(self, kind, N, C, probs=None, mean=None, log_var=None):
+        self.kind, self.N, self.C, self.probs, self.mean, self.log_var = kind, N, C, probs, mean, log_var
+
+    @classmethod
+    def categorical(cls, probs):
+        p = np.array(probs, dtype=np.float64, ndmin=2)
+        if p.ndim != 2 or p.shape[0] < 1 or not 2 <= p.shape[1] <= SMC_MAX_CLASSES:
+            raise ValueError("probs must be [N, C] with 2 <= C <= %d, got shape %s" % (SMC_MAX_CLASSES, p.shape))
+        if not np.all(np.isfinite(p)) or np.any(p < 0):
+            raise ValueError("probs must be finite and >= 0")
+        tot = p.sum(axis=1)
+        if np.any(np.abs(tot - 1.0) > 1e-6):
+            raise ValueError("every row of probs must sum to 1 (within 1e-6), got sums in [%r, %r]" % (tot.min(), tot.max()))
+        # the last bits of the sum: P * cum_C must pass u0 + P - 1 so that the tail rule never hands out a class of mass 0
+        return cls('categorical', p.shape[0], p.shape[1], probs=np.ascontiguousarray(p / tot[:, None]))
+
+    @classmethod
+    def logistic_normal(cls, mean, log_var):
+        m, lv = np.array(mean, dtype=np.float32, ndmin=2), np.array(log_var, dtype=np.float32, ndmin=2)
+        if m.ndim != 2 or m.shape != lv.shape or m.shape[0] < 1 or not 1 <= m.shape[1] < SMC_MAX_CLASSES:
+            raise ValueError("mean and log_var must both be [N, C-1] with 2 <= C <= %d, got shapes %s and %s"
+                             % (SMC_MAX_CLASSES, m.shape, lv.shape))
+        if not (np.all(np.isfinite(m)) and np.all(np.isfinite(lv))):
+            raise ValueError("mean and log_var must be finite")
+        return cls('logistic_normal', m.shape[0], m.shape[1] + 1, mean=np.ascontiguousarray(m), log_var=np.ascontiguousarray(lv))
+
+    @classmethod
+    def uniform(cls, N, C):
+        """every key equally likely"""
+        return cls.categorical(np.full((int(N), int(C)), 1.0 / int(C)))
+
+    def to(self, device):
+        """the prior's arrays as device tensors (probs float64; mean, log_var float32)"""
+        t = lambda a: None if a is None else torch.from_numpy(a).to(device)
+        return WPrior(self.kind, self.N, self.C, t(self.probs), t(self.mean), t(self.log_var))
+
+    def init_rows(self, m0, m1, P, seed, wr):
+        """draw the label rows wr [(m1-m0) * P, C] of melodies m0 .. m1-1 (device arrays: call on the result of to())"""
+        sl = lambda a: None if a is None else a[m0:m1]
+        mode = ops.SMC_W_CATEGORICAL if self.kind == 'categorical' else ops.SMC_W_LOGISTIC_NORMAL
+        ops.smc_init_w(m1 - m0, P, self.C, mode, seed, m0, sl(self.probs), sl(self.mean), sl(self.log_var), wr)
+
+
+def smc_label_args(w, w_prior, N, C, device):
+    """generate_smc takes exactly one of w [N, C] and w_prior (a WPrior over N melodies and C classes); returns
+    (w as a float32 device tensor or None, the prior on the device or None)"""
+    if (w is None) == (w_prior is None):
+        raise ValueError("give exactly one of w and w_prior")
+    if w_prior is None:
+        return w.to(dtype=torch.float32, device=device), None
+    if not isinstance(w_prior, WPrior):
+        raise ValueError("w_prior must be a WPrior, got %r" % type(w_prior).__name__)
+    if (w_prior.N, w_prior.C) != (int(N), int(C)):
+        raise ValueError("w_prior is over %d melodies x %d classes, the call over %d x %d" % (w_prior.N, w_prior.C, N, C))
+    return None, w_prior.to(device)
 
 
 def smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, device):
@@ -56,12 +125,21 @@ def smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, device):
     return clamp_roll(clamp, N, nsteps, D, device)
 
 
-def smc_samples_numpy(engine, x_seed, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence):
-    """generate_samples_device(particles=P): one draw per melody, [N, nsteps, D] float64 (and log_evidence [N] float64)"""
+def smc_samples_numpy(engine, x_seed, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
+                      w_prior=None, return_key=False):
+    """generate_samples_device(particles=P): one draw per melody, [N, nsteps, D] float64 (and log_evidence [N] float64;
+    with return_key, under a w_prior, also w_posterior [N, nsteps, C] and the path's label w_out [N, C], float64)"""
+    if return_key and w_prior is None:
+        raise ValueError("return_key needs a w_prior")
+    kw = {} if w_prior is None else dict(w_prior=w_prior)
     r = engine.generate_smc(x_seed, w, int(nsteps), clamp, particles, resample_threshold, n_out=1, seed=int(seed),
-                            z_prior=z_prior)
-    Xs = r.Xs[:, 0].cpu().numpy().astype(np.float64)
-    return (Xs, r.log_evidence.cpu().numpy()) if return_evidence else Xs
+                            z_prior=z_prior, **kw)
+    out = [r.Xs[:, 0].cpu().numpy().astype(np.float64)]
+    if return_evidence:
+        out.append(r.log_evidence.cpu().numpy())
+    if return_key:
+        out += [r.w_posterior.cpu().numpy(), r.w_out[:, 0].cpu().numpy().astype(np.float64)]
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 class _Smc:
@@ -69,8 +147,11 @@ class _Smc:
     log Z, ESS, resample counts, ancestors A_t [nsteps, R] and the uint8 frame history [nsteps, R, D].  step() is the SMC
     part of one frame (sample, resample, gather); finish() draws the returned paths."""
 
-    def __init__(self, G, P, nsteps, S, D, tau, seed, m0, clamp, device):
+    def __init__(self, G, P, nsteps, S, D, tau, seed, m0, clamp, device, wr=None):
         self.G, self.P, self.R, self.nsteps, self.S, self.D = G, P, G * P, nsteps, S, D
+        self.wr = wr                # the particles' own label rows [R, C] under a key prior (DESIGN.md 12), else None
+        if wr is not None:
+            self.w_post = torch.zeros(G, nsteps, wr.shape[1], dtype=torch.float64, device=device)
         self.tau, self.seed, self.m0, self.clamp = tau, seed, m0, clamp
         f64 = dict(dtype=torch.float64, device=device)
         i32 = dict(dtype=torch.int32, device=device)
@@ -85,10 +166,16 @@ class _Smc:
         ops.smc_resample(self.G, self.P, self.nsteps, self.S, self.seed, self.m0, self.tau, self.ell, self.logW, self.logZ,
                          self.ess, self.nres, self.flag, self.anc, counter)
         gather(self.anc, self.flag, counter)
+        if self.wr is not None:
+            ops.smc_w_posterior(self.G, self.P, self.wr.shape[1], self.nsteps, self.S, self.logW, self.wr, counter,
+                                self.w_post)
 
-    def finish(self, n_out, Xs):
+    def finish(self, n_out, Xs, w_out=None):
+        picks = None if self.wr is None else torch.zeros(self.G, n_out, dtype=torch.int32, device=Xs.device)
         ops.smc_backtrack(self.G, self.P, self.nsteps, self.D, n_out, self.seed, self.m0, self.S + self.nsteps, self.logW,
-                          self.anc, self.hist, Xs)
+                          self.anc, self.hist, Xs, picks)
+        if self.wr is not None:     # the gather moved the rows with the state: the final particle holds its path's key
+            ops.smc_take_w(self.G, self.P, self.wr.shape[1], n_out, picks, self.wr, w_out)
 
 
 def _smc_chunks(N, P, cap, chunk):
@@ -103,13 +190,21 @@ def _smc_chunks(N, P, cap, chunk):
     return [(m0, min(N, m0 + g)) for m0 in range(0, N, g)]
 
 
-def _smc_drive(chunks, run_chunk, N, nsteps, D, n_out, device):
+def _smc_drive(chunks, run_chunk, N, nsteps, D, n_out, device, C=None):
+    """C: the number of classes when the filter carries a key per particle (SmcKeyResult), else None (SmcResult)"""
     f = dict(device=device)
     out = SmcResult(torch.zeros(N, n_out, nsteps, D, dtype=torch.float32, **f), torch.zeros(N, dtype=torch.float64, **f),
                     torch.zeros(N, nsteps, dtype=torch.float64, **f), torch.zeros(N, dtype=torch.int32, **f))
+    if C is not None:
+        out = SmcKeyResult(*out, torch.zeros(N, nsteps, C, dtype=torch.float64, **f),
+                           torch.zeros(N, n_out, C, dtype=torch.float32, **f))
     for m0, m1 in chunks:
         smc = run_chunk(m0, m1)
-        smc.finish(n_out, out.Xs[m0:m1])
+        if C is None:
+            smc.finish(n_out, out.Xs[m0:m1])
+        else:
+            smc.finish(n_out, out.Xs[m0:m1], out.w_out[m0:m1])
+            out.w_posterior[m0:m1].copy_(smc.w_post)
         out.log_evidence[m0:m1].copy_(smc.logZ)
         out.ess[m0:m1].copy_(smc.ess)
         out.resamples[m0:m1].copy_(smc.nres)
@@ -175,30 +270,38 @@ class VaeGenerate:
         return Xs
 
     def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
-                     z_prior=False, chunk=None):
+                     z_prior=False, chunk=None, w_prior=None):
         """Particle-filter sampling under the constraint roll clamp [N, nsteps, D]: melody m runs P =
         `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
         probability of each frame's clamped notes and resampled (systematic, below an ESS of resample_threshold * P).
         Row t of the roll constrains frame t.  Melodies are processed in chunks of at most batch-size rows (and at most
         `chunk` melodies); the Philox keys follow the global row, so the result does not depend on the chunking.
-        x_seed [N, D], w [N, C] device tensors.  Returns SmcResult (Xs [N, n_out, nsteps, D])."""
+        x_seed [N, D], w [N, C] device tensors.  Returns SmcResult (Xs [N, n_out, nsteps, D]).
+        w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state, so the filter
+        targets p(w, free notes | seed, constraints); returns SmcKeyResult."""
         cfg, d = self.cfg, self.device
         N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
         clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
         P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
         f = dict(dtype=torch.float32, device=d)
-        x_seed, w = x_seed.to(**f), w.to(**f)
+        x_seed = x_seed.to(**f)
+        w, prior = smc_label_args(w, w_prior, N, cfg['C'], d)
 
         def run_chunk(m0, m1):
             G = m1 - m0
             R, r0 = G * P, m0 * P
             x_in = x_seed[m0:m1].repeat_interleave(P, 0).contiguous()
             hist, x_next = x_in.clone(), torch.zeros(R, D, **f)
-            wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+            if prior is None:
+                wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+            else:
+                wr = torch.zeros(R, cfg['C'], **f)
+                prior.init_rows(m0, m1, P, seed, wr)
             eps, u = torch.zeros(R, L, **f), torch.zeros(R, D, **f)
             counter = torch.zeros(1, dtype=torch.int32, device=d)
-            smc = _Smc(G, P, nsteps, 0, D, tau, seed, m0, clamp[m0:m1], d)
-            gather = ops.SmcGather(R, P, nsteps, 0, [x_next, x_in])     # x_in becomes the decoder's history below
+            smc = _Smc(G, P, nsteps, 0, D, tau, seed, m0, clamp[m0:m1], d, wr=None if prior is None else wr)
+            # x_in becomes the decoder's history below; a particle's own key travels with its state
+            gather = ops.SmcGather(R, P, nsteps, 0, [x_next, x_in] + ([] if prior is None else [wr]))
 
             def frame():
                 self.encode_z(x_in, wr, R)
@@ -216,7 +319,8 @@ class VaeGenerate:
             _replay(frame, nsteps, use_graph)
             return smc
 
-        return _smc_drive(_smc_chunks(N, P, self.B, chunk), run_chunk, N, nsteps, D, int(n_out), d)
+        return _smc_drive(_smc_chunks(N, P, self.B, chunk), run_chunk, N, nsteps, D, int(n_out), d,
+                          C=None if prior is None else cfg['C'])
 
 
 def _replay(frame, nsteps, use_graph, before=None):
@@ -363,32 +467,41 @@ class VrnnGenerate:
         return Xs
 
     def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
-                     z_prior=False, chunk=None):
+                     z_prior=False, chunk=None, w_prior=None):
         """Particle-filter sampling under the constraint roll clamp [N, nsteps, D]: melody m runs P =
         `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
         probability of each returned frame's clamped notes and resampled (systematic, below an ESS of
         resample_threshold * P).  Row j of the roll constrains the sample of step S+j; the seed steps and the bridge carry
         no constraint and no weight.  `chunk`: at most that many melodies per pass (the Philox keys follow the global row,
-        so the result does not depend on it).  x_seed [N, S, D], w [N, C] device tensors.  Returns SmcResult."""
+        so the result does not depend on it).  x_seed [N, S, D], w [N, C] device tensors.  Returns SmcResult.
+        w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state (the seed steps
+        run under it too, unweighted), so the filter targets p(w, free notes | seed, constraints); returns
+        SmcKeyResult."""
         cfg, d = self.cfg, self.device
         N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
         D, L = cfg['D'], cfg['L']
         clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
         P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
         f = dict(dtype=torch.float32, device=d)
-        x_seed, w = x_seed.to(**f), w.to(**f)
+        x_seed = x_seed.to(**f)
+        w, prior = smc_label_args(w, w_prior, N, cfg['C'], d)
 
         def run_chunk(m0, m1):
             G = m1 - m0
             R, r0 = G * P, m0 * P
             xs = x_seed[m0:m1].repeat_interleave(P, 0)
-            wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+            if prior is None:
+                wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+            else:
+                wr = torch.zeros(R, cfg['C'], **f)
+                prior.init_rows(m0, m1, P, seed, wr)
             st = self.new_state(R)
             x_prev, x_next = torch.zeros(R, D, **f), torch.zeros(R, D, **f)
             eps, u, z = torch.zeros(R, L, **f), torch.zeros(R, D, **f), torch.zeros(R, L, **f)
             counter = torch.zeros(1, dtype=torch.int32, device=d)
-            smc = _Smc(G, P, nsteps, S, D, tau, seed, m0, clamp[m0:m1], d)
-            gather = ops.SmcGather(R, P, nsteps, S, [st['h_enc'], st['c_enc'], st['h_dec'], st['c_dec'], x_next])
+            smc = _Smc(G, P, nsteps, S, D, tau, seed, m0, clamp[m0:m1], d, wr=None if prior is None else wr)
+            gather = ops.SmcGather(R, P, nsteps, S, [st['h_enc'], st['c_enc'], st['h_dec'], st['c_dec'], x_next]
+                                   + ([] if prior is None else [wr]))     # a particle's own key travels with its state
 
             def frame():
                 self.enc_step(x_prev, wr, st)
@@ -409,4 +522,5 @@ class VrnnGenerate:
             _replay(frame, S + nsteps, use_graph, before)
             return smc
 
-        return _smc_drive(_smc_chunks(N, P, None, chunk), run_chunk, N, nsteps, D, int(n_out), d)
+        return _smc_drive(_smc_chunks(N, P, None, chunk), run_chunk, N, nsteps, D, int(n_out), d,
+                          C=None if prior is None else cfg['C'])

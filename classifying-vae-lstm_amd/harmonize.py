@@ -5,7 +5,8 @@ note off, 1 forces it on, FREE (any other value) leaves it to the model.  The ou
 the recurrent state, so inside a frame the free notes are drawn exactly from p(free notes | past, z_t, w); the clamped
 frame is then fed back as the next input.  This is clamped ancestral sampling: it does not condition on constraints that
 lie in the future.  harmonize(particles=P) samples given the whole voice instead, with a particle filter
-(DESIGN.md 11), and can return the model's log p(voice | seed, w)."""
+(DESIGN.md 11), and can return the model's log p(voice | seed, w).  harmonize(particles=P, infer_key=...) gives every
+particle a key of its own, so that the key follows the voice: it also returns the posterior over the key."""
 import numpy as np
 
 FREE = 255
@@ -37,30 +38,72 @@ def voice_constraints(roll, voice='top', fence=True):
     return out
 
 
-def harmonize(model, seeds, source_rolls, w_vals, voice='top', seed=0, fence=True, z_prior=False, particles=None,
-              resample_threshold=0.5, return_evidence=False):
+INFER_KEY = ('discrete', 'continuous')
+
+
+def default_w_prior(model, N, infer_key):
+    """the key prior of harmonize(infer_key=...): 'discrete' every key equally likely, 'continuous' the model's own
+    logistic-normal prior (mean 0, log variance w_log_var_prior)"""
+    from .engine_generate import WPrior
+    cfg = model.engine.cfg
+    if infer_key == 'discrete':
+        return WPrior.uniform(N, cfg['C'])
+    shape = (N, cfg['C'] - 1)
+    return WPrior.logistic_normal(np.zeros(shape), np.full(shape, float(cfg.get('w_log_var_prior', 0.0))))
+
+
+def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fence=True, z_prior=False, particles=None,
+              resample_threshold=0.5, return_evidence=False, infer_key=None, w_prior=None):
     """Generate len(seeds) sequences that keep the `voice` of source_rolls [N, nsteps, 88] and fill in the rest, with the
     frame loop on the device.  seeds: cl_vrnn [N, S, 88] teacher-forced frames (the first source frame follows them),
     cl_vae [N, 88] (frame 0 of the sequence; the first source frame is frame 1).  Returns [N, nsteps, 88] float64.
     particles=P: a particle filter of P particles per melody samples given the whole voice instead of
-    clamped ancestral sampling; return_evidence (with particles) also returns log p(voice | seed, w) [N] float64."""
+    clamped ancestral sampling; return_evidence (with particles) also returns log p(voice | seed, w) [N] float64.
+    infer_key='discrete' | 'continuous' (with particles, instead of w_vals): every particle draws its own w from a prior
+    over the key (default_w_prior, or the WPrior given as w_prior) and the filter weighs the keys by the voice
+    (DESIGN.md 12).  The evidence is then log p(voice | seed), and the call also returns, after it, the key posterior
+    w_posterior [N, nsteps, C] (after each frame) and the label w_out [N, C] of each returned sequence, float64."""
     from .engine import VaeEngine
     source_rolls = np.asarray(source_rolls)
     if source_rolls.ndim != 3:
         raise ValueError("source_rolls must be [N, nsteps, 88], got shape %s" % (source_rolls.shape,))
+    extra = {}
+    if infer_key is not None:
+        if infer_key not in INFER_KEY:
+            raise ValueError("infer_key must be one of %s, got %r" % (INFER_KEY, infer_key))
+        if w_vals is not None:
+            raise ValueError("give either w_vals or infer_key, not both")
+        if particles is None:
+            raise ValueError("infer_key needs particles: a single path cannot weigh keys")
+        extra = dict(w_prior=w_prior if w_prior is not None else default_w_prior(model, source_rolls.shape[0], infer_key),
+                     return_key=True)
+    elif w_prior is not None:
+        raise ValueError("w_prior needs infer_key")
+    elif w_vals is None:
+        raise ValueError("harmonize needs w_vals (or infer_key with particles)")
     clamp = voice_constraints(source_rolls, voice, fence)
     nsteps = source_rolls.shape[1]
     if isinstance(model.engine, VaeEngine):
         from .cl_vae.model import generate_samples_device
         return generate_samples_device(model, seeds, nsteps, w_vals, seed=seed, use_z_prior=z_prior, clamp=clamp,
                                        particles=particles, resample_threshold=resample_threshold,
-                                       return_evidence=return_evidence)
+                                       return_evidence=return_evidence, **extra)
     from .cl_vrnn.model import generate_samples_device
     return generate_samples_device(model, seeds, nsteps, w_vals, seed=seed, z_prior=z_prior, clamp=clamp, particles=particles,
-                                   resample_threshold=resample_threshold, return_evidence=return_evidence)
+                                   resample_threshold=resample_threshold, return_evidence=return_evidence, **extra)
 
 
 def print_evidence(names, log_evidence, nsteps):
     """one line per harmonization: log p(voice | seed, w) per frame (the sample CLIs' --particles)"""
     for name, le in zip(names, np.asarray(log_evidence, dtype=np.float64)):
         print('%s: log p(voice) per frame %.4f (total %.4f over %d frames)' % (name, le / nsteps, le, nsteps))
+
+
+def print_key_posterior(names, w_posterior, key_map):
+    """one line per harmonization: the posterior over the key after the last frame, most probable key first (the sample
+    CLIs' --infer_key); key_map: PianoData.key_map (key name -> class index)"""
+    name_of = {int(idx): str(name) for name, idx in key_map.items()}
+    for name, post in zip(names, np.asarray(w_posterior, dtype=np.float64)[:, -1]):
+        order = np.argsort(-post, kind='stable')
+        print('%s: key posterior %s' % (name, ' '.join('%s=%.4f' % (name_of.get(int(c), str(int(c))), post[c])
+                                                         for c in order)))

@@ -742,6 +742,29 @@ def smc_backtrack(G, P, nsteps, D, n_out, seed, m0, step, logW, anc, hist, Xs, p
                                        _ptr(hist), _ptr(Xs), _ptr(picks), _stream()), "clv_smc_backtrack")
 
 
+SMC_W_CATEGORICAL, SMC_W_LOGISTIC_NORMAL = 0, 1
+
+
+def smc_init_w(G, P, Cn, mode, seed, m0, probs, mean, log_var, wr):
+    """the label rows wr [G*P, Cn] of G melodies x P particles from their key prior: mode SMC_W_CATEGORICAL
+    with probs [G, Cn] fp64 (a systematic draw of P keys, one-hot rows), SMC_W_LOGISTIC_NORMAL with mean, log_var
+    [G, Cn-1] fp32; m0 = global index of melody 0 (the Philox indices follow the global melody / row)."""
+    check(_lib.lib().clv_smc_init_w(G, P, Cn, int(mode), int(seed), int(m0), _ptr(probs), _ptr(mean), _ptr(log_var), _ptr(wr),
+                                    _stream()), "clv_smc_init_w")
+
+
+def smc_w_posterior(G, P, Cn, nsteps, S, logW, wr, step_dev, out):
+    """out[m, k] = sum_p exp(logW) * wr rows of melody m at step k = *step_dev - S (out [G, nsteps, Cn] fp64); runs in the
+    frame after the gather, and does nothing on the seed steps and the bridge."""
+    check(_lib.lib().clv_smc_w_posterior(G, P, Cn, nsteps, S, _ptr(logW), _ptr(wr), _ptr(step_dev), _ptr(out), _stream()),
+          "clv_smc_w_posterior")
+
+
+def smc_take_w(G, P, Cn, n_out, picks, wr, w_out):
+    """w_out [G, n_out, Cn] = the label rows of the particles picks [G, n_out] that smc_backtrack drew"""
+    check(_lib.lib().clv_smc_take_w(G, P, Cn, n_out, _ptr(picks), _ptr(wr), _ptr(w_out), _stream()), "clv_smc_take_w")
+
+
 class Graph:
     """Capture the kernels enqueued inside the ``with`` block on the current stream; replay with launch()."""
 

@@ -28,6 +28,9 @@ IW_STREAM_W, IW_STREAM_Z = 0xFFFFFFFE, 0xFFFFFFFF
 # and, for the particle filter's resampling uniforms (engine_generate.generate_smc; step = generation step,
 # index = GLOBAL melody; drawn inside csrc/smc.hip), the stream just below them:
 SMC_STREAM = 0xFFFFFFFD
+# and, for the keys of the particles when the filter infers the key (step 0: the categorical allocation's
+# uniform, index = GLOBAL melody; step 1: the logistic-normal eps, index = GLOBAL row * (C-1) + class), the one below that:
+SMC_W_STREAM = 0xFFFFFFFC
 
 
 class DevWindows:

@@ -836,7 +836,19 @@ int clv_iw_finish(int R, int nvalid, int K, const double* state, double* log_p, 
  *   device pointers, captured by value) of every melody with flag set, through scratch (sum_i widths[i] * R floats).
  * clv_smc_backtrack: n_out draws per melody from the final weights logW by systematic resampling (u0 from step `step`,
  *   index m0 + m); draw o walks anc back from nsteps-1 and writes its frames to Xs [G, n_out, nsteps, D] (fp32 0 / 1);
- *   picks [G, n_out] (optional) receives the drawn particle.  No atomics anywhere: bitwise reproducible. */
+ *   picks [G, n_out] (optional) receives the drawn particle.  No atomics anywhere: bitwise reproducible.
+ * A label row per particle (wr [R, C] fp32, 2 <= C <= 32, one more buffer of clv_smc_gather):
+ * clv_smc_init_w: one workgroup per melody draws the P rows of melody m < G from its prior, once per chunk.  mode 0,
+ *   categorical: probs [G, C] fp64 (rows >= 0 summing to 1); with cum the inclusive sums of probs[m] in class order and
+ *   u0 = Philox uniform (stream 0xFFFFFFFC, step 0, index m0 + m), particle p takes the first class c with
+ *   P * cum_c > u0 + p (the last class if none) and its row is that one-hot.  mode 1, logistic-normal: mean, log_var
+ *   [G, C-1] fp32; s_c = mean + exp(log_var / 2) * eps with eps = Philox normal (same stream, step 1, index
+ *   ((m0 + m) * P + p) * (C-1) + c), row = softmax([s, 0]) in float32, shifted by its max.  The unused prior pointers may
+ *   be NULL.
+ * clv_smc_w_posterior: in the frame after clv_smc_gather, step k = *step_dev - S (nothing outside 0 <= k < nsteps):
+ *   out[m, k, c] = sum_p exp(logW[m*P + p]) * wr[m*P + p, c] in fp64, out [G, nsteps, C]; one workgroup per melody, a wave
+ *   per class, fixed summation order.
+ * clv_smc_take_w: w_out[m, o, :] = wr[m*P + picks[m, o], :] (picks [G, n_out] of clv_smc_backtrack), w_out [G, n_out, C]. */
 int clv_smc_sample(int R, int D, int P, int nsteps, int S, const float* p, const float* u, const uint8_t* clamp,
                    const int32_t* step_dev, float* x, double* ell, uint8_t* hist, void* stream);
 int clv_smc_resample(int G, int P, int nsteps, int S, uint64_t seed, int64_t m0, double tau, const double* ell, double* logW,
@@ -846,6 +858,11 @@ int clv_smc_gather(int R, int P, int nsteps, int S, int nbuf, float* const* bufs
                    const int32_t* anc, const int32_t* flag, const int32_t* step_dev, void* stream);
 int clv_smc_backtrack(int G, int P, int nsteps, int D, int n_out, uint64_t seed, int64_t m0, int step, const double* logW,
                       const int32_t* anc, const uint8_t* hist, float* Xs, int32_t* picks, void* stream);
+int clv_smc_init_w(int G, int P, int C, int mode, uint64_t seed, int64_t m0, const double* probs, const float* mean,
+                   const float* log_var, float* wr, void* stream);
+int clv_smc_w_posterior(int G, int P, int C, int nsteps, int S, const double* logW, const float* wr, const int32_t* step_dev,
+                        double* out, void* stream);
+int clv_smc_take_w(int G, int P, int C, int n_out, const int32_t* picks, const float* wr, float* w_out, void* stream);
 
 /* ----------------------------------------------------------------- graphs --
  * thin wrappers so a host without HIP bindings can capture a step once and

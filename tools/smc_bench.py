@@ -1,8 +1,10 @@
 """Particle-filter sampling throughput at the cl_vrnn default shape: G melodies x P particles x nsteps
 frames through VrnnEngine.generate_smc, against the clamped frame chain (generate(persistent=False, clamp=...)) on the same
 G * P rows, which runs the same frame launches without the filter.  Runs alternate; medians are printed as one JSON line.
+--infer_key adds the filter with a label per particle on the same rows, in the same alternation: a uniform
+categorical prior over the keys and / or the model's own logistic-normal prior, each against the fixed-label filter.
 
-    python tools/smc_bench.py [--melodies 64] [--particles 128] [--nsteps 64] [--reps 5]
+    python tools/smc_bench.py [--melodies 64] [--particles 128] [--nsteps 64] [--reps 5] [--infer_key both]
 """
 import argparse
 import json
@@ -16,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.engine import VrnnEngine  # noqa: E402
+from clvae_amd.engine_generate import WPrior  # noqa: E402
 from clvae_amd.harmonize import FREE  # noqa: E402
 from clvae_amd.initializers import init_weights  # noqa: E402
 
@@ -26,6 +29,7 @@ ap.add_argument('--nsteps', type=int, default=64)
 ap.add_argument('--seed_frames', type=int, default=1)
 ap.add_argument('--tau', type=float, default=0.5)
 ap.add_argument('--reps', type=int, default=5)
+ap.add_argument('--infer_key', choices=('categorical', 'logistic_normal', 'both'), default=None)
 args = ap.parse_args()
 dev = torch.device('cuda:0')
 G, P, T, S = args.melodies, args.particles, args.nsteps, args.seed_frames
@@ -49,31 +53,52 @@ clamp_rows = clamp.repeat_interleave(P, 0)
 seeds_rows, wv_rows = seeds.repeat_interleave(P, 0), wv.repeat_interleave(P, 0)
 
 
-def smc():
-    return eng.generate_smc(seeds, wv, T, clamp, P, resample_threshold=args.tau, seed=2)
+priors = {'categorical': WPrior.uniform(G, 10),
+          'logistic_normal': WPrior.logistic_normal(np.zeros((G, 9)), np.full((G, 9), cfg['w_log_var_prior']))}
+key_modes = [] if args.infer_key is None else list(priors) if args.infer_key == 'both' else [args.infer_key]
+
+
+def smc(prior=None):
+    if prior is None:
+        return eng.generate_smc(seeds, wv, T, clamp, P, resample_threshold=args.tau, seed=2)
+    return eng.generate_smc(seeds, None, T, clamp, P, resample_threshold=args.tau, seed=2, w_prior=priors[prior])
 
 
 def chain():
     return eng.generate(seeds_rows, wv_rows, T, seed=2, persistent=False, clamp=clamp_rows)
 
 
-smc(); chain(); torch.cuda.synchronize()
-t = {'smc': [], 'chain': []}
+names = ['smc', 'chain'] + key_modes
+run = {'smc': smc, 'chain': chain, 'categorical': lambda: smc('categorical'), 'logistic_normal': lambda: smc('logistic_normal')}
+for name in names:
+    run[name]()
+torch.cuda.synchronize()
+t, last = {name: [] for name in names}, {}
 for rep in range(args.reps):
-    for name in (('smc', 'chain') if rep % 2 == 0 else ('chain', 'smc')):
+    for name in (names if rep % 2 == 0 else names[::-1]):
         t0 = time.perf_counter()
-        out = smc() if name == 'smc' else chain()
-        if name == 'smc':
-            r = out
+        last[name] = run[name]()
         torch.cuda.synchronize()
         t[name].append(time.perf_counter() - t0)
 med = {k: float(np.median(v)) for k, v in t.items()}
 frames = S + T
-print(json.dumps({
+r = last['smc']
+res = {
     'tool': 'smc_bench', 'melodies': G, 'particles': P, 'nsteps': T, 'seed_frames': S, 'tau': args.tau, 'reps': args.reps,
     'smc_s': med['smc'], 'chain_s': med['chain'],
     'smc_us_per_frame': 1e6 * med['smc'] / frames, 'chain_us_per_frame': 1e6 * med['chain'] / frames,
     'smc_overhead_pct': 100 * (med['smc'] / med['chain'] - 1),
     'particle_frames_per_s': G * P * T / med['smc'],
     'resamples_per_melody': float(r.resamples.float().mean()), 'mean_log_evidence_per_frame': float(r.log_evidence.mean()) / T,
-}))
+}
+for mode in key_modes:
+    k = last[mode]
+    res['key_' + mode] = {
+        's': med[mode], 'us_per_frame': 1e6 * med[mode] / frames, 'over_fixed_w_smc_pct': 100 * (med[mode] / med['smc'] - 1),
+        'all_s': t[mode], 'resamples_per_melody': float(k.resamples.float().mean()),
+        'mean_log_evidence_per_frame': float(k.log_evidence.mean()) / T,
+        'mean_max_key_posterior': float(k.w_posterior[:, -1].max(dim=1).values.mean()),
+    }
+if key_modes:
+    res['smc_all_s'] = t['smc']
+print(json.dumps(res))
