@@ -17,7 +17,7 @@ import torch
 
 from .. import ops, sampling
 from ..engine import VaeEngine
-from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy
+from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy, temper_args
 from ..initializers import init_weights
 from ..keras_like import Layer, Model, get_value
 
@@ -59,7 +59,8 @@ def generate_sample(dec_model, w_enc_model, z_enc_model, x_seed, nsteps, w_val=N
 
 
 def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_prior=False, clamp=None, particles=None,
-                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False):
+                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False,
+                            temperature=1.0, z_temperature=1.0):
     """N sequences at once with the frame loop on the device (VaeEngine.generate: one captured hipGraph replayed per
     frame, Philox noise instead of np.random: same distribution, different draws).  x_seeds [N,D], w_vals [N,C];
     returns [N,nsteps,D] float64 like generate_sample does per sequence.  clamp: numpy / torch uint8 [N,nsteps,D]
@@ -67,7 +68,12 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_p
     particles=P: particle-filter sampling given every constraint (VaeEngine.generate_smc; resampling below an
     ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64.
     w_prior (an engine_generate.WPrior, with particles and instead of w_vals): a w per particle drawn from it, the evidence
-    then log p(constraints | seed); return_key: also the key posterior [N,nsteps,C] and each path's w [N,C]."""
+    then log p(constraints | seed); return_key: also the key posterior [N,nsteps,C] and each path's w [N,C].
+    temperature (> 0) divides every note's logit before the sigmoid, z_temperature (>= 0) scales the latent noise (0: z is
+    its mean): every route then samples the TEMPERED model with the same Philox draws, and the evidence is
+    the tempered model's, log p_T(constraints | ...), not the trained model's unless both are 1 (the default)."""
+    temper = dict(temperature=temperature, z_temperature=z_temperature)
+    temper_args(**temper)
     e = model.engine
     t = lambda a: torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32), device=e.device)
     xs = t(x_seeds)
@@ -78,11 +84,11 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_p
     if particles is not None:
         smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, e.cfg['D'], e.device)
         return smc_samples_numpy(e, xs, None if w_vals is None else t(w_vals), nsteps, seed, use_z_prior, clamp, particles,
-                                 resample_threshold, return_evidence, w_prior=w_prior, return_key=return_key)
+                                 resample_threshold, return_evidence, w_prior=w_prior, return_key=return_key, **temper)
     if return_evidence:
         raise ValueError("return_evidence needs particles")
     clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), e.cfg['D'], e.device)
-    return e.generate(xs, t(w_vals), int(nsteps), seed=int(seed), z_prior=use_z_prior, clamp=clamp).cpu().numpy() \
+    return e.generate(xs, t(w_vals), int(nsteps), seed=int(seed), z_prior=use_z_prior, clamp=clamp, **temper).cpu().numpy() \
         .astype(np.float64)
 
 

@@ -8,7 +8,7 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
-from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, parser_for  # noqa: E402
+from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, TEMPERATURE_FLAGS, parser_for, temperature_kwargs  # noqa: E402
 from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
@@ -50,7 +50,8 @@ class Sampler:
         if self.args.infer_w:
             ws = [M.sample_w(self.w_enc.predict(s[None, :]), add_noise=False) for s in seeds]
         rolls = M.generate_samples_device(self.model, np.stack(seeds), self.args.t, np.vstack(ws),
-                                          seed=getattr(self.args, 'seed', 0), use_z_prior=self.args.use_z_prior)
+                                          seed=getattr(self.args, 'seed', 0), use_z_prior=self.args.use_z_prior,
+                                          **temperature_kwargs(self.args))
         for roll, name in zip(rolls, names):
             write_sample(roll, self.args.sample_dir, name, True)
         return list(rolls)
@@ -72,7 +73,8 @@ class Sampler:
             ws = [to_categorical(self.data.test_song_keys[i], self.margs['n_classes']) for i in picks]
         out = harmonize(self.model, seeds, sources, None if ws is None else np.vstack(ws), voice=voice_of(self.args),
                         seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior, particles=particles,
-                        return_evidence=particles is not None, **(dict(infer_key=infer_key) if infer_key else {}))
+                        return_evidence=particles is not None, **(dict(infer_key=infer_key) if infer_key else {}),
+                        **temperature_kwargs(self.args))
         rolls = out[0] if particles is not None else out
         if particles is not None:
             print_evidence(names, out[1], self.args.t)
@@ -102,8 +104,9 @@ def voice_of(args):
 def on_device(args):
     """Where the frame loop runs: like the reference (host loop, np.random) for every -n unless --device_loop asks for
     the device-side loop (Philox noise: other samples for the same np.random.seed, so it is opt-in); --harmonize
-    always runs there."""
-    return bool(voice_of(args)) or (bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
+    always runs there, and so does a sampling temperature (the parser refuses one next to --host_loop)."""
+    return bool(voice_of(args)) or bool(temperature_kwargs(args)) or (
+        bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
 
 
 def sample(args):
@@ -119,4 +122,4 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    sample(parser_for('cl_vae.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS).parse_args())
+    sample(parser_for('cl_vae.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS).parse_args())

@@ -17,7 +17,7 @@ import torch
 
 from .. import sampling
 from ..engine import VrnnEngine, vrnn_param_shapes
-from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy
+from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy, temper_args
 from ..initializers import glorot_uniform, init_weights, orthogonal
 from ..keras_like import Layer, Model, get_value
 from ..utils.pianoroll import Windows
@@ -236,7 +236,8 @@ class Encoder:
 
 
 def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
-                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False):
+                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False,
+                            temperature=1.0, z_temperature=1.0):
     """Batched, device-resident counterpart of generate_sample: N seeds at once, the whole frame loop as
     replays of one captured hipGraph, Philox noise instead of np.random (so the draws differ from the numpy
     path, the distribution does not).  x_seeds [N,S,88] (S >= 0 teacher-forced frames), w_vals [N,C].
@@ -246,7 +247,12 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     particles=P: particle-filter sampling given every constraint (VrnnEngine.generate_smc; resampling below
     an ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64.
     w_prior (an engine_generate.WPrior, with particles and instead of w_vals): a w per particle drawn from it, the evidence
-    then log p(constraints | seed); return_key: also the key posterior [N,nsteps,C] and each path's w [N,C]."""
+    then log p(constraints | seed); return_key: also the key posterior [N,nsteps,C] and each path's w [N,C].
+    temperature (> 0) divides every note's logit before the sigmoid, z_temperature (>= 0) scales the latent noise (0: z is
+    its mean): every route then samples the TEMPERED model with the same Philox draws, and the evidence is
+    the tempered model's, log p_T(constraints | ...), not the trained model's unless both are 1 (the default)."""
+    temper = dict(temperature=temperature, z_temperature=z_temperature)
+    temper_args(**temper)
     e = model.engine
     xs = torch.as_tensor(np.ascontiguousarray(np.asarray(x_seeds), dtype=np.float32), device=e.device)
     if (w_vals is None) == (w_prior is None):
@@ -258,11 +264,12 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     if particles is not None:
         smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, e.cfg['D'], e.device)
         return smc_samples_numpy(e, xs, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
-                                 w_prior=w_prior, return_key=return_key)
+                                 w_prior=w_prior, return_key=return_key, **temper)
     if return_evidence:
         raise ValueError("return_evidence needs particles")
     clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), e.cfg['D'], e.device)
-    return e.generate(xs, w, int(nsteps), seed=int(seed), z_prior=z_prior, clamp=clamp).cpu().numpy().astype(np.float64)
+    return e.generate(xs, w, int(nsteps), seed=int(seed), z_prior=z_prior, clamp=clamp,
+                      **temper).cpu().numpy().astype(np.float64)
 
 
 def make_w_encoder(model, original_dim, n_classes, seq_length=1, batch_size=1):

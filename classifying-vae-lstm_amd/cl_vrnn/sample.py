@@ -8,7 +8,7 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
-from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, parser_for  # noqa: E402
+from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, TEMPERATURE_FLAGS, parser_for, temperature_kwargs  # noqa: E402
 from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
@@ -39,7 +39,7 @@ def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None)
         if args.infer_w:
             ws = [M.infer_label(w_enc_model, P.x_test[i], margs['seq_length'], discrete=args.discrete_w) for i in picks]
         rolls = list(M.generate_samples_device(model, np.stack([P.x_test[i] for i in picks]), args.t, np.vstack(ws),
-                                               seed=getattr(args, 'seed', 0)))
+                                               seed=getattr(args, 'seed', 0), **temperature_kwargs(args)))
     else:
         rolls = [M.generate_sample(dec_model, w_enc_model, z_enc_model, P.x_test[i], args.t, margs['use_x_prev'],
                                    w_val=label_of(i), w_discrete=args.discrete_w, seq_length=margs['seq_length'])
@@ -63,13 +63,13 @@ def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice
     if infer_key:               # --infer_key: the filter weighs the keys by the voice, a key per particle
         model.engine.cfg['w_log_var_prior'] = float(margs.get('w_log_var_prior', 0.0))      # load_model rebuilds layers only
         out = harmonize(model, seeds, sources, None, voice=voice, seed=getattr(args, 'seed', 0), particles=particles,
-                        return_evidence=True, infer_key=infer_key)
+                        return_evidence=True, infer_key=infer_key, **temperature_kwargs(args))
     else:
         ws = [label_of(i) for i in picks]
         if args.infer_w:
             ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in seeds]
         out = harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0),
-                        particles=particles, return_evidence=particles is not None)
+                        particles=particles, return_evidence=particles is not None, **temperature_kwargs(args))
     rolls = list(out[0] if particles is not None else out)
     if particles is not None:
         names = ['%s_%d' % (args.run_name, j) for j in range(len(rolls))]
@@ -93,8 +93,10 @@ def sample(args):
     voice = getattr(args, 'harmonize', None)
     # --harmonize: windows of the seed's t frames and the t frames whose voice is kept
     P = PianoData(args.train_file, batch_size=1, seq_length=2 * args.t if voice else args.t, squeeze_x=False)
-    # the reference's host loop (np.random) for every -n; --device_loop opts into the device-side loop (Philox noise)
-    on_device = bool(voice) or (bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
+    # the reference's host loop (np.random) for every -n; --device_loop opts into the device-side loop (Philox noise), and
+    # a sampling temperature implies it (the parser refuses one next to --host_loop)
+    on_device = bool(voice) or bool(temperature_kwargs(args)) or (
+        bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
     return gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
 
 
@@ -103,4 +105,4 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    sample(parser_for('cl_vrnn.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS).parse_args())
+    sample(parser_for('cl_vrnn.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS).parse_args())

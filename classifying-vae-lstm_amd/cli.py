@@ -119,9 +119,25 @@ HARMONIZE_FLAGS = [
 ]
 INFER_KEY_CHOICES = ('discrete', 'continuous')
 
+# sampling temperatures (not in the reference): a value other than 1 implies --device_loop
+TEMPERATURE_FLAGS = [
+    Flag(('--temperature',), float, 1.0, "divide every note's logit by this before the sigmoid: below 1 more conservative, "
+                                         'above 1 more adventurous (1e-3 is as good as greedy); on the device loop only'),
+    Flag(('--z_temperature',), float, 1.0, 'scale the latent noise by this: 0 keeps z at its mean (at 0 under '
+                                           '--use_z_prior); on the device loop only'),
+]
+
+
+def temperature_kwargs(args):
+    """the sampling tools' --temperature / --z_temperature as keyword arguments of generate_samples_device / harmonize:
+    empty where both are 1 (also for parsers without the flags)"""
+    T, Tz = getattr(args, 'temperature', 1.0), getattr(args, 'z_temperature', 1.0)
+    return {} if T == 1.0 and Tz == 1.0 else dict(temperature=T, z_temperature=Tz)
+
 
 class _Parser(argparse.ArgumentParser):
-    """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles"""
+    """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles, a
+    temperature other than 1 not with --host_loop (the host loop is the reference's and has none)"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -133,6 +149,15 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--particles must be >= 1')
         elif getattr(ns, 'infer_key', None):
             self.error('--infer_key needs --particles')
+        temper = temperature_kwargs(ns)
+        if temper:
+            from .engine_generate import temper_args
+            try:
+                temper_args(**temper)
+            except ValueError as e:
+                self.error(str(e))
+            if getattr(ns, 'host_loop', False):
+                self.error('--temperature / --z_temperature run on the device loop: not with --host_loop')
         return ns, rest
 
 

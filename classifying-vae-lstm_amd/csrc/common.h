@@ -41,6 +41,9 @@ inline int launch_status() {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// the two factors of the tempered samplers: inv_T = 1 / temperature finite and > 0, Tz finite and >= 0
+inline bool temper_factor_ok(float v, bool zero_ok) { return (zero_ok ? v >= 0.f : v > 0.f) && v <= 3.402823466e+38f; }
+
 // measurement knobs: `static const int x = env_int("NAME", dflt);` (a function-local static is initialised once, thread-safe)
 inline int env_int(const char* name, int dflt) {
   const char* e = getenv(name);

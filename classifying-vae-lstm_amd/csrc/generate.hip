@@ -42,6 +42,7 @@ struct GenArgs {
   float* Xs;                    // [N,nsteps,88]
   float* xhat;                  // [N,S+nsteps,88] or null
   const uint8_t* clamp;         // [N,nsteps,88] (CL instances): row j constrains Xs[n,j], drawn at step S+j
+  float inv_T, Tz;              // TP instances: 1 / temperature of the notes, temperature of the latent noise
 };
 
 // slice_matvec with half the live registers: the h slice is consumed in two halves of 12 (the kernel is at its
@@ -83,7 +84,10 @@ __device__ __forceinline__ void frame_masks(const float* xbuf, int lane, float& 
 // head's outputs meet in LDS and L lanes draw z (5 barriers per frame).
 // CL = true: clamped ancestral sampling: the note drawn at step t >= S is replaced by clamp[n, t-S, u] where that byte is 0
 // or 1 (any other byte leaves the draw); the clamped frame is stored and fed back as the next input.  CL = false folds away.
-template <int GATE, bool ZW, bool CL>
+// TP = true: the tempered model: x_hat = sigmoid(fl(logit * inv_T)), z = m + exp(lv / 2) * fl(Tz * eps); both
+// factors are wave-uniform kernel arguments.  The draws themselves (keys, streams, steps, indices) are those of TP = false,
+// which folds away.
+template <int GATE, bool ZW, bool CL, bool TP>
 __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   constexpr int GN_LQ = (ZW ? GN_LWIDE : GN_LMAX) / PK;
   extern __shared__ __attribute__((aligned(16))) float Kxl[];            // encoder input kernel [88][352], then Wo [88][88]
@@ -197,6 +201,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   const bool zdraw = ZW ? (tid < L) : (lat_ok && s < 2);            // lanes that own a latent's eps
   const uint64_t zidx = (uint64_t)n * L + (ZW ? tid : lat);
   float e_cur = zdraw ? philox_normal_at(zidx, a.k0, a.k1, 0u, 0u) : 0.f;
+  if (TP) e_cur = a.Tz * e_cur;
   const uint32_t crow = CL ? ((uint32_t)n * (uint32_t)a.nsteps - (uint32_t)a.S) * (uint32_t)LH : 0u;   // clamp row of step 0
   float seed_carry = 0.f;                         // CL: the constraint byte requested one frame ago
   for (int t = 0; t < T; ++t) {
@@ -343,6 +348,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
         u_cur = cb == 0u ? 2.f : (cb == 1u ? -1.f : u_cur);
       }
       if (zdraw) e_cur = philox_normal_at(zidx, a.k0, a.k1, 0u, (uint32_t)(t + 1));
+      if (TP) e_cur = a.Tz * e_cur;
     }
     step_barrier();
     // ---- phase 4: output head, Bernoulli sample, next input frame (enc waves) ------------------------------------
@@ -362,7 +368,9 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
       float acc = acc0 + acc1;
       acc = reduce_slices<PK>(acc);
       if (writer) {
-        const float p = sigmoidf_(acc + (CL ? bo_l[u] : bor));
+        float lg = acc + (CL ? bo_l[u] : bor);
+        if (TP) lg = lg * a.inv_T;
+        const float p = sigmoidf_(lg);
         const float xs = u_cur <= p ? 1.f : 0.f;
         if (a.xhat) a.xhat[((size_t)n * T + t) * LH + u] = p;
         if (t >= a.S) a.Xs[((size_t)n * a.nsteps + (t - a.S)) * LH + u] = xs;
@@ -381,11 +389,18 @@ extern "C" int clv_vrnn_generate_supported(int D, int H, int L, int C) {
 }
 
 namespace {
+template <bool CL, bool TP>
+void (*pick_vrnn_generate(bool hard, bool wide))(clv::GenArgs) {
+  using namespace clv;
+  return hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, CL, TP> : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, CL, TP>)
+              : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, CL, TP> : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, CL, TP>);
+}
+
 int vrnn_generate_launch(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior, uint64_t seed,
                          const float* x_seed, const float* w, const float* Kx_enc, const float* Kw_enc, const float* b_enc,
                          const float* U_enc, const float* Wz, const float* bz, const float* Kx_dec, const float* Kz,
                          const float* Kw_dec, const float* b_dec, const float* U_dec, const float* Wo, const float* bo,
-                         const uint8_t* clamp, float* Xs, float* xhat, void* stream) {
+                         const uint8_t* clamp, bool tempered, float inv_T, float Tz, float* Xs, float* xhat, void* stream) {
   using namespace clv;
   if (!clv_vrnn_generate_supported(D, H, L, C) || N <= 0 || S < 0 || nsteps < 0 || S + nsteps <= 0) return CLV_EINVAL;
   if (gate_act != CLV_GATE_HARD_SIGMOID && gate_act != CLV_GATE_SIGMOID) return CLV_EINVAL;
@@ -396,18 +411,17 @@ int vrnn_generate_launch(int N, int S, int nsteps, int D, int H, int L, int C, i
   if (clamp && (uint64_t)N * nsteps * LH > UINT32_MAX) return CLV_EINVAL;      // the kernel addresses the roll in 32 bits
   hipStream_t s = (hipStream_t)stream;
   GenArgs a{N, S, nsteps, L, C, z_prior, Kx_dec != nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), x_seed, w,
-            Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp};
+            Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp, inv_T, Tz};
   const size_t lds = (size_t)(LH * LG + LH * LH) * sizeof(float);
   const bool hard = gate_act == CLV_GATE_HARD_SIGMOID, wide = L > GN_LMAX;
   void (*kern)(GenArgs);
-  if (clamp)
-    kern = hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true> : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true>)
-                : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true> : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true>);
+  if (tempered)
+    kern = clamp ? pick_vrnn_generate<true, true>(hard, wide) : pick_vrnn_generate<false, true>(hard, wide);
   else
-    kern = hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, false> : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, false>)
-                : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, false> : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, false>);
+    kern = clamp ? pick_vrnn_generate<true, false>(hard, wide) : pick_vrnn_generate<false, false>(hard, wide);
   if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 156 * 1024)) return e;
-  ProfScope p(clamp ? "vrnn_generate_clamped" : "vrnn_generate", s);
+  ProfScope p(tempered ? (clamp ? "vrnn_generate_tempered_clamped" : "vrnn_generate_tempered")
+                       : (clamp ? "vrnn_generate_clamped" : "vrnn_generate"), s);
   hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
   return launch_status();
 }
@@ -421,7 +435,7 @@ extern "C" int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, 
                                  const float* U_dec, const float* Wo, const float* bo,
                                  float* Xs, float* xhat, void* stream) {
   return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
-                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, nullptr, Xs, xhat, stream);
+                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, nullptr, false, 1.f, 1.f, Xs, xhat, stream);
 }
 
 extern "C" int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
@@ -433,5 +447,19 @@ extern "C" int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H,
                                          float* Xs, float* xhat, void* stream) {
   if (!clamp || nsteps <= 0) return CLV_EINVAL;
   return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
-                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, Xs, xhat, stream);
+                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, false, 1.f, 1.f, Xs, xhat, stream);
+}
+
+extern "C" int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
+                                          uint64_t seed, const float* x_seed, const float* w,
+                                          const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                                          const float* Wz, const float* bz,
+                                          const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                                          const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                                          float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream) {
+  if (!clv::temper_factor_ok(inv_temperature, false) || !clv::temper_factor_ok(z_temperature, true)) return CLV_EINVAL;
+  if (clamp && nsteps <= 0) return CLV_EINVAL;
+  return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
+                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, true, inv_temperature, z_temperature, Xs,
+                              xhat, stream);
 }

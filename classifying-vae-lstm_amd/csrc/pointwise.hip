@@ -272,6 +272,16 @@ __global__ void axpy_kernel(int64_t n, float alpha, const float* x, float* y) {
   if (i < n) y[i] += alpha * x[i];
 }
 
+// the tempered samplers' frame chains, in place: x = fl(alpha * x), then the output head's own sigmoid where
+// SIG (the GEMM ran without its activation).  One rounding of the product: what the persistent kernels' TP instances do
+template <bool SIG>
+__global__ __launch_bounds__(256) void temper_kernel(int64_t n, float alpha, float* x) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float v = alpha * x[i];
+  x[i] = SIG ? sigmoidf_(v) : v;
+}
+
 // dpre = dy * act'(.) written in terms of the activation's OUTPUT y: relu -> [y > 0], sigmoid -> y (1 - y)
 __global__ void act_grad_kernel(int64_t n, int act, const float* y, const float* dy, float* dpre) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -600,6 +610,22 @@ extern "C" int clv_axpy(int64_t n, float alpha, const float* x, float* y, void* 
   hipStream_t s = (hipStream_t)stream;
   ProfScope pr("axpy", s);
   hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, alpha, x, y);
+  return launch_status();
+}
+
+extern "C" int clv_sigmoid_temper(int64_t n, float* a, float inv_temperature, void* stream) {
+  if (n <= 0 || !a || !clv::temper_factor_ok(inv_temperature, false)) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("sigmoid_temper", s);
+  hipLaunchKernelGGL(temper_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, inv_temperature, a);
+  return launch_status();
+}
+
+extern "C" int clv_scale_temper(int64_t n, float* eps, float z_temperature, void* stream) {
+  if (n <= 0 || !eps || !clv::temper_factor_ok(z_temperature, true)) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("scale_temper", s);
+  hipLaunchKernelGGL(temper_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, z_temperature, eps);
   return launch_status();
 }
 

@@ -37,6 +37,7 @@ struct VaeGenArgs {
   float* Xs;                    // [N,nsteps,88]
   float* xhat;                  // [N,nsteps,88] or null
   const uint8_t* clamp;         // [N,nsteps,88] (CL instance): row t constrains frame t
+  float inv_T, Tz;              // TP instances: 1 / temperature of the notes, temperature of the latent noise
 };
 
 // sum over the notes that are on (two scalar masks: inputs 0..63 / 64..87) of row n of an LDS-resident [88][88] kernel,
@@ -61,7 +62,9 @@ __device__ __forceinline__ float gather_rows(const float* Kl, int j, unsigned lo
 
 // CL = true: clamped ancestral sampling: the note drawn at frame t is replaced by clamp[n, t, o] where that byte is 0 or 1
 // (any other byte leaves the draw); the clamped frame is stored and is the next input.  CL = false folds away.
-template <bool CL>
+// TP = true: the tempered model: x_hat = sigmoid(fl(logit * inv_T)), z = mean + exp(lv / 2) * fl(Tz * eps), both
+// factors wave-uniform kernel arguments; same draws as TP = false, which folds away.
+template <bool CL, bool TP>
 __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   extern __shared__ __attribute__((aligned(16))) float vg_lds[];
   float* Khl = vg_lds;                        // [88][88] frame rows of the z-encoder's hidden kernel
@@ -120,7 +123,8 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
     // this frame's constraint, requested three barriers before phase 4 uses it (2: free)
     const uint32_t cb = (CL && writer) ? (uint32_t)a.clamp[((size_t)n * a.nsteps + t) * LH + o] : 2u;
     const bool zdraw = s == 0 && zslot && !(o_raw & 1);                 // the mean slot of latent l = o_raw / 2
-    const float eps = zdraw ? philox_normal_at((uint64_t)n * L + (o_raw >> 1), a.k0, a.k1, 0u, (uint32_t)t) : 0.f;
+    float eps = zdraw ? philox_normal_at((uint64_t)n * L + (o_raw >> 1), a.k0, a.k1, 0u, (uint32_t)t) : 0.f;
+    if (TP) eps = a.Tz * eps;
     // 1. z-encoder hidden layer: relu(x_prev . K_h[frame rows] + (w . K_h[label rows] + b_h))
     {
       const float h = fmaxf(ch + gather_rows(Khl, o, cur0, cur1), 0.f);
@@ -158,7 +162,8 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
       float acc0 = 0.f, acc1 = 0.f;
 #pragma unroll
       for (int kk = 0; kk < PKK; kk += 2) { acc0 = fmaf(hv[kk], Kor[kk], acc0); acc1 = fmaf(hv[kk + 1], Kor[kk + 1], acc1); }
-      const float lg = reduce_slices<PK>(acc0 + acc1) + bor;
+      float lg = reduce_slices<PK>(acc0 + acc1) + bor;
+      if (TP) lg = lg * a.inv_T;
       if (writer) {
         const float p = sigmoidf_(lg);
         float xs = u_cur <= p ? 1.f : 0.f;
@@ -186,18 +191,20 @@ extern "C" int clv_vae_generate_supported(int D, int H, int L, int C) {
 namespace {
 int vae_generate_launch(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
                         const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz, const float* bz,
-                        const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp, float* Xs,
-                        float* xhat, void* stream) {
+                        const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp, bool tempered,
+                        float inv_T, float Tz, float* Xs, float* xhat, void* stream) {
   using namespace clv;
   if (!clv_vae_generate_supported(D, H, L, C) || N <= 0 || nsteps <= 0) return CLV_EINVAL;
   if (!x_seed || !w || !Kh || !bh || !Kz || !bz || !Kd || !bd || !Ko || !bo || !Xs) return CLV_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   VaeGenArgs a{N, nsteps, L, C, z_prior, use_x_prev != 0, (uint32_t)seed, (uint32_t)(seed >> 32), x_seed, w, Kh, bh, Kz, bz, Kd, bd,
-               Ko, bo, Xs, xhat, clamp};
+               Ko, bo, Xs, xhat, clamp, inv_T, Tz};
   const size_t lds = (size_t)(2 * LH * LH + VG_LMAX * LH) * sizeof(float);
-  void (*kern)(VaeGenArgs) = clamp ? vae_generate_kernel<true> : vae_generate_kernel<false>;
+  void (*kern)(VaeGenArgs) = tempered ? (clamp ? vae_generate_kernel<true, true> : vae_generate_kernel<false, true>)
+                                      : (clamp ? vae_generate_kernel<true, false> : vae_generate_kernel<false, false>);
   if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 96 * 1024)) return e;
-  ProfScope p(clamp ? "vae_generate_clamped" : "vae_generate", s);
+  ProfScope p(tempered ? (clamp ? "vae_generate_tempered_clamped" : "vae_generate_tempered")
+                       : (clamp ? "vae_generate_clamped" : "vae_generate"), s);
   hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
   return launch_status();
 }
@@ -208,7 +215,7 @@ extern "C" int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, i
                                 const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
                                 float* Xs, float* xhat, void* stream) {
   return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
-                             nullptr, Xs, xhat, stream);
+                             nullptr, false, 1.f, 1.f, Xs, xhat, stream);
 }
 
 extern "C" int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
@@ -217,5 +224,15 @@ extern "C" int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, 
                                         const float* bo, const uint8_t* clamp, float* Xs, float* xhat, void* stream) {
   if (!clamp) return CLV_EINVAL;
   return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
-                             clamp, Xs, xhat, stream);
+                             clamp, false, 1.f, 1.f, Xs, xhat, stream);
+}
+
+extern "C" int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
+                                         uint64_t seed, const float* x_seed, const float* w, const float* Kh, const float* bh,
+                                         const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
+                                         const float* bo, const uint8_t* clamp, float inv_temperature, float z_temperature,
+                                         float* Xs, float* xhat, void* stream) {
+  if (!clv::temper_factor_ok(inv_temperature, false) || !clv::temper_factor_ok(z_temperature, true)) return CLV_EINVAL;
+  return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
+                             clamp, true, inv_temperature, z_temperature, Xs, xhat, stream);
 }

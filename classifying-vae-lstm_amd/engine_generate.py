@@ -125,13 +125,48 @@ def smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, device):
     return clamp_roll(clamp, N, nsteps, D, device)
 
 
+def temper_args(temperature, z_temperature):
+    """Validate the two sampling temperatures and return the tempered model's factors (inv_T, Tz) as float32
+    values, or None where both are 1 (the caller then runs exactly the untempered path).  temperature T > 0 divides a
+    note's logit: inv_T = float32(1 / T), formed in double and rounded once.  z_temperature Tz >= 0 scales the latent noise;
+    0 means z = its mean (z = 0 under the prior).  ValueError for a bool, a value that is not finite, T <= 0, a 1 / T that is
+    zero or not finite in float32, Tz < 0."""
+    vals = []
+    for name, v in (('temperature', temperature), ('z_temperature', z_temperature)):
+        if isinstance(v, (bool, np.bool_)):
+            raise ValueError("%s must be a number, got %r" % (name, v))
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number, got %r" % (name, v))
+        if not np.isfinite(v):
+            raise ValueError("%s must be finite, got %r" % (name, v))
+        vals.append(v)
+    T, Tz = vals
+    if T <= 0.0:
+        raise ValueError("temperature must be > 0, got %r" % (temperature,))
+    if Tz < 0.0:
+        raise ValueError("z_temperature must be >= 0, got %r" % (z_temperature,))
+    with np.errstate(over='ignore', under='ignore'):
+        inv_T, Tz32 = np.float32(1.0 / T), np.float32(Tz)
+    if not np.isfinite(inv_T) or inv_T == 0:
+        raise ValueError("1 / temperature must be a finite non-zero float32, got temperature %r" % (temperature,))
+    if not np.isfinite(Tz32):
+        raise ValueError("z_temperature must be a finite float32, got %r" % (z_temperature,))
+    if inv_T == 1 and Tz32 == 1:
+        return None
+    return float(inv_T), float(Tz32)
+
+
 def smc_samples_numpy(engine, x_seed, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
-                      w_prior=None, return_key=False):
+                      w_prior=None, return_key=False, temperature=1.0, z_temperature=1.0):
     """generate_samples_device(particles=P): one draw per melody, [N, nsteps, D] float64 (and log_evidence [N] float64;
     with return_key, under a w_prior, also w_posterior [N, nsteps, C] and the path's label w_out [N, C], float64)"""
     if return_key and w_prior is None:
         raise ValueError("return_key needs a w_prior")
     kw = {} if w_prior is None else dict(w_prior=w_prior)
+    if temper_args(temperature, z_temperature) is not None:
+        kw.update(temperature=temperature, z_temperature=z_temperature)
     r = engine.generate_smc(x_seed, w, int(nsteps), clamp, particles, resample_threshold, n_out=1, seed=int(seed),
                             z_prior=z_prior, **kw)
     out = [r.Xs[:, 0].cpu().numpy().astype(np.float64)]
@@ -212,17 +247,22 @@ def _smc_drive(chunks, run_chunk, N, nsteps, D, n_out, device, C=None):
 
 
 class VaeGenerate:
-    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None):
+    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None,
+                 temperature=1.0, z_temperature=1.0):
         """N independent sequences of `nsteps` frames on the device: the frame loop of cl_vae/model.py:28-41
         (z-encoder on the last frame, z ~ N(mean, exp(lv)) or N(0, 1), decoder on (w, z, frame before last),
         x ~ Bernoulli); eps and u come from the Philox streams 0 / 1 at step = frame index.  x_seed [N,D], w [N,C] device
         tensors.  persistent=True (default where the shapes allow): the whole loop is ONE kernel, a workgroup per
         sequence (csrc/vae_generate.hip; any N); otherwise the layer chain captured once as a hipGraph and replayed per
         frame (N <= batch size).  Same noise, same samples either way.  clamp: constraint roll [N,nsteps,D] (clamp_roll;
-        row t constrains frame t, which is then fed back like a sampled one: clamped ancestral sampling)."""
+        row t constrains frame t, which is then fed back like a sampled one: clamped ancestral sampling).
+        temperature, z_temperature (temper_args): sample from the tempered model, x_hat = sigmoid(logit /
+        temperature) and z = mean + exp(lv / 2) * z_temperature * eps, with the same Philox draws; xhat_out then holds the
+        tempered probabilities.  Both 1.0 (default): exactly the untempered launches."""
         cfg, d = self.cfg, self.device
         N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
         clamp = clamp_roll(clamp, N, nsteps, D, d)
+        temper = temper_args(temperature, z_temperature)
         if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
             P = self.P
             f = dict(dtype=torch.float32, device=d)
@@ -230,7 +270,8 @@ class VaeGenerate:
             ops.vae_generate(N, nsteps, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], z_prior, seed,
                              x_seed.to(**f).contiguous(), w.to(**f).contiguous(), P.p('h/kernel'), P.p('h/bias'),
                              P.p('zargs/kernel'), P.p('zargs/bias'), P.p('decoder_h/kernel'), P.p('decoder_h/bias'),
-                             P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs, xhat_out, clamp=clamp)
+                             P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs, xhat_out, clamp=clamp,
+                             temper=temper)
             return Xs
         if N > self.B:
             raise ValueError("%d sequences exceed the engine's batch size %d" % (N, self.B))
@@ -246,8 +287,10 @@ class VaeGenerate:
             ops.philox_normal(eps, N * L, seed, 0, 0, 0, step_dev=counter)
             if z_prior:
                 self.zargs[:N].zero_()
+            _temper_eps(temper, eps, N * L)
             ops.gauss_fwd(N, L, self.zargs, eps, self.z, L, None)
-            self.decode(w, self.z, hist if cfg['use_x_prev'] else None, N, act=ACT_SIGMOID)
+            self.decode(w, self.z, hist if cfg['use_x_prev'] else None, N, act=_head_act(temper))
+            _temper_head(temper, self.logits, N * D)
             ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
             if clamp is None:
                 ops.bernoulli_sample(N * D, self.logits, u, x_next)
@@ -270,7 +313,7 @@ class VaeGenerate:
         return Xs
 
     def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
-                     z_prior=False, chunk=None, w_prior=None):
+                     z_prior=False, chunk=None, w_prior=None, temperature=1.0, z_temperature=1.0):
         """Particle-filter sampling under the constraint roll clamp [N, nsteps, D]: melody m runs P =
         `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
         probability of each frame's clamped notes and resampled (systematic, below an ESS of resample_threshold * P).
@@ -278,9 +321,13 @@ class VaeGenerate:
         `chunk` melodies); the Philox keys follow the global row, so the result does not depend on the chunking.
         x_seed [N, D], w [N, C] device tensors.  Returns SmcResult (Xs [N, n_out, nsteps, D]).
         w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state, so the filter
-        targets p(w, free notes | seed, constraints); returns SmcKeyResult."""
+        targets p(w, free notes | seed, constraints); returns SmcKeyResult.
+        temperature, z_temperature (temper_args): the filter runs on the TEMPERED model; its weights are the
+        tempered probabilities of the clamped notes, so log_evidence estimates log p_T(constraints | seed, w), the evidence
+        under the tempered model -- the trained model's only where both are 1."""
         cfg, d = self.cfg, self.device
         N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
+        temper = temper_args(temperature, z_temperature)
         clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
         P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
         f = dict(dtype=torch.float32, device=d)
@@ -308,8 +355,10 @@ class VaeGenerate:
                 ops.philox_normal(eps, R * L, seed, 0, 0, r0 * L, step_dev=counter)
                 if z_prior:
                     self.zargs[:R].zero_()
+                _temper_eps(temper, eps, R * L)
                 ops.gauss_fwd(R, L, self.zargs, eps, self.z, L, None)
-                self.decode(wr, self.z, hist if cfg['use_x_prev'] else None, R, act=ACT_SIGMOID)
+                self.decode(wr, self.z, hist if cfg['use_x_prev'] else None, R, act=_head_act(temper))
+                _temper_head(temper, self.logits, R * D)
                 ops.philox_uniform(u, R * D, seed, 0, 1, r0 * D, step_dev=counter)
                 smc.step(self.logits, u, counter, x_next, gather)
                 ops.i32_add(counter, 1)
@@ -321,6 +370,23 @@ class VaeGenerate:
 
         return _smc_drive(_smc_chunks(N, P, self.B, chunk), run_chunk, N, nsteps, D, int(n_out), d,
                           C=None if prior is None else cfg['C'])
+
+
+def _head_act(temper):
+    """the output head's GEMM epilogue in a frame chain: its own sigmoid, or none where _temper_head applies it"""
+    return ACT_SIGMOID if temper is None or temper[0] == 1.0 else ACT_NONE
+
+
+def _temper_head(temper, a, n):
+    """tempered frame chain: the head's pre-activations a[:n] -> sigmoid(fl32(a * inv_T)), one launch (none at inv_T = 1)"""
+    if temper is not None and temper[0] != 1.0:
+        ops.sigmoid_temper(n, a, temper[0])
+
+
+def _temper_eps(temper, eps, n):
+    """tempered frame chain: eps[:n] -> fl32(Tz * eps) between philox_normal and gauss_fwd, one launch (none at Tz = 1)"""
+    if temper is not None and temper[1] != 1.0:
+        ops.scale_temper(n, eps, temper[1])
 
 
 def _replay(frame, nsteps, use_graph, before=None):
@@ -370,8 +436,8 @@ class VrnnGenerate:
         self._lstm_step(rec_name, st, 'h_enc', 'c_enc')
         g(st['hs'], P.p('Zargs/kernel'), st['zargs'], B, 2 * L, H, bias=P.p('Zargs/bias'), ws=ws)
 
-    def dec_step(self, z, xp, w, st):
-        """one decoder-LSTM step on [x_{t-1}, z_t, w] + sigmoid head -> st['xhat']"""
+    def dec_step(self, z, xp, w, st, act=ACT_SIGMOID):
+        """one decoder-LSTM step on [x_{t-1}, z_t, w] + sigmoid head -> st['xhat'] (act=ACT_NONE: the head's pre-activations)"""
         cfg, P, B = self.cfg, self.P, st['B']
         D, H, L, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['C']
         g, ws, off = ops.gemm, self.ws, self.off
@@ -383,27 +449,33 @@ class VrnnGenerate:
           bias=P.p('decoder_h/bias'), ws=ws)     # three tiny GEMMs: batch-1 sampling is launch-bound, not flop-bound
         self._lstm_step('decoder_h', st, 'h_dec', 'c_dec')
         g(st['hs'], P.p('X_decoded_mean/kernel'), st['xhat'], B, D, H, bias=P.p('X_decoded_mean/bias'),
-          act=ACT_SIGMOID, ws=ws)
+          act=act, ws=ws)
 
-    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None):
+    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None,
+                 temperature=1.0, z_temperature=1.0):
         """Autoregressive generation of N independent sequences on the device.  persistent=True (default where the
         shapes allow): the whole frame loop is ONE kernel, a workgroup per sequence (csrc/generate.hip); otherwise the
         per-frame chain below, captured once and replayed per frame.  Same Philox noise either way.
         xhat_out [N,S+nsteps,D] (persistent path only) receives every frame's note probabilities.
         clamp: constraint roll [N,nsteps,D] (engine_generate.clamp_roll): row j constrains the returned frame Xs[:, j],
         drawn at step S+j; the bridge sample of step S-1 stays free (clamped ancestral sampling).  The
-        persistent kernel addresses the roll in 32 bits: a roll of 2^32 bytes or more takes the frame chain."""
+        persistent kernel addresses the roll in 32 bits: a roll of 2^32 bytes or more takes the frame chain.
+        temperature, z_temperature (temper_args): sample from the tempered model, x_hat = sigmoid(logit /
+        temperature) and z = mean + exp(lv / 2) * z_temperature * eps, with the same Philox draws (runs that differ only in
+        the temperature share their uniforms); xhat_out then holds the tempered probabilities.  Both 1.0 (default):
+        exactly the untempered launches."""
         cfg = self.cfg
+        temper = temper_args(temperature, z_temperature)
         clamp = clamp_roll(clamp, int(x_seed.shape[0]), nsteps, cfg['D'], self.device)
         if clamp is not None and nsteps == 0:
             clamp = None                # nothing is returned, so nothing is constrained
         if clamp is not None and clamp.numel() >= 2 ** 32:
             persistent = False
         if persistent and ops.vrnn_generate_supported(cfg['D'], cfg['H'], cfg['L'], cfg['C']):
-            return self._generate_persistent(x_seed, w, nsteps, seed, z_prior, xhat_out, clamp)
-        return self._generate_frames(x_seed, w, nsteps, seed, use_graph, z_prior, clamp)
+            return self._generate_persistent(x_seed, w, nsteps, seed, z_prior, xhat_out, clamp, temper)
+        return self._generate_frames(x_seed, w, nsteps, seed, use_graph, z_prior, clamp, temper)
 
-    def _generate_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp=None):
+    def _generate_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp=None, temper=None):
         cfg, P, d = self.cfg, self.P, self.device
         D, H, L, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.off
         N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
@@ -414,10 +486,10 @@ class VrnnGenerate:
                           P.p('encoder_h/recurrent_kernel'), P.p('Zargs/kernel'), P.p('Zargs/bias'),
                           P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
                           rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
-                          P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out, clamp=clamp)
+                          P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out, clamp=clamp, temper=temper)
         return Xs
 
-    def _generate_frames(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, clamp=None):
+    def _generate_frames(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, clamp=None, temper=None):
         """Batched autoregressive generation on the device (the hot loop of cl_vrnn/model.py:47-59 for N
         independent sequences at once, noise from Philox instead of np.random).
         x_seed [N,S,D] device tensor (teacher-forced frames, S may be 0), w [N,C]; returns Xs [N,nsteps,D].
@@ -439,8 +511,10 @@ class VrnnGenerate:
             ops.philox_normal(eps, N * L, seed, 0, 0, 0, step_dev=counter)
             if z_prior:
                 st['zargs'].zero_()
+            _temper_eps(temper, eps, N * L)
             ops.gauss_fwd(N, L, st['zargs'], eps, z, L, None)
-            self.dec_step(z, x_prev if cfg['use_x_prev'] else None, w, st)
+            self.dec_step(z, x_prev if cfg['use_x_prev'] else None, w, st, act=_head_act(temper))
+            _temper_head(temper, st['xhat'], N * D)
             ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
             if clamp is None:
                 ops.bernoulli_sample(N * D, st['xhat'], u, x_next)
@@ -467,7 +541,7 @@ class VrnnGenerate:
         return Xs
 
     def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
-                     z_prior=False, chunk=None, w_prior=None):
+                     z_prior=False, chunk=None, w_prior=None, temperature=1.0, z_temperature=1.0):
         """Particle-filter sampling under the constraint roll clamp [N, nsteps, D]: melody m runs P =
         `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
         probability of each returned frame's clamped notes and resampled (systematic, below an ESS of
@@ -476,10 +550,14 @@ class VrnnGenerate:
         so the result does not depend on it).  x_seed [N, S, D], w [N, C] device tensors.  Returns SmcResult.
         w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state (the seed steps
         run under it too, unweighted), so the filter targets p(w, free notes | seed, constraints); returns
-        SmcKeyResult."""
+        SmcKeyResult.
+        temperature, z_temperature (temper_args): the filter runs on the TEMPERED model; its weights are the
+        tempered probabilities of the clamped notes, so log_evidence estimates log p_T(constraints | seed, w), the evidence
+        under the tempered model -- the trained model's only where both are 1."""
         cfg, d = self.cfg, self.device
         N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
         D, L = cfg['D'], cfg['L']
+        temper = temper_args(temperature, z_temperature)
         clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
         P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
         f = dict(dtype=torch.float32, device=d)
@@ -508,8 +586,10 @@ class VrnnGenerate:
                 ops.philox_normal(eps, R * L, seed, 0, 0, r0 * L, step_dev=counter)
                 if z_prior:
                     st['zargs'].zero_()
+                _temper_eps(temper, eps, R * L)
                 ops.gauss_fwd(R, L, st['zargs'], eps, z, L, None)
-                self.dec_step(z, x_prev if cfg['use_x_prev'] else None, wr, st)
+                self.dec_step(z, x_prev if cfg['use_x_prev'] else None, wr, st, act=_head_act(temper))
+                _temper_head(temper, st['xhat'], R * D)
                 ops.philox_uniform(u, R * D, seed, 0, 1, r0 * D, step_dev=counter)
                 smc.step(st['xhat'], u, counter, x_next, gather)
                 ops.i32_add(counter, 1)

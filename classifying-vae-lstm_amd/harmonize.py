@@ -53,7 +53,7 @@ def default_w_prior(model, N, infer_key):
 
 
 def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fence=True, z_prior=False, particles=None,
-              resample_threshold=0.5, return_evidence=False, infer_key=None, w_prior=None):
+              resample_threshold=0.5, return_evidence=False, infer_key=None, w_prior=None, temperature=1.0, z_temperature=1.0):
     """Generate len(seeds) sequences that keep the `voice` of source_rolls [N, nsteps, 88] and fill in the rest, with the
     frame loop on the device.  seeds: cl_vrnn [N, S, 88] teacher-forced frames (the first source frame follows them),
     cl_vae [N, 88] (frame 0 of the sequence; the first source frame is frame 1).  Returns [N, nsteps, 88] float64.
@@ -62,7 +62,10 @@ def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fenc
     infer_key='discrete' | 'continuous' (with particles, instead of w_vals): every particle draws its own w from a prior
     over the key (default_w_prior, or the WPrior given as w_prior) and the filter weighs the keys by the voice
     (DESIGN.md 12).  The evidence is then log p(voice | seed), and the call also returns, after it, the key posterior
-    w_posterior [N, nsteps, C] (after each frame) and the label w_out [N, C] of each returned sequence, float64."""
+    w_posterior [N, nsteps, C] (after each frame) and the label w_out [N, C] of each returned sequence, float64.
+    temperature, z_temperature: harmonize with the tempered model (note logits divided by temperature, latent
+    noise scaled by z_temperature); evidence and key posterior are then that tempered model's, not the trained model's
+    unless both are 1."""
     from .engine import VaeEngine
     source_rolls = np.asarray(source_rolls)
     if source_rolls.ndim != 3:
@@ -83,6 +86,7 @@ def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fenc
         raise ValueError("harmonize needs w_vals (or infer_key with particles)")
     clamp = voice_constraints(source_rolls, voice, fence)
     nsteps = source_rolls.shape[1]
+    extra.update(temperature=temperature, z_temperature=z_temperature)
     if isinstance(model.engine, VaeEngine):
         from .cl_vae.model import generate_samples_device
         return generate_samples_device(model, seeds, nsteps, w_vals, seed=seed, use_z_prior=z_prior, clamp=clamp,

@@ -356,13 +356,17 @@ def vrnn_generate_supported(D, H, L, Cn):
 
 
 def vrnn_generate(N, S, nsteps, D, H, L, Cn, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
-                  Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None):
+                  Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None, temper=None):
     """cl_vrnn frame loop for N sequences in one persistent launch (csrc/generate.hip); clamp: uint8 [N,nsteps,D]
-    constraint roll (clv_vrnn_generate_clamped) or None."""
+    constraint roll (clv_vrnn_generate_clamped) or None; temper: None or (inv_temperature, z_temperature), the tempered
+    model's two factors (clv_vrnn_generate_tempered, with or without a roll)."""
     args = [N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed), _ptr(x_seed), _ptr(w), _ptr(Kx_enc),
             _ptr(Kw_enc), _ptr(b_enc), _ptr(U_enc), _ptr(Wz), _ptr(bz), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec),
             _ptr(U_dec), _ptr(Wo), _ptr(bo)]
-    if clamp is None:
+    if temper is not None:
+        check(_lib.lib().clv_vrnn_generate_tempered(*args, _ptr(clamp), float(temper[0]), float(temper[1]), _ptr(Xs), _ptr(xhat),
+                                                    _stream()), "clv_vrnn_generate_tempered")
+    elif clamp is None:
         check(_lib.lib().clv_vrnn_generate(*args, _ptr(Xs), _ptr(xhat), _stream()), "clv_vrnn_generate")
     else:
         check(_lib.lib().clv_vrnn_generate_clamped(*args, _ptr(clamp), _ptr(Xs), _ptr(xhat), _stream()),
@@ -374,12 +378,16 @@ def vae_generate_supported(D, H, L, Cn):
 
 
 def vae_generate(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs, xhat=None,
-                 clamp=None):
+                 clamp=None, temper=None):
     """cl_vae frame loop for N sequences in one persistent launch (csrc/vae_generate.hip); clamp: uint8 [N,nsteps,D]
-    constraint roll (clv_vae_generate_clamped) or None."""
+    constraint roll (clv_vae_generate_clamped) or None; temper: None or (inv_temperature, z_temperature)
+    (clv_vae_generate_tempered, with or without a roll)."""
     args = [N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed), _ptr(x_seed), _ptr(w), _ptr(Kh),
             _ptr(bh), _ptr(Kz), _ptr(bz), _ptr(Kd), _ptr(bd), _ptr(Ko), _ptr(bo)]
-    if clamp is None:
+    if temper is not None:
+        check(_lib.lib().clv_vae_generate_tempered(*args, _ptr(clamp), float(temper[0]), float(temper[1]), _ptr(Xs), _ptr(xhat),
+                                                   _stream()), "clv_vae_generate_tempered")
+    elif clamp is None:
         check(_lib.lib().clv_vae_generate(*args, _ptr(Xs), _ptr(xhat), _stream()), "clv_vae_generate")
     else:
         check(_lib.lib().clv_vae_generate_clamped(*args, _ptr(clamp), _ptr(Xs), _ptr(xhat), _stream()),
@@ -688,6 +696,16 @@ def dropout_rows(R, T, n, X, ldx, U, ldu, rate, out, ldo, beta=0.0):
     """out[r, :n] = beta * out + X[r, :n] * mask(U[r // T, :n]), mask(u) = (u >= rate) / (1 - rate) (clv_dropout_rows)."""
     check(_lib.lib().clv_dropout_rows(R, T, n, _ptr(X), ldx, _ptr(U), ldu, float(rate), float(beta), _ptr(out), ldo, _stream()),
           "clv_dropout_rows")
+
+
+def sigmoid_temper(n, a, inv_temperature):
+    """a[:n] = sigmoid(fl32(a * inv_temperature)) in place: the output head of a tempered frame chain (clv_sigmoid_temper)"""
+    check(_lib.lib().clv_sigmoid_temper(n, _ptr(a), float(inv_temperature), _stream()), "clv_sigmoid_temper")
+
+
+def scale_temper(n, eps, z_temperature):
+    """eps[:n] = fl32(z_temperature * eps) in place: the latent noise of a tempered frame chain (clv_scale_temper)"""
+    check(_lib.lib().clv_scale_temper(n, _ptr(eps), float(z_temperature), _stream()), "clv_scale_temper")
 
 
 def bernoulli_sample(n, p, u, x):

@@ -443,6 +443,32 @@ int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, int C, int 
                              const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
                              const uint8_t* clamp, float* Xs, float* xhat, void* stream);
 
+/* ----------------------------------------------- generation at a temperature --
+ * The TEMPERED MODEL: inv_temperature = float32(1 / T), T > 0, multiplies a note's logit (product plus bias,
+ * rounded once) before the same sigmoid; z_temperature = Tz >= 0 multiplies the latent noise, z = mean + exp(log_var/2) *
+ * fl(Tz * eps) (Tz = 0: z = mean, or 0 under z_prior).  Everything else is clv_vrnn_generate / clv_vae_generate and their
+ * _clamped forms: the same Philox keys, streams, steps and indices (runs that differ only in T share their uniforms), the
+ * same bridge rule; xhat receives the TEMPERED probabilities.  clamp may be NULL (no constraint).  Both factors at 1.0f
+ * give bit for bit the frames of the untempered entry points.  CLV_EINVAL for an inv_temperature that is zero, negative or
+ * not finite and a z_temperature that is negative or not finite. */
+int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
+                               uint64_t seed, const float* x_seed, const float* w,
+                               const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                               const float* Wz, const float* bz,
+                               const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                               const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                               float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream);
+int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
+                              const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
+                              const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
+                              const uint8_t* clamp, float inv_temperature, float z_temperature, float* Xs, float* xhat,
+                              void* stream);
+/* The same two factors for the per-frame chains, in place and with one rounding of the product, as the kernels above form
+ * them: a[i] = sigmoid(fl(a[i] * inv_temperature)) on the output head's pre-activations (the head GEMM then runs with
+ * CLV_ACT_NONE), eps[i] = fl(z_temperature * eps[i]) on the latent noise between clv_philox_normal and clv_gauss_fwd. */
+int clv_sigmoid_temper(int64_t n, float* a, float inv_temperature, void* stream);
+int clv_scale_temper(int64_t n, float* eps, float z_temperature, void* stream);
+
 /* ------------------------------------------------------------ pointwise --
  * logistic-normal label sample + its two losses, one thread per row:
  *   w = softmax([mean + exp(lv/2)*eps, 0]); kl_w, w_rec = (C-1)*CCE(onehot, w+1e-10), hit
