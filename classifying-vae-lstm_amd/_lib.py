@@ -125,6 +125,9 @@ SIGNATURES = {
     "clv_gemm_f32": (_i, [_i, _i, _i, _i, _i, _f, _p, _i, _p, _i, _f, _p, _i, _p, _i, _p, _i, _p, _sz, _p, _p]),
     "clv_gemm_grouped_tn": (_i, [_p, _i, _i, _i, _p, _i, _f, _i, _p, _sz, _p, _p]),
     "clv_splitk_reduce_multi": (_i, [_p, _i, _p, _p, _p, _i, _p, _p, _i, _p]),
+    "clv_splitk_reduce_multi_outer_supported": (_i, [_i, _i, _i, _i, _i]),
+    "clv_splitk_reduce_multi_outer": (_i, [_p, _i, _p, _p, _p, _i, _p, _p, _i,
+                                           _i, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _p]),
     "clv_lstm_wgrad_supported": (_i, [_i, _i, _i, _i, _i]),
     "clv_lstm_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "clv_lstm_wgrad_pair_supported": (_i, [_p, _p]),

@@ -80,6 +80,7 @@ SWITCHES = {
     'lstm_mx':        ('CLV_USE_MX',           True,  "large batches on the generic chain instead of csrc/lstm_mx.hip"),
     'frames_u8':      ('CLV_FRAMES_U8',        True,  "the large-batch step widens its byte batch to float (rounds 4-5) instead of reading bytes"),
     'front_fused':    ('CLV_FRONT_FUSED',      True,  "the frame projections as a launch of their own behind the label launch instead of workgroups of it (csrc/label_head.hip: vrnn_front_kernel)"),
+    'tail_launch':    ('CLV_TAIL_LAUNCH',      True,  "the hW kernel gradient as a launch of its own in front of grads_tail() instead of workgroups of the reduction launch that ends it (csrc/tail_launch.hip)"),
     'fine_grid':      ('CLV_FINE_GRID',        False, "twice the workgroups, half the rows each, for the LSTM kernel gradients (what tune_dp_schedule may pick next to an all-reduce)"),
     'fuse_notes':     ('CLV_FUSE_NOTES',       False, "input projections gathered inside the pair forward from note lists (+48 us on MI355X: profiles/r03_notes_fusion_ab.txt)"),
 }
@@ -425,6 +426,12 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
             and ops.lstm_mx_supported(B, D, L, H)
         self.frames_u8 = sw('frames_u8')
         self.front_fused = sw('front_fused')
+        # the hW kernel gradient rides in the reduction launch that ends grads_tail() -- when nothing reads it in between:
+        # loss_and_grads(do_tail=True) knows that by itself; a caller that runs the two halves one after the other sets
+        # halves_adjacent for one pass (TrainStep: exactly when it has no all-reduce to start between them)
+        self.tail_launch = sw('tail_launch')
+        self.halves_adjacent = False
+        self._hw_outer = None        # the product's arguments while it is pending (loss_and_grads -> grads_tail)
         # notes_valid: the note lists describe the frames now in X / XZ (TrainStep sets it per staged batch)
         self.fuse_notes = sw('fuse_notes') and self.fuse_pair and self.sparse_inputs and D == ops.NOTE_NONE
         self.notes_valid = False
@@ -788,7 +795,8 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
 
     def tail_range(self):
         """(offset, numel) of the hW-kernel bucket inside the flat gradient buffer: complete after
-        loss_and_grads(do_tail=False), i.e. before grads_tail() has produced the rest."""
+        loss_and_grads(do_tail=False), i.e. before grads_tail() has produced the rest (unless the caller set
+        halves_adjacent for the pass: then it may be complete only after grads_tail())."""
         D, T = self.cfg['D'], self.cfg['T']
         return self.P.offsets['hW/kernel'], T * D * D
 
@@ -831,6 +839,8 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         C1, BT, G4 = Cn - 1, B * T, 4 * H
         inv_bt, inv_b = 1.0 / BT, 1.0 / B
         g, ws, off = ops.gemm, self.ws, self.off
+        adjacent, self.halves_adjacent = bool(do_tail or self.halves_adjacent), False
+        self._hw_outer = None
         self._train_pass = bool(need_grads)      # LSTM(dropout=p) applies in training passes only
         try:
             self.forward(X, Xp, eps_W, eps_Z, w_true, nll=(inv_bt, need_grads), target=target, noise=noise, frames8=frames8)
@@ -889,8 +899,15 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
             # over X (csrc/outer_bf16.hip); else the kernel that walks the notes
             outer = ops.dense_outer_bf16 if (self.dense_hw_grad and self.frames_exact_bf16 and
                                              ops.dense_outer_bf16_supported(B, T * D, D, T * D, D)) else ops.sparse_outer
-            outer(B, T * D, D, X if frames8 is None else frames8[0], T * D, self.dhW, D, P.g('hW/kernel'), colsum=P.g('hW/bias'),
-                  gdot=(self.hW, D, P.p('hW/bias'), self.gdot))
+            frames = X if frames8 is None else frames8[0]
+            gdot = (self.hW, D, P.p('hW/bias'), self.gdot)
+            if (outer is ops.dense_outer_bf16 and self.tail_launch and adjacent and self._rq() is not None
+                    and ops.reduce_outer_supported(B, T * D, D, T * D, D)):
+                # nothing reads the product before the pass's last launch: it runs there, beside the reduction (grads_tail)
+                self._hw_outer = dict(Bn=B, nx=T * D, N=D, X=frames, ldx=T * D, G=self.dhW, ldg=D, out=P.g('hW/kernel'),
+                                      colsum=P.g('hW/bias'), gdot=gdot)
+            else:
+                outer(B, T * D, D, frames, T * D, self.dhW, D, P.g('hW/kernel'), colsum=P.g('hW/bias'), gdot=gdot)
             self.gdot_fresh = True
         else:
             g(X, self.dhW, P.g('hW/kernel'), T * D, D, B, ta=True, ws=ws)
@@ -943,5 +960,6 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                                            self.dzsum_dec, 4 * H, B)
         # (the Wargs layer's gradient: per-row slabs of the label backward kernel, already among the pending reductions)
         if rq is not None:
-            rq.flush(means=getattr(self, '_loss_terms', None), out=self.scal, skinny=skinny)
+            rq.flush(means=getattr(self, '_loss_terms', None), out=self.scal, skinny=skinny, outer=self._hw_outer)
             self._loss_terms = None
+            self._hw_outer = None

@@ -65,11 +65,14 @@ class ReduceQueue:
         self.n += 1
         return a
 
-    def flush(self, means=None, out=None, skinny=None):
+    def flush(self, means=None, out=None, skinny=None, outer=None):
         """Run the pending reductions in one launch.  means: up to five (tensor, n, stride) terms whose means go to
         out[k] from extra blocks of the same launch (a step's loss terms: no launch of their own).  skinny: up to two
-        dict(A, lda, rows, B, ldb, N, K, C, ldc, bias_row) few-row products A[:, :rows]^T B riding along as well."""
-        if means or skinny or self.n:
+        dict(A, lda, rows, B, ldb, N, K, C, ldc, bias_row) few-row products A[:, :rows]^T B riding along as well.
+        outer: the arguments of dense_outer_bf16 as a dict (Bn, nx, N, X, ldx, G, ldg, out and optionally ldo, colsum, gdot)
+        -- that product as workgroups of the same launch (clv_splitk_reduce_multi_outer; reduce_outer_supported() says
+        which shapes), every result bit for bit what the two launches give."""
+        if means or skinny or self.n or outer is not None:
             means = means or []
             k = len(means)
             xs = (C.c_void_p * max(k, 1))(*[_ptr(t) for t, _, _ in means])
@@ -80,10 +83,23 @@ class ReduceQueue:
             for i, p in enumerate(skinny):
                 riders[i] = _lib.SkinnyProduct(_ptr(p['A']), p['lda'], p['rows'], _ptr(p['B']), p['ldb'], p['N'], p['K'],
                                                _ptr(p['C']), p['ldc'], _ptr(p.get('bias_row')))
-            check(_lib.lib().clv_splitk_reduce_multi(self.jobs, self.n, xs if k else None, ns if k else None, st if k else None, k,
-                                                     _ptr(out) if k else None, riders if skinny else None, len(skinny), _stream()),
-                  "clv_splitk_reduce_multi")
+            args = (self.jobs, self.n, xs if k else None, ns if k else None, st if k else None, k,
+                    _ptr(out) if k else None, riders if skinny else None, len(skinny))
+            if outer is None:
+                check(_lib.lib().clv_splitk_reduce_multi(*args, _stream()), "clv_splitk_reduce_multi")
+            else:
+                o = outer
+                h, ldh, hb, go = o['gdot'] if o.get('gdot') is not None else (None, 0, None, None)
+                ldo = o['ldo'] if o.get('ldo') is not None else o['N']
+                check(_lib.lib().clv_splitk_reduce_multi_outer(
+                    *args, o['Bn'], o['nx'], o['N'], _ptr(o['X']), _is_u8(o['X']), o['ldx'], _ptr(o['G']), o['ldg'], _ptr(o['out']),
+                    ldo, _ptr(o.get('colsum')), _ptr(h), int(ldh), _ptr(hb), _ptr(go), _stream()), "clv_splitk_reduce_multi_outer")
         self.n = 0
+
+
+def reduce_outer_supported(Bn, nx, N, ldx, ldg):
+    """shapes ReduceQueue.flush(outer=...) takes"""
+    return bool(_lib.lib().clv_splitk_reduce_multi_outer_supported(Bn, nx, N, ldx, ldg))
 
 
 def gemm(A, B, C_out, M, N, K, ta=False, tb=False, lda=None, ldb=None, ldc=None, alpha=1.0, beta=0.0,

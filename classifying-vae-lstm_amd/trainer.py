@@ -260,6 +260,9 @@ class TrainStep:
                                     noise=self.noise_spec(), bump=True)
             return
         if self.is_vrnn:     # eps is drawn inside the label / pair kernels where they run (else one Philox launch in forward())
+            # no all-reduce starts between this half and _tail(): the hW kernel gradient may wait for the pass's last launch
+            if hasattr(self.eng, 'halves_adjacent'):
+                self.eng.halves_adjacent = self.ar is None
             self.eng.loss_and_grads(self.X, self.Xp, self.w_true, self.eps_w, self.eps_z, do_tail=False, target=self.Y,
                                     noise=self.noise_spec(), frames8=self._f8)
             return

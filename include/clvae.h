@@ -120,7 +120,8 @@ typedef struct clv_frame_proj {
  *        CLV_FRAMES_U8 of lstm_mx_fwd, lstm_wgrad, out_head_train, dense_window_fwd_bf16, dense_outer_bf16; src_u8 == 2 of the
  *        gather); clv_latent_head_fwd draws its own eps (noise); removed: the 4x4x1 f32-MFMA sequence forward
  *        (lstm_seq_fwd_z) and the in-kernel input gather of the single-LSTM forward (lstm_seq_fwd_x), which no shipped path
- *        launched */
+ *        launched
+ *        (still 600: + clv_splitk_reduce_multi_outer / _supported, an addition; no existing entry point changed) */
 #define CLV_ABI_VERSION 600
 int clv_version(void);
 /* number of visible HIP devices whose arch is gfx950 (0 => the product must fail loudly) */
@@ -194,6 +195,24 @@ typedef struct clv_skinny_product {
 int clv_splitk_reduce_multi(const clv_reduce_job* jobs, int njobs, const float* const* x, const int* n,
                                const int* stride, int n_terms, float* means_out,
                                const clv_skinny_product* riders, int n_riders, void* stream);
+/* clv_splitk_reduce_multi_outer: the same launch with the dense bf16 kernel gradient of clv_dense_outer_bf16 (further down:
+ * its arguments Bn .. gdot, its rules, its results bit for bit) as workgroups in front of the reduction's -- the launch that
+ * ends the backward pass of a single-GPU cl_vrnn step.  The two are independent and complementary (the reduction waits on
+ * memory, the product is MFMA + LDS on fewer workgroups than the chip has CUs), and a captured step replays its launches on
+ * one queue, so they share the chip only as workgroups of one grid (csrc/tail_launch.hip).  Every workgroup then has the
+ * product's footprint (256 threads, 48 KB of LDS: 12 waves per CU), and the reduce blocks request the slab loads of a
+ * round together whatever the slab count; the order of additions per output is clv_splitk_reduce_multi's, so every reduced
+ * output, mean and rider product is bit for bit what that launch gives.  Bn == nx == N == 0 with X == G == out == NULL:
+ * no product, that reduction alone (12 KB of LDS).  The caller must know that nothing between the point where the product
+ * would have run and this launch reads its results (a data-parallel step starts the hW bucket's all-reduce there: it keeps
+ * the two launches).  _supported: the shapes the product takes (= clv_dense_outer_bf16_supported). */
+int clv_splitk_reduce_multi_outer_supported(int Bn, int nx, int N, int ldx, int ldg);
+int clv_splitk_reduce_multi_outer(const clv_reduce_job* jobs, int njobs, const float* const* x, const int* n,
+                                  const int* stride, int n_terms, float* means_out,
+                                  const clv_skinny_product* riders, int n_riders,
+                                  int Bn, int nx, int N, const void* X, int x_u8, int ldx, const float* G, int ldg,
+                                  float* out, int ldo, float* colsum, const float* Hact, int ldh, const float* hbias,
+                                  float* gdot, void* stream);
 
 /* Every kernel gradient of one LSTM in one pass over dz [K,N], N = 4H = 352, K = B*T (cl_vrnn/model.py:196-199,
  * 225-228; replaces the grouped f32-MFMA product for these shapes):
