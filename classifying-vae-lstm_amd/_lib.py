@@ -178,6 +178,9 @@ SIGNATURES = {
     "clv_vae_generate_clamped": (_i, [_i] * 8 + [_u64] + [_p] * 14),
     "clv_vrnn_generate_tempered": (_i, [_i] * 9 + [_u64] + [_p] * 16 + [_f, _f] + [_p] * 3),
     "clv_vae_generate_tempered": (_i, [_i] * 8 + [_u64] + [_p] * 11 + [_f, _f] + [_p] * 3),
+    "clv_vrnn_vary": (_i, [_i] * 8 + [_u64] + [_p] * 18 + [_f, _f] + [_p] * 3),
+    "clv_vae_vary": (_i, [_i] * 8 + [_u64] + [_p] * 13 + [_f, _f] + [_p] * 3),
+    "clv_take_frame": (_i, [_i64, _i, _i, _p, _p, _p, _p]),
     "clv_sigmoid_temper": (_i, [_i64, _p, _f, _p]),
     "clv_scale_temper": (_i, [_i64, _p, _f, _p]),
     "clv_label_fwd": (_i, [_i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p]),

@@ -8,11 +8,13 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
-from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, TEMPERATURE_FLAGS, parser_for, temperature_kwargs  # noqa: E402
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, parser_for,  # noqa: E402
+                           temperature_kwargs)
 from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
+from clvae_amd.vary import vary  # noqa: E402
 
 
 class Sampler:
@@ -85,6 +87,21 @@ class Sampler:
             write_sample(src, self.args.sample_dir, name + '_source', True)
         return list(rolls)
 
+    def vary_on_device(self, names):
+        """--vary: the t frames of a random test window re-decoded under their own key (the data's, or the
+        w-encoder's mean over the frames with --infer_w), or under --to_key; writes <name>.mid and <name>_source.mid."""
+        picks = [np.random.choice(range(len(self.data.x_test))) for _ in names]
+        sources = np.stack([np.asarray(self.data.x_test[i]).reshape(self.args.t, -1) for i in picks])
+        ws = None if self.args.infer_w else np.vstack([to_categorical(self.data.test_song_keys[i], self.margs['n_classes'])
+                                                       for i in picks])
+        rolls = vary(self.model, sources, ws, to_key=getattr(self.args, 'to_key', None), key_map=self.data.key_map,
+                     history=getattr(self.args, 'vary_history', 'own'), seed=getattr(self.args, 'seed', 0),
+                     **temperature_kwargs(self.args))
+        for roll, src, name in zip(rolls, sources, names):
+            write_sample(roll, self.args.sample_dir, name, True)
+            write_sample(src, self.args.sample_dir, name + '_source', True)
+        return list(rolls)
+
 
 def make_sample(P, dec_model, w_enc_model, z_enc_model, args, margs):
     """One sample from explicit sub-models (the reference's helper, :8-19)."""
@@ -104,8 +121,8 @@ def voice_of(args):
 def on_device(args):
     """Where the frame loop runs: like the reference (host loop, np.random) for every -n unless --device_loop asks for
     the device-side loop (Philox noise: other samples for the same np.random.seed, so it is opt-in); --harmonize
-    always runs there, and so does a sampling temperature (the parser refuses one next to --host_loop)."""
-    return bool(voice_of(args)) or bool(temperature_kwargs(args)) or (
+    and --vary always run there, and so does a sampling temperature (the parser refuses them next to --host_loop)."""
+    return bool(voice_of(args)) or bool(getattr(args, 'vary', False)) or bool(temperature_kwargs(args)) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
 
 
@@ -114,6 +131,8 @@ def sample(args):
     names = ['%s_%d' % (args.run_name, i) for i in range(args.n)]
     if voice_of(args):
         return s.harmonize_on_device(names)
+    if getattr(args, 'vary', False):
+        return s.vary_on_device(names)
     return s.many_on_device(names) if on_device(args) else [s.one(nm) for nm in names]
 
 
@@ -122,4 +141,4 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    sample(parser_for('cl_vae.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS).parse_args())
+    sample(parser_for('cl_vae.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS).parse_args())

@@ -17,7 +17,7 @@ import torch
 
 from .. import sampling
 from ..engine import VrnnEngine, vrnn_param_shapes
-from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy, temper_args
+from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy, temper_args, vary_samples_numpy
 from ..initializers import glorot_uniform, init_weights, orthogonal
 from ..keras_like import Layer, Model, get_value
 from ..utils.pianoroll import Windows
@@ -270,6 +270,20 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), e.cfg['D'], e.device)
     return e.generate(xs, w, int(nsteps), seed=int(seed), z_prior=z_prior, clamp=clamp,
                       **temper).cpu().numpy().astype(np.float64)
+
+
+def vary_samples_device(model, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
+                        z_temperature=1.0, return_xhat=False):
+    """Re-decode pieces on the device (VrnnEngine.vary): sources [N,T,88] binary frames, w_enc [N,C] the
+    label the encoder conditions on, w_dec [N,C] the decoder's (None: w_enc, a variation of the piece under its own key;
+    another label: key transfer).  both LSTMs start from zero state; frame t: the encoder step on [sources[t], w_enc], the decoder step on [xp, z_t, w_dec].
+    xp = x0 [N,88] (None: zeros) at t = 0, then the previous SAMPLE (history='own': the decoder runs on its own output) or
+    the previous source frame ('source': the training forward pass).  clamp: uint8 [N,T,88] roll, row t constrains frame t;
+    temperature, z_temperature as in generate_samples_device.  Returns [N,T,88] float64 (with return_xhat also the unclamped
+    probabilities [N,T,88] float64).  ValueError for wrong shapes, an unknown history, a bool or out-of-range temperature,
+    and a w_dec without a w_enc."""
+    return vary_samples_numpy(model.engine, sources, w_enc, w_dec, x0=x0, history=history, seed=seed, clamp=clamp,
+                              temperature=temperature, z_temperature=z_temperature, return_xhat=return_xhat)
 
 
 def make_w_encoder(model, original_dim, n_classes, seq_length=1, batch_size=1):

@@ -8,11 +8,13 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
-from clvae_amd.cli import DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, TEMPERATURE_FLAGS, parser_for, temperature_kwargs  # noqa: E402
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, parser_for,  # noqa: E402
+                           temperature_kwargs)
 from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
+from clvae_amd.vary import vary  # noqa: E402
 
 
 def seed_windows(P, key, n):
@@ -34,6 +36,8 @@ def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None)
     voice = getattr(args, 'harmonize', None)
     if voice:
         return harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice, half_speed)
+    if getattr(args, 'vary', False):
+        return vary_samples(P, w_enc_model, args, margs, model, picks, label_of, half_speed)
     if model is not None and len(picks):
         ws = [label_of(i) for i in picks]
         if args.infer_w:
@@ -83,6 +87,23 @@ def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice
     return rolls
 
 
+def vary_samples(P, w_enc_model, args, margs, model, picks, label_of, half_speed):
+    """--vary: the t frames of each picked test window re-decoded under their own key, or under --to_key.
+    Writes <run>_<j>.mid (the re-decoding) and <run>_<j>_source.mid (the window's frames)."""
+    if not len(picks):
+        return []
+    sources = np.stack([np.asarray(P.x_test[i])[:args.t] for i in picks])
+    ws = [label_of(i) for i in picks]
+    if args.infer_w:
+        ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in sources]
+    rolls = list(vary(model, sources, np.vstack(ws), to_key=getattr(args, 'to_key', None), key_map=P.key_map,
+                      history=getattr(args, 'vary_history', 'own'), seed=getattr(args, 'seed', 0), **temperature_kwargs(args)))
+    for j, roll in enumerate(rolls):
+        write_sample(roll, args.sample_dir, '%s_%d' % (args.run_name, j), half_speed)
+        write_sample(sources[j], args.sample_dir, '%s_%d_source' % (args.run_name, j), half_speed)
+    return rolls
+
+
 def sample(args):
     model, _, margs = M.load_model(args.model_file, optimizer='adam')
     dims = (margs['intermediate_dim'], margs['latent_dim'])
@@ -94,8 +115,8 @@ def sample(args):
     # --harmonize: windows of the seed's t frames and the t frames whose voice is kept
     P = PianoData(args.train_file, batch_size=1, seq_length=2 * args.t if voice else args.t, squeeze_x=False)
     # the reference's host loop (np.random) for every -n; --device_loop opts into the device-side loop (Philox noise), and
-    # a sampling temperature implies it (the parser refuses one next to --host_loop)
-    on_device = bool(voice) or bool(temperature_kwargs(args)) or (
+    # a sampling temperature and --vary imply it (the parser refuses them next to --host_loop)
+    on_device = bool(voice) or bool(getattr(args, 'vary', False)) or bool(temperature_kwargs(args)) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
     return gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
 
@@ -105,4 +126,4 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    sample(parser_for('cl_vrnn.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS).parse_args())
+    sample(parser_for('cl_vrnn.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS).parse_args())

@@ -128,6 +128,18 @@ TEMPERATURE_FLAGS = [
 ]
 
 
+# re-decoding (not in the reference): variations of test pieces and key transfer (implies --device_loop)
+VARY_HISTORY_CHOICES = ('own', 'source')
+VARY_FLAGS = [
+    Flag(('--vary',), ON, False, 're-decode the -t test frames of each pick: the encoder reads the piece, the decoder runs on '
+                                 'its own output (a variation of the piece; implies --device_loop)'),
+    Flag(('--to_key',), str, None, 'with --vary: decode under this key (a name of the data set\'s key map) instead of the '
+                                   "piece's own: key transfer"),
+    Flag(('--vary_history',), str, 'own', "with --vary: the decoder's previous frame is its own sample (own) or the piece's "
+                                          'frame (source: teacher-forced reconstruction)'),
+]
+
+
 def temperature_kwargs(args):
     """the sampling tools' --temperature / --z_temperature as keyword arguments of generate_samples_device / harmonize:
     empty where both are 1 (also for parsers without the flags)"""
@@ -137,7 +149,8 @@ def temperature_kwargs(args):
 
 class _Parser(argparse.ArgumentParser):
     """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles, a
-    temperature other than 1 not with --host_loop (the host loop is the reference's and has none)"""
+    temperature other than 1 not with --host_loop (the host loop is the reference's and has none), --vary not with
+    --harmonize or --host_loop, --to_key / --vary_history only with --vary"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -149,6 +162,13 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--particles must be >= 1')
         elif getattr(ns, 'infer_key', None):
             self.error('--infer_key needs --particles')
+        if getattr(ns, 'vary', False):
+            if getattr(ns, 'harmonize', None):
+                self.error('--vary re-decodes whole pieces: not with --harmonize')
+            if getattr(ns, 'host_loop', False):
+                self.error('--vary runs on the device loop: not with --host_loop')
+        elif getattr(ns, 'to_key', None) is not None or getattr(ns, 'vary_history', 'own') != 'own':
+            self.error('--to_key / --vary_history need --vary')
         temper = temperature_kwargs(ns)
         if temper:
             from .engine_generate import temper_args
@@ -170,6 +190,8 @@ def parser_for(tool, extra=()):
             p.add_argument(*f.names, type=f.kind, default=f.default, choices=SPLIT_CHOICES, help=f.help)
         elif f.names == ('--harmonize',):
             p.add_argument(*f.names, type=f.kind, default=f.default, choices=HARMONIZE_CHOICES, help=f.help)
+        elif f.names == ('--vary_history',):
+            p.add_argument(*f.names, type=f.kind, default=f.default, choices=VARY_HISTORY_CHOICES, help=f.help)
         elif f.names == ('--infer_key',):
             p.add_argument(*f.names, type=f.kind, default=f.default, choices=INFER_KEY_CHOICES, help=f.help)
         elif f.names[0].startswith('-'):

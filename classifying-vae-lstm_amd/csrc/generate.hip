@@ -43,6 +43,9 @@ struct GenArgs {
   float* xhat;                  // [N,S+nsteps,88] or null
   const uint8_t* clamp;         // [N,nsteps,88] (CL instances): row j constrains Xs[n,j], drawn at step S+j
   float inv_T, Tz;              // TP instances: 1 / temperature of the notes, temperature of the latent noise
+  const float* w_dec;           // VR instances: [N,C] the decoder's label (w is then the encoder's)
+  const float* x0;              // VR instances: [N,88] the frame before x_seed[:, 0], or null (zeros)
+  int hist_source;              // VR instances: the decoder's history is the source frame, not the fed-back sample
 };
 
 // slice_matvec with half the live registers: the h slice is consumed in two halves of 12 (the kernel is at its
@@ -87,7 +90,12 @@ __device__ __forceinline__ void frame_masks(const float* xbuf, int lane, float& 
 // TP = true: the tempered model: x_hat = sigmoid(fl(logit * inv_T)), z = m + exp(lv / 2) * fl(Tz * eps); both
 // factors are wave-uniform kernel arguments.  The draws themselves (keys, streams, steps, indices) are those of TP = false,
 // which folds away.
-template <int GATE, bool ZW, bool CL, bool TP>
+// VR = true (with CL and TP): re-decoding.  S = 0 and x_seed [N,nsteps,88] holds the SOURCE frames: the
+// encoder is teacher-forced with source frame t at every step (its writer lanes request frame t+1 a frame early, as seed
+// frames are requested), the decoder's input-kernel prefetch reads a second frame buffer (x0, then the fed-back sample or,
+// with hist_source, the encoder's previous input), and the two roles form their gate bias from two labels.  clamp may be
+// null (every note free).  VR = false folds away.
+template <int GATE, bool ZW, bool CL, bool TP, bool VR = false>
 __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   constexpr int GN_LQ = (ZW ? GN_LWIDE : GN_LMAX) / PK;
   extern __shared__ __attribute__((aligned(16))) float Kxl[];            // encoder input kernel [88][352], then Wo [88][88]
@@ -99,6 +107,8 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   __shared__ float wbuf[GN_CMAX];
   __shared__ float bo_l[CL ? 128 : 1];          // CL: the output bias, read in phase 4 instead of held in a register
   __shared__ uint8_t cbuf[CL ? 128 : 1];        // CL: the constraint byte of the current step, one per writer lane
+  __shared__ float xbuf_d[VR ? 128 : 1];        // VR: the decoder's history frame (xbuf is the encoder's input)
+  __shared__ float wbuf_d[VR ? GN_CMAX : 1];    // VR: the decoder's label
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool enc = wave < GN_NW;
@@ -126,10 +136,13 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   for (int i = tid; i < LH * LH; i += GN_NT) Wol[i] = a.Wo[i];
   for (int i = tid; i < 2 * 2 * PK * PKP; i += GN_NT) (&hb[0][0][0])[i] = 0.f;
   if (tid < GN_LWIDE) zbuf[tid] = 0.f;
-  if (tid < 128) xbuf[tid] = (a.S > 0 && tid < LH) ? a.x_seed[((size_t)n * a.S) * LH + tid] : 0.f;
+  if (tid < 128) xbuf[tid] = ((VR || a.S > 0) && tid < LH) ? a.x_seed[((size_t)n * (VR ? T : a.S)) * LH + tid] : 0.f;
   if (tid < a.C) wbuf[tid] = a.w[(size_t)n * a.C + tid];
   if (CL && tid < LH) bo_l[tid] = a.bo[tid];
-  if (CL && a.S == 0 && tid < LH) cbuf[tid] = a.clamp[(size_t)n * a.nsteps * LH + tid];      // step 0's row
+  if (CL && a.S == 0 && tid < LH)               // step 0's row
+    cbuf[tid] = (VR && !a.clamp) ? (uint8_t)255 : a.clamp[(size_t)n * a.nsteps * LH + tid];
+  if (VR && tid < 128) xbuf_d[tid] = (a.x0 && tid < LH) ? a.x0[(size_t)n * LH + tid] : 0.f;
+  if (VR && tid < a.C) wbuf_d[tid] = a.w_dec[(size_t)n * a.C + tid];
   __syncthreads();
 
   // recurrent kernel slice of this lane's unit (gate pairs), per-sequence bias W.K_w + b of its gate s
@@ -153,13 +166,14 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   float rb;
   {
     const float* Kw = enc ? a.Kw_enc : a.Kw_dec;
+    const float* wl = (VR && !enc) ? wbuf_d : wbuf;
     float acc = (enc ? a.b_enc : a.b_dec)[s * LH + u];
     for (int c0 = 0; c0 < a.C; c0 += 8) {
       float kv[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) kv[q] = Kw[(size_t)min(c0 + q, a.C - 1) * LG + s * LH + u];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) acc = fmaf(c0 + q < a.C ? wbuf[c0 + q] : 0.f, kv[q], acc);
+      for (int q = 0; q < 8; ++q) acc = fmaf(c0 + q < a.C ? wl[c0 + q] : 0.f, kv[q], acc);
     }
     rb = acc;
   }
@@ -204,11 +218,13 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   if (TP) e_cur = a.Tz * e_cur;
   const uint32_t crow = CL ? ((uint32_t)n * (uint32_t)a.nsteps - (uint32_t)a.S) * (uint32_t)LH : 0u;   // clamp row of step 0
   float seed_carry = 0.f;                         // CL: the constraint byte requested one frame ago
+  const float* src_n = VR ? a.x_seed + (size_t)n * T * LH : nullptr;      // VR: this sequence's source frames
   for (int t = 0; t < T; ++t) {
     const int cur = t & 1;
     float x0, x1;
     unsigned long long m0, m1;
-    frame_masks(xbuf, lane, x0, x1, m0, m1);       // xbuf = input frame of step t (seed frame or last sample)
+    // xbuf = input frame of step t (seed frame or last sample); VR: the source frame for the encoder, xbuf_d for the decoder
+    frame_masks((VR && !enc) ? xbuf_d : xbuf, lane, x0, x1, m0, m1);
     float u_cur = 0.f;
     float seed_next = 0.f;                         // teacher forcing: next seed frame, requested a whole frame early
     // CL: the constraint byte of the NEXT sampled step rides in the same register, which holds no seed frame where
@@ -217,8 +233,12 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     if (CL && enc && writer && t >= a.S && t > 0) cbuf[u] = (uint8_t)__builtin_bit_cast(uint32_t, seed_carry);
     if (enc && writer && t + 1 < a.S) seed_next = a.x_seed[((size_t)n * a.S + t + 1) * LH + u];
     if (CL && enc && writer && t + 1 >= a.S && t + 1 < T)
-      seed_next = __builtin_bit_cast(float, (uint32_t)a.clamp[crow + (uint32_t)(t + 1) * LH + (uint32_t)u]);
+      seed_next = __builtin_bit_cast(float, (VR && !a.clamp) ? 255u
+                                                : (uint32_t)a.clamp[crow + (uint32_t)(t + 1) * LH + (uint32_t)u]);
     if (CL) seed_carry = seed_next;
+    float src_next = 0.f;                          // VR: source frame t+1, the encoder's next input
+    // 32-bit offset from this sequence's (uniform) base: no per-lane address pair to keep across the frame
+    if (VR && enc && writer && t + 1 < T) src_next = src_n[(uint32_t)(t + 1) * (uint32_t)LH + (uint32_t)u];
     // ---- phase 1: encoder cell (enc waves) | decoder input-kernel rows from L2 (dec waves) ------------------------
     float xd = 0.f;
     if (enc) {
@@ -375,7 +395,12 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
         if (a.xhat) a.xhat[((size_t)n * T + t) * LH + u] = p;
         if (t >= a.S) a.Xs[((size_t)n * a.nsteps + (t - a.S)) * LH + u] = xs;
         // teacher forcing: the next input is the next seed frame while there is one
-        xbuf[u] = (t + 1 < a.S) ? seed_next : xs;
+        if (VR) {
+          xbuf_d[u] = a.hist_source ? xbuf[u] : xs;      // this lane alone writes slot u of both buffers
+          xbuf[u] = src_next;
+        } else {
+          xbuf[u] = (t + 1 < a.S) ? seed_next : xs;
+        }
       }
     }
     step_barrier();
@@ -425,6 +450,40 @@ int vrnn_generate_launch(int N, int S, int nsteps, int D, int H, int L, int C, i
   hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
   return launch_status();
 }
+
+// re-decoding: the VR instances, always clamped (a null roll is all free) and tempered (1.0f is exact)
+int vrnn_vary_launch(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
+                     const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kx_enc,
+                     const float* Kw_enc, const float* b_enc, const float* U_enc, const float* Wz, const float* bz,
+                     const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec, const float* U_dec,
+                     const float* Wo, const float* bo, const uint8_t* clamp, float inv_T, float Tz, float* Xs, float* xhat,
+                     void* stream) {
+  using namespace clv;
+  if (!clv_vrnn_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
+  if (gate_act != CLV_GATE_HARD_SIGMOID && gate_act != CLV_GATE_SIGMOID) return CLV_EINVAL;
+  if (!temper_factor_ok(inv_T, false) || !temper_factor_ok(Tz, true)) return CLV_EINVAL;
+  if (!sources || !w_enc || !w_dec || !Kx_enc || !Kw_enc || !b_enc || !U_enc || !Wz || !bz || !Kz || !Kw_dec || !b_dec ||
+      !U_dec || !Wo || !bo || !Xs)
+    return CLV_EINVAL;
+  if (((uintptr_t)Kx_enc) % 16 != 0) return CLV_EINVAL;
+  if (clamp && (uint64_t)N * T * LH > UINT32_MAX) return CLV_EINVAL;          // the kernel addresses the roll in 32 bits
+  if ((uint64_t)T * LH * sizeof(float) > UINT32_MAX) return CLV_EINVAL;       // and a sequence's source frames likewise
+  hipStream_t s = (hipStream_t)stream;
+  GenArgs a{N, 0, T, L, C, 0, Kx_dec != nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), sources, w_enc,
+            Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp, inv_T, Tz,
+            w_dec, x0, hist_source != 0};
+  const size_t lds = (size_t)(LH * LG + LH * LH) * sizeof(float);
+  const bool hard = gate_act == CLV_GATE_HARD_SIGMOID, wide = L > GN_LMAX;
+  void (*kern)(GenArgs) =
+      hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true, true, true>
+                   : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true, true, true>)
+           : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true, true, true>
+                   : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true, true, true>);
+  if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 156 * 1024)) return e;
+  ProfScope p("vrnn_vary", s);
+  hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
+  return launch_status();
+}
 }  // namespace
 
 extern "C" int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
@@ -462,4 +521,16 @@ extern "C" int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H
   return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
                               bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, true, inv_temperature, z_temperature, Xs,
                               xhat, stream);
+}
+
+extern "C" int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
+                             const float* sources, const float* x0, const float* w_enc, const float* w_dec,
+                             const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                             const float* Wz, const float* bz,
+                             const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                             const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                             float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream) {
+  return vrnn_vary_launch(N, T, D, H, L, C, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc,
+                          U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, inv_temperature, z_temperature, Xs,
+                          xhat, stream);
 }

@@ -469,9 +469,29 @@ __global__ void bernoulli_sample_clamped_kernel(int64_t n, int D, int nsteps, in
   x[i] = xs;
 }
 
+
+// out[r, :] = src[r, c, :] for the step c = *step_dev of a captured frame chain (src [R, T, D]); a step outside [0, T) leaves
+// out as it is
+__global__ void take_frame_kernel(int64_t n, int T, int D, const float* src, const int32_t* step_dev, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int c = *step_dev;
+  if (c < 0 || c >= T) return;
+  const int64_t r = i / D, j = i - r * D;
+  out[i] = src[(r * T + c) * D + j];
+}
+
 }  // namespace clv
 
 using namespace clv;
+
+extern "C" int clv_take_frame(int64_t n, int T, int D, const float* src, const int32_t* step_dev, float* out, void* stream) {
+  if (n <= 0 || T <= 0 || D <= 0 || n % D != 0 || !src || !step_dev || !out) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("take_frame", s);
+  hipLaunchKernelGGL(take_frame_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, T, D, src, step_dev, out);
+  return launch_status();
+}
 
 extern "C" int clv_label_fwd(int B, int C, const float* mean, const float* logvar, int ld_in,
                              const float* eps, const float* onehot, float prior_logvar,

@@ -38,6 +38,9 @@ struct VaeGenArgs {
   float* xhat;                  // [N,nsteps,88] or null
   const uint8_t* clamp;         // [N,nsteps,88] (CL instance): row t constrains frame t
   float inv_T, Tz;              // TP instances: 1 / temperature of the notes, temperature of the latent noise
+  const float* w_dec;           // VR instance: [N,C] the decoder's label (w is then the z-encoder's)
+  const float* x0;              // VR instance: [N,88] the frame before x_seed[:, 0], or null (zeros)
+  int hist_source;              // VR instance: the decoder's history is the source frame, not the fed-back sample
 };
 
 // sum over the notes that are on (two scalar masks: inputs 0..63 / 64..87) of row n of an LDS-resident [88][88] kernel,
@@ -64,7 +67,11 @@ __device__ __forceinline__ float gather_rows(const float* Kl, int j, unsigned lo
 // (any other byte leaves the draw); the clamped frame is stored and is the next input.  CL = false folds away.
 // TP = true: the tempered model: x_hat = sigmoid(fl(logit * inv_T)), z = mean + exp(lv / 2) * fl(Tz * eps), both
 // factors wave-uniform kernel arguments; same draws as TP = false, which folds away.
-template <bool CL, bool TP>
+// VR = true (with CL and TP): re-decoding.  x_seed [N,nsteps,88] holds the SOURCE frames: the z-encoder
+// reads source frame t (requested a frame early by the writer lanes), the decoder's history is the frame directly before t
+// as in training -- x0, then the fed-back sample or, with hist_source, source frame t-1 -- and the two hidden layers take
+// their label share from two labels.  clamp may be null (every note free).  VR = false folds away.
+template <bool CL, bool TP, bool VR = false>
 __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   extern __shared__ __attribute__((aligned(16))) float vg_lds[];
   float* Khl = vg_lds;                        // [88][88] frame rows of the z-encoder's hidden kernel
@@ -74,6 +81,8 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   __shared__ float zbuf[VG_LMAX];
   __shared__ float xbuf[2][128];              // [parity]: the frame sampled last (0/1 per note)
   __shared__ float wbuf[VG_CMAX];
+  __shared__ float xhis[VR ? 128 : 1];        // VR: the decoder's history frame (x0, then the sample of the frame before)
+  __shared__ float wbuf_d[VR ? VG_CMAX : 1];  // VR: the decoder's label
   const int tid = threadIdx.x, lane = tid & 63;
   const int s = tid & 3, o_raw = tid >> 2, o = min(o_raw, LH - 1);       // output slot (unit / note) and k-slice
   const int L = a.L, n = blockIdx.x;
@@ -89,8 +98,13 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
     Kdz[i] = i < L * LH ? a.Kd[(size_t)(a.C + (a.has_xp ? LH : 0)) * LH + i] : 0.f;
   for (int i = tid; i < 2 * PK * PKP; i += VG_NT) (&hbuf[0][0])[i] = 0.f;
   if (tid < VG_LMAX) zbuf[tid] = 0.f;
-  if (tid < 128) { xbuf[0][tid] = tid < LH ? a.x_seed[(size_t)n * LH + tid] : 0.f; xbuf[1][tid] = xbuf[0][tid]; }
+  if (tid < 128) {
+    xbuf[0][tid] = tid < LH ? a.x_seed[(size_t)n * (VR ? a.nsteps : 1) * LH + tid] : 0.f;
+    xbuf[1][tid] = xbuf[0][tid];
+    if (VR) xhis[tid] = (a.x0 && tid < LH) ? a.x0[(size_t)n * LH + tid] : 0.f;
+  }
   if (tid < VG_CMAX) wbuf[tid] = tid < a.C ? a.w[(size_t)n * a.C + tid] : 0.f;
+  if (VR && tid < VG_CMAX) wbuf_d[tid] = tid < a.C ? a.w_dec[(size_t)n * a.C + tid] : 0.f;
   // head kernel: slot c < 2L owns column c; the pairs (mean_l, log_var_l) sit in neighbouring slots 2l, 2l+1 so that the
   // log-variance reaches the mean's lanes by one DPP row shift (the kernel's own column order is [means | log-variances])
   const int zc = (o_raw & 1) * L + (o_raw >> 1);          // head column of this slot
@@ -107,7 +121,7 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   float ch = a.bh[o], cd = a.bd[o];
   for (int c = 0; c < a.C; ++c) {
     ch = fmaf(wbuf[c], a.Kh[(size_t)(LH + c) * LH + o], ch);
-    cd = fmaf(wbuf[c], a.Kd[(size_t)c * LH + o], cd);
+    cd = fmaf((VR ? wbuf_d : wbuf)[c], a.Kd[(size_t)c * LH + o], cd);
   }
   // notes of the current input frame and of the one before it (the decoder's history lags: cl_vae/model.py:38-40)
   unsigned long long cur0, cur1, his0, his1;
@@ -115,13 +129,19 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
     const float x0 = xbuf[0][lane], x1 = lane + 64 < LH ? xbuf[0][lane + 64] : 0.f;
     cur0 = __ballot(x0 != 0.f); cur1 = __ballot(x1 != 0.f);
     his0 = cur0; his1 = cur1;
+    if (VR) {
+      const float h0 = xhis[lane], h1 = lane + 64 < LH ? xhis[lane + 64] : 0.f;
+      his0 = __ballot(h0 != 0.f); his1 = __ballot(h1 != 0.f);
+    }
   }
 
   for (int t = 0; t < a.nsteps; ++t) {
     // this frame's noise, drawn before anything depends on it
     const float u_cur = writer ? philox_uniform_at((uint64_t)n * LH + o, a.k0, a.k1, 1u, (uint32_t)t) : 2.f;
     // this frame's constraint, requested three barriers before phase 4 uses it (2: free)
-    const uint32_t cb = (CL && writer) ? (uint32_t)a.clamp[((size_t)n * a.nsteps + t) * LH + o] : 2u;
+    const uint32_t cb = (CL && writer && !(VR && !a.clamp)) ? (uint32_t)a.clamp[((size_t)n * a.nsteps + t) * LH + o] : 2u;
+    // VR: source frame t+1, the z-encoder's next input, requested a whole frame before it is published
+    const float src_next = (VR && writer && t + 1 < a.nsteps) ? a.x_seed[((size_t)n * a.nsteps + t + 1) * LH + o] : 0.f;
     const bool zdraw = s == 0 && zslot && !(o_raw & 1);                 // the mean slot of latent l = o_raw / 2
     float eps = zdraw ? philox_normal_at((uint64_t)n * L + (o_raw >> 1), a.k0, a.k1, 0u, (uint32_t)t) : 0.f;
     if (TP) eps = a.Tz * eps;
@@ -170,13 +190,18 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
         if (CL && cb <= 1u) xs = (float)cb;         // 0: forced off, 1: forced on, else free (the draw stands)
         if (a.xhat) a.xhat[((size_t)n * a.nsteps + t) * LH + o] = p;
         a.Xs[((size_t)n * a.nsteps + t) * LH + o] = xs;
-        xbuf[(t + 1) & 1][o] = xs;
+        xbuf[(t + 1) & 1][o] = VR ? src_next : xs;
+        if (VR) xhis[o] = xs;               // read after this frame's last barrier, written again three barriers later
       }
     }
     step_barrier();
     {
       const float x0 = xbuf[(t + 1) & 1][lane], x1 = lane + 64 < LH ? xbuf[(t + 1) & 1][lane + 64] : 0.f;
       his0 = cur0; his1 = cur1;
+      if (VR && !a.hist_source) {
+        const float h0 = xhis[lane], h1 = lane + 64 < LH ? xhis[lane + 64] : 0.f;
+        his0 = __ballot(h0 != 0.f); his1 = __ballot(h1 != 0.f);
+      }
       cur0 = __ballot(x0 != 0.f); cur1 = __ballot(x1 != 0.f);
     }
   }
@@ -208,6 +233,26 @@ int vae_generate_launch(int N, int nsteps, int D, int H, int L, int C, int use_x
   hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
   return launch_status();
 }
+
+// re-decoding: the VR instance, always clamped (a null roll is all free) and tempered (1.0f is exact)
+int vae_vary_launch(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
+                    const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
+                    const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
+                    const float* bo, const uint8_t* clamp, float inv_T, float Tz, float* Xs, float* xhat, void* stream) {
+  using namespace clv;
+  if (!clv_vae_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
+  if (!temper_factor_ok(inv_T, false) || !temper_factor_ok(Tz, true)) return CLV_EINVAL;
+  if (!sources || !w_enc || !w_dec || !Kh || !bh || !Kz || !bz || !Kd || !bd || !Ko || !bo || !Xs) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  VaeGenArgs a{N, T, L, C, 0, use_x_prev != 0, (uint32_t)seed, (uint32_t)(seed >> 32), sources, w_enc, Kh, bh, Kz, bz, Kd, bd,
+               Ko, bo, Xs, xhat, clamp, inv_T, Tz, w_dec, x0, hist_source != 0};
+  const size_t lds = (size_t)(2 * LH * LH + VG_LMAX * LH) * sizeof(float);
+  void (*kern)(VaeGenArgs) = vae_generate_kernel<true, true, true>;
+  if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 96 * 1024)) return e;
+  ProfScope p("vae_vary", s);
+  hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
+  return launch_status();
+}
 }  // namespace
 
 extern "C" int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
@@ -235,4 +280,13 @@ extern "C" int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L,
   if (!clv::temper_factor_ok(inv_temperature, false) || !clv::temper_factor_ok(z_temperature, true)) return CLV_EINVAL;
   return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
                              clamp, true, inv_temperature, z_temperature, Xs, xhat, stream);
+}
+
+extern "C" int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
+                            const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
+                            const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
+                            const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
+                            float z_temperature, float* Xs, float* xhat, void* stream) {
+  return vae_vary_launch(N, T, D, H, L, C, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko,
+                         bo, clamp, inv_temperature, z_temperature, Xs, xhat, stream);
 }

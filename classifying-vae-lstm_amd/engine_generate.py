@@ -158,6 +158,49 @@ def temper_args(temperature, z_temperature):
     return float(inv_T), float(Tz32)
 
 
+VARY_HISTORY = ('own', 'source')
+
+
+def vary_args(sources, w_enc, w_dec, x0, history, clamp, D, C, device):
+    """Validate the arguments of a re-decoding and return them as contiguous device tensors: (sources
+    [N, T, D] fp32, w_enc [N, C], w_dec [N, C] (w_enc where None), x0 [N, D] or None, the roll or None, history == 'source').
+    numpy or torch in; ValueError for a wrong shape, an unknown history, and a w_dec given without a w_enc."""
+    if history not in VARY_HISTORY:
+        raise ValueError("history must be one of %s, got %r" % (VARY_HISTORY, history))
+    if w_enc is None:
+        raise ValueError("re-decoding needs w_enc, the label the encoder conditions on%s"
+                         % ("" if w_dec is None else " (w_dec was given without it)"))
+    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32))
+                   ).to(dtype=torch.float32, device=device).contiguous()
+    sources = t(sources)
+    if sources.dim() != 3 or sources.shape[0] < 1 or sources.shape[1] < 1 or sources.shape[2] != D:
+        raise ValueError("sources must be [N, T, %d] with N, T >= 1, got shape %s" % (D, tuple(sources.shape)))
+    N = int(sources.shape[0])
+    w_enc = t(w_enc)
+    w_dec = w_enc if w_dec is None else t(w_dec)
+    for name, w in (('w_enc', w_enc), ('w_dec', w_dec)):
+        if tuple(w.shape) != (N, C):
+            raise ValueError("%s must have shape %s, got %s" % (name, (N, C), tuple(w.shape)))
+    if x0 is not None:
+        x0 = t(x0)
+        if tuple(x0.shape) != (N, D):
+            raise ValueError("x0 must have shape %s, got %s" % ((N, D), tuple(x0.shape)))
+    return sources, w_enc, w_dec, x0, clamp_roll(clamp, N, int(sources.shape[1]), D, device), history == 'source'
+
+
+def vary_samples_numpy(engine, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
+                       z_temperature=1.0, return_xhat=False):
+    """vary_samples_device of both families: engine.vary on host arrays -> [N, T, D] float64 (and x_hat, float64)"""
+    temper_args(temperature, z_temperature)
+    cfg, d = engine.cfg, engine.device
+    sources, w_enc, w_dec, x0, clamp, _ = vary_args(sources, w_enc, w_dec, x0, history, clamp, cfg['D'], cfg['C'], d)
+    xhat = torch.zeros_like(sources) if return_xhat else None
+    Xs = engine.vary(sources, w_enc, w_dec, x0=x0, history=history, seed=int(seed), clamp=clamp, temperature=temperature,
+                     z_temperature=z_temperature, xhat_out=xhat)
+    Xs = Xs.cpu().numpy().astype(np.float64)
+    return (Xs, xhat.cpu().numpy().astype(np.float64)) if return_xhat else Xs
+
+
 def smc_samples_numpy(engine, x_seed, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
                       w_prior=None, return_key=False, temperature=1.0, z_temperature=1.0):
     """generate_samples_device(particles=P): one draw per melody, [N, nsteps, D] float64 (and log_evidence [N] float64;
@@ -312,6 +355,58 @@ class VaeGenerate:
             Xs[:, t].copy_(x_next)
         return Xs
 
+    def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
+             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None):
+        """Re-decode sources [N, T, D]: per frame t the z-encoder on [sources[t], w_enc], z = mean +
+        exp(lv / 2) * Tz * eps, the decoder on [w_dec, xp, z] with xp the frame directly before t as in training: x0 (None:
+        zeros) at t = 0, then the sample of frame t-1 (history='own') or sources[t-1] ('source': the training forward pass);
+        x ~ Bernoulli(x_hat), then the roll clamp [N, T, D] (row t constrains frame t).  w_dec=None: w_enc (a variation);
+        another label: key transfer.  Noise as generate's (step = frame).  persistent=True (default where the shapes allow):
+        ONE kernel, a workgroup per sequence (the VR instance of csrc/vae_generate.hip; any N); else the layer chain,
+        captured once and replayed per frame (N <= batch size), reading its source frame through the device step counter.
+        Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
+        cfg, d = self.cfg, self.device
+        D, L = cfg['D'], cfg['L']
+        temper = temper_args(temperature, z_temperature)
+        sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, cfg['C'], d)
+        N, T = int(sources.shape[0]), int(sources.shape[1])
+        f = dict(dtype=torch.float32, device=d)
+        Xs = torch.zeros(N, T, D, **f)
+        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
+            P = self.P
+            ops.vae_vary(N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], hist_source, seed, sources, x0, w_enc, w_dec,
+                         P.p('h/kernel'), P.p('h/bias'), P.p('zargs/kernel'), P.p('zargs/bias'), P.p('decoder_h/kernel'),
+                         P.p('decoder_h/bias'), P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs, xhat_out,
+                         clamp=clamp, temper=temper)
+            return Xs
+        if N > self.B:
+            raise ValueError("%d sequences exceed the engine's batch size %d" % (N, self.B))
+        x_src, x_next = torch.zeros(N, D, **f), torch.zeros(N, D, **f)
+        xp = torch.zeros(N, D, **f) if x0 is None else x0.clone()
+        eps, u = torch.zeros(N, L, **f), torch.zeros(N, D, **f)
+        counter = torch.zeros(1, dtype=torch.int32, device=d)
+
+        def frame():
+            ops.take_frame(N, T, D, sources, counter, x_src)
+            self.encode_z(x_src, w_enc, N)
+            ops.philox_normal(eps, N * L, seed, 0, 0, 0, step_dev=counter)
+            _temper_eps(temper, eps, N * L)
+            ops.gauss_fwd(N, L, self.zargs, eps, self.z, L, None)
+            self.decode(w_dec, self.z, xp if cfg['use_x_prev'] else None, N, act=_head_act(temper))
+            _temper_head(temper, self.logits, N * D)
+            ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
+            _vary_sample(N, D, T, self.logits, u, clamp, counter, x_next)
+            ops.i32_add(counter, 1)
+            xp.copy_(x_src if hist_source else x_next)
+
+        def after(t):
+            Xs[:, t].copy_(x_next)
+            if xhat_out is not None:
+                xhat_out[:, t].copy_(self.logits[:N])
+
+        _replay(frame, T, use_graph, after=after)
+        return Xs
+
     def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
                      z_prior=False, chunk=None, w_prior=None, temperature=1.0, z_temperature=1.0):
         """Particle-filter sampling under the constraint roll clamp [N, nsteps, D]: melody m runs P =
@@ -389,9 +484,17 @@ def _temper_eps(temper, eps, n):
         ops.scale_temper(n, eps, temper[1])
 
 
-def _replay(frame, nsteps, use_graph, before=None):
+def _vary_sample(N, D, T, p, u, clamp, counter, x_next):
+    """a re-decoding chain's draw of frame *counter: x_next = [u <= p], then row *counter of the roll (None: all free)"""
+    if clamp is None:
+        ops.bernoulli_sample(N * D, p, u, x_next)
+    else:
+        ops.bernoulli_sample_clamped(N * D, D, T, 0, p, u, clamp, counter, x_next)
+
+
+def _replay(frame, nsteps, use_graph, before=None, after=None):
     """run frame() nsteps times: step 0 eagerly (it sizes every workspace), then one captured graph replayed per step;
-    before(t) runs eagerly ahead of step t"""
+    before(t) runs eagerly ahead of step t, after(t) behind it"""
     graph = None
     for t in range(nsteps):
         if before is not None:
@@ -403,6 +506,8 @@ def _replay(frame, nsteps, use_graph, before=None):
             graph.launch()
         else:
             frame()
+        if after is not None:
+            after(t)
 
 
 class VrnnGenerate:
@@ -538,6 +643,62 @@ class VrnnGenerate:
                 frame()
             if t >= S:
                 Xs[:, t - S].copy_(x_next)
+        return Xs
+
+    def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
+             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None):
+        """Re-decode sources [N, T, D]: from zero LSTM states, per frame t the encoder step on [sources[t],
+        w_enc], z = mean + exp(lv / 2) * Tz * eps, the decoder step on [xp, z, w_dec] with xp = x0 (None: zeros) at t = 0,
+        then the sample of frame t-1 (history='own') or sources[t-1] ('source': the training forward pass; no effect
+        without use_x_prev); x ~ Bernoulli(x_hat), then the roll clamp [N, T, D] (row t constrains frame t; no bridge).
+        w_dec=None: w_enc (a variation); another label: key transfer.  Noise as generate's with S = 0.  persistent=True
+        (default where the shapes allow): ONE kernel, a workgroup per sequence (the VR instances of csrc/generate.hip);
+        else the per-frame chain, captured once and replayed per frame, reading its source frame through the device step
+        counter.  A roll of 2^32 bytes or more takes the chain.  Returns Xs [N, T, D]; xhat_out [N, T, D] receives the
+        unclamped (tempered) probabilities."""
+        cfg, d, P = self.cfg, self.device, self.P
+        D, H, L, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.off
+        temper = temper_args(temperature, z_temperature)
+        sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, Cn, d)
+        N, T = int(sources.shape[0]), int(sources.shape[1])
+        f = dict(dtype=torch.float32, device=d)
+        Xs = torch.zeros(N, T, D, **f)
+        if (clamp is not None and clamp.numel() >= 2 ** 32) or T * D * 4 >= 2 ** 32:
+            persistent = False
+        if persistent and ops.vrnn_generate_supported(D, H, L, Cn):
+            rows = lambda name, r: P.rows(P.params, name, r)
+            ops.vrnn_vary(N, T, D, H, L, Cn, self.gate_act, hist_source, seed, sources, x0, w_enc, w_dec,
+                          P.p('encoder_h/kernel'), rows('encoder_h/kernel', D), P.p('encoder_h/bias'),
+                          P.p('encoder_h/recurrent_kernel'), P.p('Zargs/kernel'), P.p('Zargs/bias'),
+                          P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
+                          rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
+                          P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out, clamp=clamp, temper=temper)
+            return Xs
+        st = self.new_state(N)
+        x_src, x_next = torch.zeros(N, D, **f), torch.zeros(N, D, **f)
+        xp = torch.zeros(N, D, **f) if x0 is None else x0.clone()
+        eps, u, z = torch.zeros(N, L, **f), torch.zeros(N, D, **f), torch.zeros(N, L, **f)
+        counter = torch.zeros(1, dtype=torch.int32, device=d)
+
+        def frame():
+            ops.take_frame(N, T, D, sources, counter, x_src)
+            self.enc_step(x_src, w_enc, st)
+            ops.philox_normal(eps, N * L, seed, 0, 0, 0, step_dev=counter)
+            _temper_eps(temper, eps, N * L)
+            ops.gauss_fwd(N, L, st['zargs'], eps, z, L, None)
+            self.dec_step(z, xp if cfg['use_x_prev'] else None, w_dec, st, act=_head_act(temper))
+            _temper_head(temper, st['xhat'], N * D)
+            ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
+            _vary_sample(N, D, T, st['xhat'], u, clamp, counter, x_next)
+            ops.i32_add(counter, 1)
+            xp.copy_(x_src if hist_source else x_next)
+
+        def after(t):
+            Xs[:, t].copy_(x_next)
+            if xhat_out is not None:
+                xhat_out[:, t].copy_(st['xhat'])
+
+        _replay(frame, T, use_graph, after=after)
         return Xs
 
     def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,

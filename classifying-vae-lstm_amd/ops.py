@@ -410,6 +410,33 @@ def vae_generate(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, x_seed, w, K
               "clv_vae_generate_clamped")
 
 
+def vrnn_vary(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
+              Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None, temper=None):
+    """cl_vrnn re-decoding of sources [N,T,D] in one persistent launch (clv_vrnn_vary); x0, clamp, xhat may be
+    None; temper: None or (inv_temperature, z_temperature)."""
+    inv_T, Tz = (1.0, 1.0) if temper is None else temper
+    check(_lib.lib().clv_vrnn_vary(N, T, D, H, L, Cn, gate_act, int(bool(hist_source)), int(seed), _ptr(sources), _ptr(x0),
+                                   _ptr(w_enc), _ptr(w_dec), _ptr(Kx_enc), _ptr(Kw_enc), _ptr(b_enc), _ptr(U_enc), _ptr(Wz),
+                                   _ptr(bz), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec), _ptr(U_dec), _ptr(Wo), _ptr(bo),
+                                   _ptr(clamp), float(inv_T), float(Tz), _ptr(Xs), _ptr(xhat), _stream()), "clv_vrnn_vary")
+
+
+def vae_vary(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs,
+             xhat=None, clamp=None, temper=None):
+    """cl_vae re-decoding of sources [N,T,D] in one persistent launch (clv_vae_vary); arguments as vrnn_vary"""
+    inv_T, Tz = (1.0, 1.0) if temper is None else temper
+    check(_lib.lib().clv_vae_vary(N, T, D, H, L, Cn, int(bool(use_x_prev)), int(bool(hist_source)), int(seed), _ptr(sources),
+                                  _ptr(x0), _ptr(w_enc), _ptr(w_dec), _ptr(Kh), _ptr(bh), _ptr(Kz), _ptr(bz), _ptr(Kd), _ptr(bd),
+                                  _ptr(Ko), _ptr(bo), _ptr(clamp), float(inv_T), float(Tz), _ptr(Xs), _ptr(xhat), _stream()),
+          "clv_vae_vary")
+
+
+def take_frame(R, T, D, src, step_dev, out):
+    """out [R, D] = src[:, *step_dev] of src [R, T, D]: a captured frame chain's read of its source (clv_take_frame)"""
+    check(_lib.lib().clv_take_frame(int(R) * int(D), int(T), int(D), _ptr(src), _ptr(step_dev), _ptr(out), _stream()),
+          "clv_take_frame")
+
+
 def lstm_pair_supported(L, H=88):
     return bool(_lib.lib().clv_lstm_pair_supported(H, L))
 

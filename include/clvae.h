@@ -488,6 +488,33 @@ int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L, int C, int
 int clv_sigmoid_temper(int64_t n, float* a, float inv_temperature, void* stream);
 int clv_scale_temper(int64_t n, float* eps, float z_temperature, void* stream);
 
+/* ------------------------------------- re-decoding a piece (variations, key transfer) --
+ * DESIGN.md 14.  The frame loops above with the ENCODER teacher-forced on sources [N,T,D] for the whole length and the
+ * decoder running on its own output: per frame t the encoder step on [sources[t], w_enc], z = mean + exp(log_var/2) *
+ * fl(z_temperature * eps), the decoder step on [xp, z, w_dec] with xp = x0 [N,D] (NULL: zeros) at t = 0, then the sample of
+ * frame t-1 (hist_source = 0) or sources[t-1] (hist_source != 0; the training forward pass), x_hat = sigmoid(fl(logit *
+ * inv_temperature)), x = [u <= x_hat], then the roll clamp [N,T,D] (NULL: every note free; row t constrains frame t; there is
+ * no bridge).  cl_vae: the decoder's history is the frame directly before t, as in training.  Without use_x_prev (Kx_dec NULL
+ * / use_x_prev = 0) hist_source has no effect.  Philox keys, streams, steps and indices are those of clv_vrnn_generate /
+ * clv_vae_generate with S = 0.  Xs [N,T,D]; xhat [N,T,D] (optional) the unclamped probabilities.  Shapes: those of
+ * clv_vrnn_generate_supported / clv_vae_generate_supported; N, T >= 1; with a roll N*T*D < 2^32 (cl_vrnn).  CLV_EINVAL for the
+ * temperatures clv_vrnn_generate_tempered refuses. */
+int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
+                  const float* sources, const float* x0, const float* w_enc, const float* w_dec,
+                  const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                  const float* Wz, const float* bz,
+                  const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                  const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                  float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream);
+int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
+                 const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
+                 const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
+                 const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
+                 float z_temperature, float* Xs, float* xhat, void* stream);
+/* The per-frame chains' read of the source: out[r,:] = src[r, *step_dev, :] for src [n/D, T, D] (n = rows * D elements), the
+ * step read from the device counter of the captured frame; a step outside [0, T) leaves out untouched. */
+int clv_take_frame(int64_t n, int T, int D, const float* src, const int32_t* step_dev, float* out, void* stream);
+
 /* ------------------------------------------------------------ pointwise --
  * logistic-normal label sample + its two losses, one thread per row:
  *   w = softmax([mean + exp(lv/2)*eps, 0]); kl_w, w_rec = (C-1)*CCE(onehot, w+1e-10), hit
