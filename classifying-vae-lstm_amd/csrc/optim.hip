@@ -761,16 +761,22 @@ extern "C" int clv_adam_wn_step(const clv_param_desc* host_table, int n_tensors,
   // step_t == -1 with a device counter: read it, leave it alone (another call of the same step, on another subset of the
   // tensors, advances it)
   int32_t* bump = (iterations_dev && (step_t == -1 || step_t == CLV_STEP_ADVANCED)) ? nullptr : iterations_dev;
-  ProfScope pr("adam_wn_step", st);
   const bool wn = weightnorm == CLV_OPT_ADAM_WN && c.n_cols > 0;
-  if (known && known->use && wn) {
-    // the two-launch form: exactly one tall matrix, whose sum g.V the caller brings and whose ||V||^2 vn2 holds
+  const bool fast = known && known->use && wn;
+  int nunits = 0;
+  if (fast) {
+    // the two-launch form: exactly one tall matrix, whose sum g.V the caller brings and whose ||V||^2 vn2 holds.  Its argument
+    // checks come before the profiler scope: a refused call launches nothing and leaves no 'adam_wn_step' record either
     const int ti = known->tensor;
     if (ti < 0 || ti >= n_tensors || c.n_big != 1 || is_small(host_table[ti]) || !known->gdot || !vn2) return CLV_EINVAL;
     const clv_param_desc& t = host_table[ti];
     if (t.cols > 128 || t.cols % 2 || t.offset % 2 || t.col_offset % 2) return CLV_EINVAL;      // 8-byte accesses
-    const int nunits = (t.rows + FAST_ROWS - 1) / FAST_ROWS;
+    nunits = (t.rows + FAST_ROWS - 1) / FAST_ROWS;
     if ((size_t)nunits * t.cols > (size_t)c.n_part) return CLV_EWORKSPACE;      // partC lives where the classic chain keeps its own
+  }
+  ProfScope pr("adam_wn_step", st);
+  if (fast) {
+    const clv_param_desc& t = host_table[known->tensor];
     AdamFast f{t.offset, t.col_offset, t.rows, t.cols, nunits, known->gdot, vn2, colscal, partC};
     hipLaunchKernelGGL(wn_fast_update_kernel, dim3(nunits + c.n_small), dim3(FAST_NT), 0, st, f, small, params, grads, m, v, mg,
                        vg, s, h);

@@ -356,6 +356,8 @@ def test_bce_clip_points_are_those_of_float32_keras(dev):
 
 @pytest.mark.parametrize("weightnorm", [True, False])
 def test_adam_wn_three_steps(dev, weightnorm):
+    """A cheap end-to-end run through FlatParams against the oracle, parameters only.  The optimizer state (m, v, mg, vg, s, vn2),
+    every route of the launcher and per-element bounds: tests/test_gpu_optim.py."""
     from clvae_amd.engine import FlatParams
     rng = np.random.default_rng(7)
     shapes = [('a/kernel', (200, 88)), ('a/bias', (88,)), ('b/kernel', (88, 3)), ('b/bias', (3,)),
@@ -379,7 +381,8 @@ def test_adam_wn_three_steps(dev, weightnorm):
 
 
 def test_rmsprop_three_steps(dev):
-    """The 'rmsprop' optimizer string (cl_vae/train.py:83): CLV_OPT_RMSPROP vs the oracle's Keras RMSprop."""
+    """The 'rmsprop' optimizer string (cl_vae/train.py:83): CLV_OPT_RMSPROP vs the oracle's Keras RMSprop.
+    State, what it must leave alone and per-element bounds: tests/test_gpu_optim.py."""
     from clvae_amd.engine import FlatParams
     rng = np.random.default_rng(9)
     shapes = [('a/kernel', (200, 88)), ('a/bias', (88,)), ('c/recurrent_kernel', (88, 352))]
