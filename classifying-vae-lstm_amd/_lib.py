@@ -181,6 +181,11 @@ SIGNATURES = {
     "clv_vrnn_vary": (_i, [_i] * 8 + [_u64] + [_p] * 18 + [_f, _f] + [_p] * 3),
     "clv_vae_vary": (_i, [_i] * 8 + [_u64] + [_p] * 13 + [_f, _f] + [_p] * 3),
     "clv_take_frame": (_i, [_i64, _i, _i, _p, _p, _p, _p]),
+    "clv_vrnn_vary_latents": (_i, [_i] * 8 + [_u64] + [_p] * 18 + [_f, _f] + [_p] * 4),
+    "clv_vae_vary_latents": (_i, [_i] * 8 + [_u64] + [_p] * 13 + [_f, _f] + [_p] * 4),
+    "clv_vrnn_decode": (_i, [_i] * 7 + [_u64] + [_p] * 13 + [_f] + [_p] * 3),
+    "clv_vae_decode": (_i, [_i] * 7 + [_u64] + [_p] * 10 + [_f] + [_p] * 3),
+    "clv_lerp_rows": (_i, [_i64, _i64] + [_p] * 7),
     "clv_sigmoid_temper": (_i, [_i64, _p, _f, _p]),
     "clv_scale_temper": (_i, [_i64, _p, _f, _p]),
     "clv_label_fwd": (_i, [_i, _i, _p, _p, _i, _p, _p, _f, _p, _p, _p]),

@@ -17,7 +17,8 @@ import torch
 
 from .. import ops, sampling
 from ..engine import VaeEngine
-from ..engine_generate import clamp_roll, smc_args, smc_samples_numpy, temper_args, vary_samples_numpy
+from ..engine_generate import (clamp_roll, decode_latents_numpy, encode_latents_numpy, smc_args, smc_samples_numpy, temper_args,
+                               vary_samples_numpy)
 from ..initializers import init_weights
 from ..keras_like import Layer, Model, get_value
 
@@ -93,7 +94,7 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_p
 
 
 def vary_samples_device(model, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
-                        z_temperature=1.0, return_xhat=False):
+                        z_temperature=1.0, return_xhat=False, return_latents=False):
     """Re-decode pieces on the device (VaeEngine.vary): sources [N,T,88] binary frames, w_enc [N,C] the
     label the encoder conditions on, w_dec [N,C] the decoder's (None: w_enc, a variation of the piece under its own key;
     another label: key transfer).  x_hat of frame t = decoder([w_dec, xp, z_t]) with z_t from the z-encoder on [sources[t], w_enc] and xp the frame directly
@@ -102,9 +103,34 @@ def vary_samples_device(model, sources, w_enc, w_dec=None, x0=None, history='own
     the previous source frame ('source': the training forward pass).  clamp: uint8 [N,T,88] roll, row t constrains frame t;
     temperature, z_temperature as in generate_samples_device.  Returns [N,T,88] float64 (with return_xhat also the unclamped
     probabilities [N,T,88] float64).  ValueError for wrong shapes, an unknown history, a bool or out-of-range temperature,
-    and a w_dec without a w_enc."""
+    and a w_dec without a w_enc.  return_latents: the tuple (z, z_mean, z_log_var), each [N,T,L] float64, is
+    returned last; the frames and probabilities are those of the call without it, bit for bit."""
     return vary_samples_numpy(model.engine, sources, w_enc, w_dec, x0=x0, history=history, seed=seed, clamp=clamp,
-                              temperature=temperature, z_temperature=z_temperature, return_xhat=return_xhat)
+                              temperature=temperature, z_temperature=z_temperature, return_xhat=return_xhat,
+                              return_latents=return_latents)
+
+
+def encode_latents_device(model, sources, w_enc, seed=0, z_temperature=1.0):
+    """Encode whole pieces of any length to their latent paths on the device (VaeEngine.vary with its latents
+    stored): sources [N,T,88] binary frames, w_enc [N,C]; per frame the z-encoder on [sources[t], w_enc].
+    Returns (z, z_mean, z_log_var), each [N,T,L] float64: z = z_mean + exp(z_log_var / 2) * z_temperature * eps with the eps
+    of vary_samples_device(seed) -- the float32 value its decoder is fed; z_temperature=0 gives z = z_mean."""
+    return encode_latents_numpy(model.engine, sources, w_enc, seed=seed, z_temperature=z_temperature)
+
+
+def decode_latents_device(model, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
+                          return_xhat=False):
+    """Decode latent paths on the device (VaeEngine.decode_latents): z [N,T,L] (an encoder's, an edited or averaged one,
+    one read from a file), w_dec [N,C] the decoder's label.  The loop of vary_samples_device without its encoder: the
+    decoder's previous frame is x0 [N,88] (None: zeros) at t = 0, then its own SAMPLE (history='own') or history[:, t-1] of an
+    [N,T,88] array (teacher forcing).  No latent noise is drawn, so there is no z_temperature; the notes' uniforms are those
+    of vary_samples_device(seed), so decoding the z of a re-decoding under its arguments gives its frames bit for bit.
+    noise_rows [N] integers >= 0 (None: arange(N)): row n draws the uniforms of row noise_rows[n], so rows with equal entries
+    share them (common random numbers).  clamp, temperature as in vary_samples_device.  Returns [N,T,88] float64 (with
+    return_xhat also the unclamped probabilities).  ValueError for wrong shapes, a z whose last dimension is not L, a bool or
+    out-of-range temperature, negative noise_rows."""
+    return decode_latents_numpy(model.engine, z, w_dec, x0=x0, history=history, seed=seed, clamp=clamp,
+                                temperature=temperature, noise_rows=noise_rows, return_xhat=return_xhat)
 
 
 # --------------------------------------------------------------------------- #

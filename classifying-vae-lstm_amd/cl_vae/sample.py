@@ -8,12 +8,13 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, parser_for,  # noqa: E402
-                           temperature_kwargs)
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS,  # noqa: E402
+                           morph_kwargs, parser_for, temperature_kwargs)
 from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
+from clvae_amd.morph import morph  # noqa: E402
 from clvae_amd.vary import vary  # noqa: E402
 
 
@@ -102,6 +103,32 @@ class Sampler:
             write_sample(src, self.args.sample_dir, name + '_source', True)
         return list(rolls)
 
+    def morph_on_device(self, names):
+        """--morph K: consecutive picks are pairs (a, b): the t frames of two random test windows (of the key -c where
+        given) are encoded and K + 1 mixes of their latent paths and labels decoded; writes <run>_<j>_a.mid,
+        <run>_<j>_b.mid and <run>_<j>_morph<k>.mid, k = 0..K."""
+        pool = np.arange(len(self.data.x_test))
+        key = getattr(self.args, 'c', None)
+        if key is not None:
+            name_of = {idx: name for name, idx in self.data.key_map.items()}
+            pool = pool[np.array([name_of[k] for k in self.data.test_song_keys]) == key]
+        n = 2 * (len(names) // 2)
+        if not n or not len(pool):
+            return []
+        picks = [np.random.choice(pool) for _ in range(n)]
+        sources = np.stack([np.asarray(self.data.x_test[i]).reshape(self.args.t, -1) for i in picks])
+        ws = None if self.args.infer_w else np.vstack([to_categorical(self.data.test_song_keys[i], self.margs['n_classes'])
+                                                       for i in picks])
+        rolls = morph(self.model, sources[0::2], sources[1::2], steps=self.args.morph,
+                      w_a=None if ws is None else ws[0::2], w_b=None if ws is None else ws[1::2],
+                      seed=getattr(self.args, 'seed', 0), **morph_kwargs(self.args))
+        for j, rows in enumerate(rolls):
+            write_sample(sources[2 * j], self.args.sample_dir, '%s_%d_a' % (self.args.run_name, j), True)
+            write_sample(sources[2 * j + 1], self.args.sample_dir, '%s_%d_b' % (self.args.run_name, j), True)
+            for k, roll in enumerate(rows):
+                write_sample(roll, self.args.sample_dir, '%s_%d_morph%d' % (self.args.run_name, j, k), True)
+        return list(rolls)
+
 
 def make_sample(P, dec_model, w_enc_model, z_enc_model, args, margs):
     """One sample from explicit sub-models (the reference's helper, :8-19)."""
@@ -121,8 +148,9 @@ def voice_of(args):
 def on_device(args):
     """Where the frame loop runs: like the reference (host loop, np.random) for every -n unless --device_loop asks for
     the device-side loop (Philox noise: other samples for the same np.random.seed, so it is opt-in); --harmonize
-    and --vary always run there, and so does a sampling temperature (the parser refuses them next to --host_loop)."""
-    return bool(voice_of(args)) or bool(getattr(args, 'vary', False)) or bool(temperature_kwargs(args)) or (
+    --vary and --morph always run there, and so does a sampling temperature (the parser refuses them next to --host_loop)."""
+    return bool(voice_of(args)) or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
+        temperature_kwargs(args)) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
 
 
@@ -133,6 +161,8 @@ def sample(args):
         return s.harmonize_on_device(names)
     if getattr(args, 'vary', False):
         return s.vary_on_device(names)
+    if getattr(args, 'morph', None) is not None:
+        return s.morph_on_device(names)
     return s.many_on_device(names) if on_device(args) else [s.one(nm) for nm in names]
 
 
@@ -141,4 +171,5 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    sample(parser_for('cl_vae.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS).parse_args())
+    sample(parser_for('cl_vae.sample',
+                      DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS).parse_args())

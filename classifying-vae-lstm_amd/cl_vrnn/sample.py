@@ -8,12 +8,13 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, parser_for,  # noqa: E402
-                           temperature_kwargs)
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS,  # noqa: E402
+                           morph_kwargs, parser_for, temperature_kwargs)
 from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
+from clvae_amd.morph import morph  # noqa: E402
 from clvae_amd.vary import vary  # noqa: E402
 
 
@@ -38,6 +39,8 @@ def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None)
         return harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice, half_speed)
     if getattr(args, 'vary', False):
         return vary_samples(P, w_enc_model, args, margs, model, picks, label_of, half_speed)
+    if getattr(args, 'morph', None) is not None:
+        return morph_samples(P, w_enc_model, args, margs, model, picks, label_of, half_speed)
     if model is not None and len(picks):
         ws = [label_of(i) for i in picks]
         if args.infer_w:
@@ -104,6 +107,27 @@ def vary_samples(P, w_enc_model, args, margs, model, picks, label_of, half_speed
     return rolls
 
 
+def morph_samples(P, w_enc_model, args, margs, model, picks, label_of, half_speed):
+    """--morph K: consecutive picks are pairs (a, b); the t frames of both are encoded and K + 1 mixes of their latent paths
+    and labels decoded.  Writes <run>_<j>_a.mid, <run>_<j>_b.mid and <run>_<j>_morph<k>.mid, k = 0..K."""
+    picks = picks[:2 * (len(picks) // 2)]
+    if not len(picks):
+        return []
+    sources = np.stack([np.asarray(P.x_test[i])[:args.t] for i in picks])
+    ws = [label_of(i) for i in picks]
+    if args.infer_w:
+        ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in sources]
+    ws = np.vstack(ws)
+    rolls = morph(model, sources[0::2], sources[1::2], steps=args.morph, w_a=ws[0::2], w_b=ws[1::2],
+                  seed=getattr(args, 'seed', 0), **morph_kwargs(args))
+    for j, rows in enumerate(rolls):
+        write_sample(sources[2 * j], args.sample_dir, '%s_%d_a' % (args.run_name, j), half_speed)
+        write_sample(sources[2 * j + 1], args.sample_dir, '%s_%d_b' % (args.run_name, j), half_speed)
+        for k, roll in enumerate(rows):
+            write_sample(roll, args.sample_dir, '%s_%d_morph%d' % (args.run_name, j, k), half_speed)
+    return list(rolls)
+
+
 def sample(args):
     model, _, margs = M.load_model(args.model_file, optimizer='adam')
     dims = (margs['intermediate_dim'], margs['latent_dim'])
@@ -115,8 +139,9 @@ def sample(args):
     # --harmonize: windows of the seed's t frames and the t frames whose voice is kept
     P = PianoData(args.train_file, batch_size=1, seq_length=2 * args.t if voice else args.t, squeeze_x=False)
     # the reference's host loop (np.random) for every -n; --device_loop opts into the device-side loop (Philox noise), and
-    # a sampling temperature and --vary imply it (the parser refuses them next to --host_loop)
-    on_device = bool(voice) or bool(getattr(args, 'vary', False)) or bool(temperature_kwargs(args)) or (
+    # a sampling temperature, --vary and --morph imply it (the parser refuses them next to --host_loop)
+    on_device = bool(voice) or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
+        temperature_kwargs(args)) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
     return gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
 
@@ -126,4 +151,5 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    sample(parser_for('cl_vrnn.sample', DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS).parse_args())
+    sample(parser_for('cl_vrnn.sample',
+                      DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS).parse_args())

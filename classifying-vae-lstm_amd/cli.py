@@ -140,6 +140,14 @@ VARY_FLAGS = [
 ]
 
 
+# latent morphing (not in the reference): consecutive picks are pairs, K + 1 mixes of each (implies --device_loop)
+MORPH_FLAGS = [
+    Flag(('--morph',), int, None, 'interpolate between consecutive picks in latent space in this many steps: both pieces are '
+                                  'encoded, their latent paths and labels mixed at k / K, k = 0..K, and every mix decoded '
+                                  '(the posterior means are mixed unless --z_temperature is given; implies --device_loop)'),
+]
+
+
 def temperature_kwargs(args):
     """the sampling tools' --temperature / --z_temperature as keyword arguments of generate_samples_device / harmonize:
     empty where both are 1 (also for parsers without the flags)"""
@@ -147,10 +155,20 @@ def temperature_kwargs(args):
     return {} if T == 1.0 and Tz == 1.0 else dict(temperature=T, z_temperature=Tz)
 
 
+def morph_kwargs(args):
+    """--temperature / --z_temperature for morph(): the latent temperature stays at morph's default (0: the posterior means
+    are mixed) unless the flag was given a value other than 1"""
+    kw = dict(temperature=getattr(args, 'temperature', 1.0))
+    if getattr(args, 'z_temperature', 1.0) != 1.0:
+        kw['z_temperature'] = args.z_temperature
+    return kw
+
+
 class _Parser(argparse.ArgumentParser):
     """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles, a
     temperature other than 1 not with --host_loop (the host loop is the reference's and has none), --vary not with
-    --harmonize or --host_loop, --to_key / --vary_history only with --vary"""
+    --harmonize or --host_loop, --to_key / --vary_history only with --vary, --morph >= 1 and not with --harmonize, --vary or
+    --host_loop"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -169,6 +187,16 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--vary runs on the device loop: not with --host_loop')
         elif getattr(ns, 'to_key', None) is not None or getattr(ns, 'vary_history', 'own') != 'own':
             self.error('--to_key / --vary_history need --vary')
+        morph = getattr(ns, 'morph', None)
+        if morph is not None:
+            if morph < 1:
+                self.error('--morph must be >= 1')
+            if getattr(ns, 'harmonize', None):
+                self.error('--morph mixes whole pieces: not with --harmonize')
+            if getattr(ns, 'vary', False):
+                self.error('--morph decodes mixed latent paths: not with --vary')
+            if getattr(ns, 'host_loop', False):
+                self.error('--morph runs on the device loop: not with --host_loop')
         temper = temperature_kwargs(ns)
         if temper:
             from .engine_generate import temper_args

@@ -46,6 +46,9 @@ struct GenArgs {
   const float* w_dec;           // VR instances: [N,C] the decoder's label (w is then the encoder's)
   const float* x0;              // VR instances: [N,88] the frame before x_seed[:, 0], or null (zeros)
   int hist_source;              // VR instances: the decoder's history is the source frame, not the fed-back sample
+  float* zout;                  // ZO instances: [3,N,T,L] = (z_mean, z_log_var, z) of every frame
+  const float* z_in;            // ZG instances: [N,T,L] the latent path that replaces the encoder's
+  const int32_t* noise_rows;    // ZG instances: [N] the row whose uniforms sequence n draws, or null (n itself)
 };
 
 // slice_matvec with half the live registers: the h slice is consumed in two halves of 12 (the kernel is at its
@@ -95,11 +98,20 @@ __device__ __forceinline__ void frame_masks(const float* xbuf, int lane, float& 
 // frames are requested), the decoder's input-kernel prefetch reads a second frame buffer (x0, then the fed-back sample or,
 // with hist_source, the encoder's previous input), and the two roles form their gate bias from two labels.  clamp may be
 // null (every note free).  VR = false folds away.
-template <int GATE, bool ZW, bool CL, bool TP, bool VR = false>
+// ZO = true (with VR): latents out.  The lanes that form z in phase 2 also store (z_mean, z_log_var, z) of the
+// frame to zout, at a 32-bit offset from the sequence's uniform base.  ZO = false folds away.
+// ZG = true (with VR): latents in, the decode-only loop.  z_t is z_in[n, t, :], requested a frame early by the
+// lanes that would have drawn eps and parked in zbuf as it is; the encoder cell, the latent head, the staging of Kx_enc and
+// the encoder's label bias fold away (their pointers are null), and the encoder waves keep phase 4.  x_seed holds the given
+// HISTORY frames (with hist_source) or is null (the decoder runs on its own samples).  The uniforms are those of row
+// noise_rows[n].  Two barriers per frame are left: decoder cell | output head + sample; the z of frame t+1 is parked behind
+// the first of them, after the decoder cell of frame t has read zbuf.  ZG = false folds away.
+template <int GATE, bool ZW, bool CL, bool TP, bool VR = false, bool ZO = false, bool ZG = false>
 __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
+  static_assert((!ZO && !ZG) || (VR && CL && TP && !(ZO && ZG)), "ZO and ZG are variants of the VR instances");
   constexpr int GN_LQ = (ZW ? GN_LWIDE : GN_LMAX) / PK;
   extern __shared__ __attribute__((aligned(16))) float Kxl[];            // encoder input kernel [88][352], then Wo [88][88]
-  float* Wol = Kxl + LH * LG;
+  float* Wol = ZG ? Kxl : Kxl + LH * LG;                                 // ZG: no encoder, Wo alone
   __shared__ __attribute__((aligned(16))) float hb[2][2][PK * PKP];       // [chain][parity][sliced h]
   __shared__ __attribute__((aligned(16))) float zbuf[GN_LWIDE];
   __shared__ float zargs_l[2 * GN_LWIDE];
@@ -120,7 +132,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   const int n = blockIdx.x;
 
   // ---- one-time staging ----------------------------------------------------------------------------------------
-  {
+  if (!ZG) {
     const int nv = LH * LG / 4;
     const float4* src = reinterpret_cast<const float4*>(a.Kx_enc);
     float4* dst = reinterpret_cast<float4*>(Kxl);
@@ -136,8 +148,8 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   for (int i = tid; i < LH * LH; i += GN_NT) Wol[i] = a.Wo[i];
   for (int i = tid; i < 2 * 2 * PK * PKP; i += GN_NT) (&hb[0][0][0])[i] = 0.f;
   if (tid < GN_LWIDE) zbuf[tid] = 0.f;
-  if (tid < 128) xbuf[tid] = ((VR || a.S > 0) && tid < LH) ? a.x_seed[((size_t)n * (VR ? T : a.S)) * LH + tid] : 0.f;
-  if (tid < a.C) wbuf[tid] = a.w[(size_t)n * a.C + tid];
+  if (tid < 128) xbuf[tid] = ((VR || a.S > 0) && (!ZG || a.x_seed) && tid < LH) ? a.x_seed[((size_t)n * (VR ? T : a.S)) * LH + tid] : 0.f;
+  if (!ZG && tid < a.C) wbuf[tid] = a.w[(size_t)n * a.C + tid];
   if (CL && tid < LH) bo_l[tid] = a.bo[tid];
   if (CL && a.S == 0 && tid < LH)               // step 0's row
     cbuf[tid] = (VR && !a.clamp) ? (uint8_t)255 : a.clamp[(size_t)n * a.nsteps * LH + tid];
@@ -146,11 +158,12 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   __syncthreads();
 
   // recurrent kernel slice of this lane's unit (gate pairs), per-sequence bias W.K_w + b of its gate s
-  const float* U = enc ? a.U_enc : a.U_dec;
+  const float* U = (enc && !ZG) ? a.U_enc : a.U_dec;        // ZG: the encoder waves hold no recurrent kernel of their own
   const int zj = u_raw - LH;                                 // encoder role: surplus group index
-  const bool is_z = !ZW && enc && zj >= 0 && 2 * zj < L;     // group carries latents 2zj, 2zj+1
+  const bool is_zl = !ZW && enc && zj >= 0 && 2 * zj < L;    // group carries latents 2zj, 2zj+1
+  const bool is_z = !ZG && is_zl;                            // ... and their head columns
   const int lat = 2 * zj + (s & 1);
-  const bool lat_ok = is_z && lat < L;
+  const bool lat_ok = is_zl && lat < L;
   auto zcol = [&](int g) { const int l = 2 * zj + (g & 1); return l < L ? (g >> 1) * L + l : -1; };
   f2 Ur[PKK][2];
 #pragma unroll
@@ -165,9 +178,9 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     }
   float rb;
   {
-    const float* Kw = enc ? a.Kw_enc : a.Kw_dec;
-    const float* wl = (VR && !enc) ? wbuf_d : wbuf;
-    float acc = (enc ? a.b_enc : a.b_dec)[s * LH + u];
+    const float* Kw = (enc && !ZG) ? a.Kw_enc : a.Kw_dec;
+    const float* wl = (VR && (ZG || !enc)) ? wbuf_d : wbuf;
+    float acc = ((enc && !ZG) ? a.b_enc : a.b_dec)[s * LH + u];
     for (int c0 = 0; c0 < a.C; c0 += 8) {
       float kv[8];
 #pragma unroll
@@ -183,7 +196,10 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   // kernel, lane s takes latents s, s+4, ... -> RR[4q+g]; encoder, ZW: this lane group's head column -> RR[kk]
   constexpr int GN_RR = ZW ? 32 : 16;
   float RR[GN_RR];
-  if (enc) {
+  if (enc && ZG) {
+#pragma unroll
+    for (int kk = 0; kk < GN_RR; ++kk) RR[kk] = 0.f;
+  } else if (enc) {
 #pragma unroll
     for (int kk = 0; kk < GN_RR; ++kk) {
       const bool own = ZW && kk < PKK && u_raw < 2 * L;
@@ -200,7 +216,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
         RR[4 * q + g] = l < L ? v : 0.f;
       }
   }
-  if (enc) {
+  if (enc && !ZG) {
     if (!CL) bor = a.bo[u];
     const float bzv = a.bz[max(zcol(s), 0)];
     bzr = lat_ok ? bzv : 0.f;
@@ -214,8 +230,21 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   // slots where its lanes would otherwise wait at a barrier.
   const bool zdraw = ZW ? (tid < L) : (lat_ok && s < 2);            // lanes that own a latent's eps
   const uint64_t zidx = (uint64_t)n * L + (ZW ? tid : lat);
-  float e_cur = zdraw ? philox_normal_at(zidx, a.k0, a.k1, 0u, 0u) : 0.f;
-  if (TP) e_cur = a.Tz * e_cur;
+  // ZO / ZG: this sequence's latents, the lane's latent index clamped so that every lane's address is in bounds
+  const uint32_t zl = (uint32_t)min(max(ZW ? tid : lat, 0), L - 1), zlast = (uint32_t)T * (uint32_t)L - 1u;
+  float* zo_n = ZO ? a.zout + (size_t)n * T * L : nullptr;
+  const size_t zo_plane = ZO ? (size_t)a.N * T * L : 0;
+  const float* zi_n = ZG ? a.z_in + (size_t)n * T * L : nullptr;
+  const int nrow = (ZG && a.noise_rows) ? a.noise_rows[n] : n;             // the row whose uniforms this sequence draws
+  float e_cur;
+  if (ZG) {
+    e_cur = zi_n[zl];                                                       // z of frame 0, as it is
+    if (zdraw) zbuf[ZW ? (tid % PK) * GN_LQ + tid / PK : zpos] = e_cur;
+    __syncthreads();
+  } else {
+    e_cur = zdraw ? philox_normal_at(zidx, a.k0, a.k1, 0u, 0u) : 0.f;
+    if (TP) e_cur = a.Tz * e_cur;
+  }
   const uint32_t crow = CL ? ((uint32_t)n * (uint32_t)a.nsteps - (uint32_t)a.S) * (uint32_t)LH : 0u;   // clamp row of step 0
   float seed_carry = 0.f;                         // CL: the constraint byte requested one frame ago
   const float* src_n = VR ? a.x_seed + (size_t)n * T * LH : nullptr;      // VR: this sequence's source frames
@@ -238,10 +267,13 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     if (CL) seed_carry = seed_next;
     float src_next = 0.f;                          // VR: source frame t+1, the encoder's next input
     // 32-bit offset from this sequence's (uniform) base: no per-lane address pair to keep across the frame
-    if (VR && enc && writer && t + 1 < T) src_next = src_n[(uint32_t)(t + 1) * (uint32_t)LH + (uint32_t)u];
+    if (VR && (!ZG || a.x_seed) && enc && writer && t + 1 < T) src_next = src_n[(uint32_t)(t + 1) * (uint32_t)LH + (uint32_t)u];
     // ---- phase 1: encoder cell (enc waves) | decoder input-kernel rows from L2 (dec waves) ------------------------
     float xd = 0.f;
-    if (enc) {
+    if (ZG) e_cur = zi_n[min((uint32_t)(t + 1) * (uint32_t)L + zl, zlast)];   // frame t+1's z: unconditional, index clamped
+    if (ZG && enc) {
+      // no encoder: nothing to do before the decoder cell
+    } else if (enc) {
       float xv = rb;
       while (m0) {
         const int k = __builtin_ctzll(m0);
@@ -290,9 +322,11 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
         for (int q = 0; q < 4; ++q) xd = fmaf(vv[q], kv[q], xd);
       }
     }
-    step_barrier();
+    if (!ZG) step_barrier();
     // ---- phase 2: latent head + z ------------------------------------------------------------------------------------
-    if (!ZW) {          // surplus lane groups of the encoder's last wave
+    if (ZG) {
+      // the path is given: zbuf already holds z_t
+    } else if (!ZW) {          // surplus lane groups of the encoder's last wave
       if (enc && wave == GN_NW - 1) {
         f2 acc2[2];
 #pragma unroll
@@ -304,7 +338,14 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
         if (lat_ok && s < 2) {
           const float m = a.z_prior ? 0.f : ((s & 1) ? z[1] : z[0]);
           const float lv = a.z_prior ? 0.f : ((s & 1) ? z[3] : z[2]);
-          zbuf[zpos] = fmaf(expf(0.5f * lv), e_cur, m);
+          const float zv = fmaf(expf(0.5f * lv), e_cur, m);
+          zbuf[zpos] = zv;
+          if (ZO) {
+            const uint32_t zoff = (uint32_t)t * (uint32_t)L + zl;
+            zo_n[zoff] = m;
+            zo_n[zo_plane + zoff] = lv;
+            zo_n[2 * zo_plane + zoff] = zv;
+          }
         }
       }
       step_barrier();
@@ -326,7 +367,14 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
       step_barrier();
       if (tid < L) {
         const float m = a.z_prior ? 0.f : zargs_l[tid], lv = a.z_prior ? 0.f : zargs_l[L + tid];
-        zbuf[(tid % PK) * GN_LQ + tid / PK] = fmaf(expf(0.5f * lv), e_cur, m);
+        const float zv = fmaf(expf(0.5f * lv), e_cur, m);
+        zbuf[(tid % PK) * GN_LQ + tid / PK] = zv;
+        if (ZO) {
+          const uint32_t zoff = (uint32_t)t * (uint32_t)L + zl;
+          zo_n[zoff] = m;
+          zo_n[zo_plane + zoff] = lv;
+          zo_n[2 * zo_plane + zoff] = zv;
+        }
       }
       step_barrier();
     }
@@ -360,15 +408,15 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
       hb[1][cur ^ 1][hslot] = h;
     } else {
       // encoder waves are idle here: draw this frame's Bernoulli uniforms and the next frame's latent noise
-      if (writer) u_cur = philox_uniform_at((uint64_t)n * LH + u, a.k0, a.k1, 1u, (uint32_t)t);
+      if (writer) u_cur = philox_uniform_at((uint64_t)nrow * LH + u, a.k0, a.k1, 1u, (uint32_t)t);
       // CL: a clamped note's uniform (drawn and discarded) becomes 2 (forced off: never <= p) or -1 (forced on: always
       // <= p, p in [0, 1]), so phase 4 samples the constraint with no extra work; any other byte leaves the draw
       if (CL && writer && t >= a.S) {
         const uint32_t cb = cbuf[u];
         u_cur = cb == 0u ? 2.f : (cb == 1u ? -1.f : u_cur);
       }
-      if (zdraw) e_cur = philox_normal_at(zidx, a.k0, a.k1, 0u, (uint32_t)(t + 1));
-      if (TP) e_cur = a.Tz * e_cur;
+      if (!ZG && zdraw) e_cur = philox_normal_at(zidx, a.k0, a.k1, 0u, (uint32_t)(t + 1));
+      if (!ZG && TP) e_cur = a.Tz * e_cur;
     }
     step_barrier();
     // ---- phase 4: output head, Bernoulli sample, next input frame (enc waves) ------------------------------------
@@ -402,6 +450,8 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
           xbuf[u] = (t + 1 < a.S) ? seed_next : xs;
         }
       }
+      // ZG: park frame t+1's z; the decoder cell of frame t read zbuf before the barrier above
+      if (ZG && zdraw) zbuf[ZW ? (tid % PK) * GN_LQ + tid / PK : zpos] = e_cur;
     }
     step_barrier();
   }
@@ -457,9 +507,10 @@ int vrnn_vary_launch(int N, int T, int D, int H, int L, int C, int gate_act, int
                      const float* Kw_enc, const float* b_enc, const float* U_enc, const float* Wz, const float* bz,
                      const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec, const float* U_dec,
                      const float* Wo, const float* bo, const uint8_t* clamp, float inv_T, float Tz, float* Xs, float* xhat,
-                     void* stream) {
+                     float* zout, void* stream) {
   using namespace clv;
   if (!clv_vrnn_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
+  if (zout && (uint64_t)N * T * L > UINT32_MAX) return CLV_EINVAL;             // the latents are addressed in 32 bits
   if (gate_act != CLV_GATE_HARD_SIGMOID && gate_act != CLV_GATE_SIGMOID) return CLV_EINVAL;
   if (!temper_factor_ok(inv_T, false) || !temper_factor_ok(Tz, true)) return CLV_EINVAL;
   if (!sources || !w_enc || !w_dec || !Kx_enc || !Kw_enc || !b_enc || !U_enc || !Wz || !bz || !Kz || !Kw_dec || !b_dec ||
@@ -471,16 +522,49 @@ int vrnn_vary_launch(int N, int T, int D, int H, int L, int C, int gate_act, int
   hipStream_t s = (hipStream_t)stream;
   GenArgs a{N, 0, T, L, C, 0, Kx_dec != nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), sources, w_enc,
             Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp, inv_T, Tz,
-            w_dec, x0, hist_source != 0};
+            w_dec, x0, hist_source != 0, zout, nullptr, nullptr};
   const size_t lds = (size_t)(LH * LG + LH * LH) * sizeof(float);
   const bool hard = gate_act == CLV_GATE_HARD_SIGMOID, wide = L > GN_LMAX;
   void (*kern)(GenArgs) =
-      hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true, true, true>
-                   : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true, true, true>)
-           : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true, true, true>
-                   : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true, true, true>);
+      zout ? (hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true, true, true, true>
+                           : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true, true, true, true>)
+                   : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true, true, true, true>
+                           : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true, true, true, true>))
+           : (hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true, true, true>
+                           : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true, true, true>)
+                   : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true, true, true>
+                           : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true, true, true>));
   if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 156 * 1024)) return e;
-  ProfScope p("vrnn_vary", s);
+  ProfScope p(zout ? "vrnn_vary_latents" : "vrnn_vary", s);
+  hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
+  return launch_status();
+}
+
+// decoding a given latent path: the ZG instances.  No encoder: its weights, label and sources are absent
+int vrnn_decode_launch(int N, int T, int D, int H, int L, int C, int gate_act, uint64_t seed, const float* z_in,
+                       const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
+                       const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec, const float* U_dec,
+                       const float* Wo, const float* bo, const uint8_t* clamp, float inv_T, float* Xs, float* xhat,
+                       void* stream) {
+  using namespace clv;
+  if (!clv_vrnn_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
+  if (gate_act != CLV_GATE_HARD_SIGMOID && gate_act != CLV_GATE_SIGMOID) return CLV_EINVAL;
+  if (!temper_factor_ok(inv_T, false)) return CLV_EINVAL;
+  if (!z_in || !w_dec || !Kz || !Kw_dec || !b_dec || !U_dec || !Wo || !bo || !Xs) return CLV_EINVAL;
+  // the kernel addresses the latents, the roll and a sequence's history frames in 32 bits
+  if ((uint64_t)N * T * L > UINT32_MAX || (uint64_t)N * T * LH > UINT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  GenArgs a{N, 0, T, L, C, 0, Kx_dec != nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), history, nullptr,
+            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp,
+            inv_T, 1.f, w_dec, x0, history != nullptr, nullptr, z_in, noise_rows};
+  const size_t lds = (size_t)(LH * LH) * sizeof(float);
+  const bool hard = gate_act == CLV_GATE_HARD_SIGMOID, wide = L > GN_LMAX;
+  void (*kern)(GenArgs) =
+      hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true, true, true, false, true>
+                   : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true, true, true, false, true>)
+           : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true, true, true, false, true>
+                   : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true, true, true, false, true>);
+  ProfScope p("vrnn_decode", s);
   hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
   return launch_status();
 }
@@ -532,5 +616,27 @@ extern "C" int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_
                              float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream) {
   return vrnn_vary_launch(N, T, D, H, L, C, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc,
                           U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, inv_temperature, z_temperature, Xs,
-                          xhat, stream);
+                          xhat, nullptr, stream);
+}
+
+extern "C" int clv_vrnn_vary_latents(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
+                                     const float* sources, const float* x0, const float* w_enc, const float* w_dec,
+                                     const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                                     const float* Wz, const float* bz,
+                                     const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                                     const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                                     float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout,
+                                     void* stream) {
+  return vrnn_vary_launch(N, T, D, H, L, C, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc,
+                          U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, inv_temperature, z_temperature, Xs,
+                          xhat, zout, stream);
+}
+
+extern "C" int clv_vrnn_decode(int N, int T, int D, int H, int L, int C, int gate_act, uint64_t seed, const float* z_in,
+                               const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
+                               const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                               const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                               float inv_temperature, float* Xs, float* xhat, void* stream) {
+  return vrnn_decode_launch(N, T, D, H, L, C, gate_act, seed, z_in, x0, history, w_dec, noise_rows, Kx_dec, Kz, Kw_dec, b_dec,
+                            U_dec, Wo, bo, clamp, inv_temperature, Xs, xhat, stream);
 }

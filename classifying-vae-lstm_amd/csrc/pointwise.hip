@@ -481,9 +481,31 @@ __global__ void take_frame_kernel(int64_t n, int T, int D, const float* src, con
   out[i] = src[(r * T + c) * D + j];
 }
 
+// out[r, :] = (1 - alpha[r]) a[ia[r], :] + alpha[r] b[ib[r], :] as two fused multiply-adds, exact at alpha = 0 and alpha = 1
+// (DESIGN.md 15); one thread per element, rows of n elements
+__global__ void lerp_rows_kernel(int64_t total, int64_t n, const float* a, const int32_t* ia, const float* b, const int32_t* ib,
+                                 const float* alpha, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int64_t r = i / n, j = i - r * n;
+  const float al = alpha[r];
+  const float av = a[(int64_t)ia[r] * n + j], bv = b[(int64_t)ib[r] * n + j];
+  out[i] = fmaf(al, bv, fmaf(-al, av, av));
+}
+
 }  // namespace clv
 
 using namespace clv;
+
+extern "C" int clv_lerp_rows(int64_t R, int64_t n, const float* a, const int32_t* ia, const float* b, const int32_t* ib,
+                             const float* alpha, float* out, void* stream) {
+  if (R <= 0 || n <= 0 || !a || !ia || !b || !ib || !alpha || !out) return CLV_EINVAL;
+  if (R > INT64_MAX / n || (R * n + 255) / 256 > (int64_t)INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("lerp_rows", s);
+  hipLaunchKernelGGL(lerp_rows_kernel, dim3((unsigned)((R * n + 255) / 256)), dim3(256), 0, s, R * n, n, a, ia, b, ib, alpha, out);
+  return launch_status();
+}
 
 extern "C" int clv_take_frame(int64_t n, int T, int D, const float* src, const int32_t* step_dev, float* out, void* stream) {
   if (n <= 0 || T <= 0 || D <= 0 || n % D != 0 || !src || !step_dev || !out) return CLV_EINVAL;

@@ -41,6 +41,9 @@ struct VaeGenArgs {
   const float* w_dec;           // VR instance: [N,C] the decoder's label (w is then the z-encoder's)
   const float* x0;              // VR instance: [N,88] the frame before x_seed[:, 0], or null (zeros)
   int hist_source;              // VR instance: the decoder's history is the source frame, not the fed-back sample
+  float* zout;                  // ZO instance: [3,N,T,L] = (z_mean, z_log_var, z) of every frame
+  const float* z_in;            // ZG instance: [N,T,L] the latent path that replaces the z-encoder's
+  const int32_t* noise_rows;    // ZG instance: [N] the row whose uniforms sequence n draws, or null (n itself)
 };
 
 // sum over the notes that are on (two scalar masks: inputs 0..63 / 64..87) of row n of an LDS-resident [88][88] kernel,
@@ -71,11 +74,19 @@ __device__ __forceinline__ float gather_rows(const float* Kl, int j, unsigned lo
 // reads source frame t (requested a frame early by the writer lanes), the decoder's history is the frame directly before t
 // as in training -- x0, then the fed-back sample or, with hist_source, source frame t-1 -- and the two hidden layers take
 // their label share from two labels.  clamp may be null (every note free).  VR = false folds away.
-template <bool CL, bool TP, bool VR = false>
+// ZO = true (with VR): latents out: the lanes that form z also store (z_mean, z_log_var, z) of the frame to
+// zout, at a 32-bit offset from the sequence's uniform base.  ZO = false folds away.
+// ZG = true (with VR): latents in, the decode-only loop.  z_t is z_in[n, t, :], requested a frame early and
+// parked in zbuf as it is; the z-encoder's hidden layer and the latent head fold away with their weights (null pointers, no
+// LDS copy of K_h).  x_seed holds the given HISTORY frames (with hist_source) or is null (the decoder runs on its own
+// samples); the uniforms are those of row noise_rows[n].  Two barriers per frame are left: the decoder's hidden layer |
+// output layer + sample; the z of frame t+1 is parked behind the first, after the hidden layer of frame t has read zbuf.
+template <bool CL, bool TP, bool VR = false, bool ZO = false, bool ZG = false>
 __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
+  static_assert((!ZO && !ZG) || (VR && CL && TP && !(ZO && ZG)), "ZO and ZG are variants of the VR instance");
   extern __shared__ __attribute__((aligned(16))) float vg_lds[];
-  float* Khl = vg_lds;                        // [88][88] frame rows of the z-encoder's hidden kernel
-  float* Kdl = Khl + LH * LH;                 // [88][88] history rows of the decoder's hidden kernel (has_xp)
+  float* Khl = vg_lds;                        // [88][88] frame rows of the z-encoder's hidden kernel (ZG: absent)
+  float* Kdl = ZG ? vg_lds : Khl + LH * LH;   // [88][88] history rows of the decoder's hidden kernel (has_xp)
   float* Kdz = Kdl + LH * LH;                 // [VG_LMAX][88] latent rows of the decoder's hidden kernel
   __shared__ __attribute__((aligned(16))) float hbuf[2][PK * PKP];      // sliced hidden vectors: z-encoder's, decoder's
   __shared__ float zbuf[VG_LMAX];
@@ -88,22 +99,28 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   const int L = a.L, n = blockIdx.x;
   const bool writer = s == 0 && o_raw < LH;
   const int hslot = PKP * (o / PKK) + (o % PKK);
+  // ZO / ZG: this sequence's latents, the slot's latent index clamped so that every lane's address is in bounds
+  const uint32_t zl = (uint32_t)min(o_raw >> 1, L - 1), zlast = (uint32_t)a.nsteps * (uint32_t)L - 1u;
+  float* zo_n = ZO ? a.zout + (size_t)n * a.nsteps * L : nullptr;
+  const size_t zo_plane = ZO ? (size_t)a.N * a.nsteps * L : 0;
+  const float* zi_n = ZG ? a.z_in + (size_t)n * a.nsteps * L : nullptr;
+  const int nrow = (ZG && a.noise_rows) ? a.noise_rows[n] : n;           // the row whose uniforms this sequence draws
 
   // ---- one-time staging ---------------------------------------------------------------------------------------------
   for (int i = tid; i < LH * LH; i += VG_NT) {
-    Khl[i] = a.Kh[i];
+    if (!ZG) Khl[i] = a.Kh[i];
     Kdl[i] = a.has_xp ? a.Kd[(size_t)a.C * LH + i] : 0.f;
   }
   for (int i = tid; i < VG_LMAX * LH; i += VG_NT)
     Kdz[i] = i < L * LH ? a.Kd[(size_t)(a.C + (a.has_xp ? LH : 0)) * LH + i] : 0.f;
   for (int i = tid; i < 2 * PK * PKP; i += VG_NT) (&hbuf[0][0])[i] = 0.f;
-  if (tid < VG_LMAX) zbuf[tid] = 0.f;
+  if (tid < VG_LMAX) zbuf[tid] = (ZG && tid < L) ? zi_n[tid] : 0.f;       // ZG: z of frame 0, as it is
   if (tid < 128) {
-    xbuf[0][tid] = tid < LH ? a.x_seed[(size_t)n * (VR ? a.nsteps : 1) * LH + tid] : 0.f;
+    xbuf[0][tid] = (tid < LH && (!ZG || a.x_seed)) ? a.x_seed[(size_t)n * (VR ? a.nsteps : 1) * LH + tid] : 0.f;
     xbuf[1][tid] = xbuf[0][tid];
     if (VR) xhis[tid] = (a.x0 && tid < LH) ? a.x0[(size_t)n * LH + tid] : 0.f;
   }
-  if (tid < VG_CMAX) wbuf[tid] = tid < a.C ? a.w[(size_t)n * a.C + tid] : 0.f;
+  if (!ZG && tid < VG_CMAX) wbuf[tid] = tid < a.C ? a.w[(size_t)n * a.C + tid] : 0.f;
   if (VR && tid < VG_CMAX) wbuf_d[tid] = tid < a.C ? a.w_dec[(size_t)n * a.C + tid] : 0.f;
   // head kernel: slot c < 2L owns column c; the pairs (mean_l, log_var_l) sit in neighbouring slots 2l, 2l+1 so that the
   // log-variance reaches the mean's lanes by one DPP row shift (the kernel's own column order is [means | log-variances])
@@ -112,15 +129,15 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   float Kzr[PKK], Kor[PKK];
 #pragma unroll
   for (int kk = 0; kk < PKK; ++kk) {
-    Kzr[kk] = zslot ? a.Kz[(size_t)(PKK * s + kk) * 2 * L + zc] : 0.f;
+    Kzr[kk] = (!ZG && zslot) ? a.Kz[(size_t)(PKK * s + kk) * 2 * L + zc] : 0.f;
     Kor[kk] = a.Ko[(size_t)(PKK * s + kk) * LH + o];
   }
-  const float bzr = zslot ? a.bz[zc] : 0.f, bor = a.bo[o];
+  const float bzr = (!ZG && zslot) ? a.bz[zc] : 0.f, bor = a.bo[o];
   __syncthreads();
   // the label's share of both hidden layers (+ bias): constant over the sequence
-  float ch = a.bh[o], cd = a.bd[o];
+  float ch = ZG ? 0.f : a.bh[o], cd = a.bd[o];
   for (int c = 0; c < a.C; ++c) {
-    ch = fmaf(wbuf[c], a.Kh[(size_t)(LH + c) * LH + o], ch);
+    if (!ZG) ch = fmaf(wbuf[c], a.Kh[(size_t)(LH + c) * LH + o], ch);
     cd = fmaf((VR ? wbuf_d : wbuf)[c], a.Kd[(size_t)c * LH + o], cd);
   }
   // notes of the current input frame and of the one before it (the decoder's history lags: cl_vae/model.py:38-40)
@@ -137,22 +154,27 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
 
   for (int t = 0; t < a.nsteps; ++t) {
     // this frame's noise, drawn before anything depends on it
-    const float u_cur = writer ? philox_uniform_at((uint64_t)n * LH + o, a.k0, a.k1, 1u, (uint32_t)t) : 2.f;
+    const float u_cur = writer ? philox_uniform_at((uint64_t)nrow * LH + o, a.k0, a.k1, 1u, (uint32_t)t) : 2.f;
     // this frame's constraint, requested three barriers before phase 4 uses it (2: free)
     const uint32_t cb = (CL && writer && !(VR && !a.clamp)) ? (uint32_t)a.clamp[((size_t)n * a.nsteps + t) * LH + o] : 2u;
     // VR: source frame t+1, the z-encoder's next input, requested a whole frame before it is published
-    const float src_next = (VR && writer && t + 1 < a.nsteps) ? a.x_seed[((size_t)n * a.nsteps + t + 1) * LH + o] : 0.f;
+    const float src_next = (VR && (!ZG || a.x_seed) && writer && t + 1 < a.nsteps) ? a.x_seed[((size_t)n * a.nsteps + t + 1) * LH + o] : 0.f;
     const bool zdraw = s == 0 && zslot && !(o_raw & 1);                 // the mean slot of latent l = o_raw / 2
-    float eps = zdraw ? philox_normal_at((uint64_t)n * L + (o_raw >> 1), a.k0, a.k1, 0u, (uint32_t)t) : 0.f;
-    if (TP) eps = a.Tz * eps;
+    float eps;
+    if (ZG) {
+      eps = zi_n[min((uint32_t)(t + 1) * (uint32_t)L + zl, zlast)];      // frame t+1's z: unconditional, index clamped
+    } else {
+      eps = zdraw ? philox_normal_at((uint64_t)n * L + (o_raw >> 1), a.k0, a.k1, 0u, (uint32_t)t) : 0.f;
+      if (TP) eps = a.Tz * eps;
+    }
     // 1. z-encoder hidden layer: relu(x_prev . K_h[frame rows] + (w . K_h[label rows] + b_h))
-    {
+    if (!ZG) {
       const float h = fmaxf(ch + gather_rows(Khl, o, cur0, cur1), 0.f);
       if (writer) hbuf[0][hslot] = h;
     }
-    step_barrier();
+    if (!ZG) step_barrier();
     // 2. latent head + sample
-    {
+    if (!ZG) {
       float hv[PKP];
       load_hslice(&hbuf[0][PKP * s], hv);
       float acc0 = 0.f, acc1 = 0.f;
@@ -162,10 +184,17 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
       const float lv = dpp_mov<0x104>(za);                             // row_shl:4: the next slot's value
       if (zdraw) {
         const float mean = a.z_prior ? 0.f : za, lvv = a.z_prior ? 0.f : lv;
-        zbuf[o_raw >> 1] = fmaf(__expf(0.5f * lvv), eps, mean);
+        const float zv = fmaf(__expf(0.5f * lvv), eps, mean);
+        zbuf[o_raw >> 1] = zv;
+        if (ZO) {
+          const uint32_t zoff = (uint32_t)t * (uint32_t)L + zl;
+          zo_n[zoff] = mean;
+          zo_n[zo_plane + zoff] = lvv;
+          zo_n[2 * zo_plane + zoff] = zv;
+        }
       }
     }
-    step_barrier();
+    if (!ZG) step_barrier();
     // 3. decoder hidden layer: relu(w . K_d[label rows] + b_d + x_prev_t . K_d[history rows] + z . K_d[latent rows])
     {
       float acc = cd + (a.has_xp ? gather_rows(Kdl, o, his0, his1) : 0.f);
@@ -193,6 +222,8 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
         xbuf[(t + 1) & 1][o] = VR ? src_next : xs;
         if (VR) xhis[o] = xs;               // read after this frame's last barrier, written again three barriers later
       }
+      // ZG: park frame t+1's z; the hidden layer of frame t read zbuf before the barrier above
+      if (ZG && zdraw) zbuf[o_raw >> 1] = eps;
     }
     step_barrier();
     {
@@ -238,18 +269,41 @@ int vae_generate_launch(int N, int nsteps, int D, int H, int L, int C, int use_x
 int vae_vary_launch(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
                     const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
                     const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
-                    const float* bo, const uint8_t* clamp, float inv_T, float Tz, float* Xs, float* xhat, void* stream) {
+                    const float* bo, const uint8_t* clamp, float inv_T, float Tz, float* Xs, float* xhat, float* zout,
+                    void* stream) {
   using namespace clv;
   if (!clv_vae_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
+  if (zout && (uint64_t)N * T * L > UINT32_MAX) return CLV_EINVAL;             // the latents are addressed in 32 bits
   if (!temper_factor_ok(inv_T, false) || !temper_factor_ok(Tz, true)) return CLV_EINVAL;
   if (!sources || !w_enc || !w_dec || !Kh || !bh || !Kz || !bz || !Kd || !bd || !Ko || !bo || !Xs) return CLV_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   VaeGenArgs a{N, T, L, C, 0, use_x_prev != 0, (uint32_t)seed, (uint32_t)(seed >> 32), sources, w_enc, Kh, bh, Kz, bz, Kd, bd,
-               Ko, bo, Xs, xhat, clamp, inv_T, Tz, w_dec, x0, hist_source != 0};
+               Ko, bo, Xs, xhat, clamp, inv_T, Tz, w_dec, x0, hist_source != 0, zout, nullptr, nullptr};
   const size_t lds = (size_t)(2 * LH * LH + VG_LMAX * LH) * sizeof(float);
-  void (*kern)(VaeGenArgs) = vae_generate_kernel<true, true, true>;
+  void (*kern)(VaeGenArgs) = zout ? vae_generate_kernel<true, true, true, true> : vae_generate_kernel<true, true, true>;
   if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 96 * 1024)) return e;
-  ProfScope p("vae_vary", s);
+  ProfScope p(zout ? "vae_vary_latents" : "vae_vary", s);
+  hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
+  return launch_status();
+}
+
+// decoding a given latent path: the ZG instance.  No z-encoder: its weights, label and sources are absent
+int vae_decode_launch(int N, int T, int D, int H, int L, int C, int use_x_prev, uint64_t seed, const float* z_in,
+                      const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows, const float* Kd,
+                      const float* bd, const float* Ko, const float* bo, const uint8_t* clamp, float inv_T, float* Xs,
+                      float* xhat, void* stream) {
+  using namespace clv;
+  if (!clv_vae_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
+  if (!temper_factor_ok(inv_T, false)) return CLV_EINVAL;
+  if (!z_in || !w_dec || !Kd || !bd || !Ko || !bo || !Xs) return CLV_EINVAL;
+  if ((uint64_t)N * T * L > UINT32_MAX || (uint64_t)N * T * LH > UINT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  VaeGenArgs a{N, T, L, C, 0, use_x_prev != 0, (uint32_t)seed, (uint32_t)(seed >> 32), history, nullptr, nullptr, nullptr,
+               nullptr, nullptr, Kd, bd, Ko, bo, Xs, xhat, clamp, inv_T, 1.f, w_dec, x0, history != nullptr, nullptr, z_in,
+               noise_rows};
+  const size_t lds = (size_t)(LH * LH + VG_LMAX * LH) * sizeof(float);
+  void (*kern)(VaeGenArgs) = vae_generate_kernel<true, true, true, false, true>;
+  ProfScope p("vae_decode", s);
   hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
   return launch_status();
 }
@@ -288,5 +342,23 @@ extern "C" int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_
                             const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
                             float z_temperature, float* Xs, float* xhat, void* stream) {
   return vae_vary_launch(N, T, D, H, L, C, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko,
-                         bo, clamp, inv_temperature, z_temperature, Xs, xhat, stream);
+                         bo, clamp, inv_temperature, z_temperature, Xs, xhat, nullptr, stream);
+}
+
+extern "C" int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
+                                    const float* sources, const float* x0, const float* w_enc, const float* w_dec,
+                                    const float* Kh, const float* bh, const float* Kz, const float* bz, const float* Kd,
+                                    const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
+                                    float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout,
+                                    void* stream) {
+  return vae_vary_launch(N, T, D, H, L, C, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko,
+                         bo, clamp, inv_temperature, z_temperature, Xs, xhat, zout, stream);
+}
+
+extern "C" int clv_vae_decode(int N, int T, int D, int H, int L, int C, int use_x_prev, uint64_t seed, const float* z_in,
+                              const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
+                              const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
+                              float inv_temperature, float* Xs, float* xhat, void* stream) {
+  return vae_decode_launch(N, T, D, H, L, C, use_x_prev, seed, z_in, x0, history, w_dec, noise_rows, Kd, bd, Ko, bo, clamp,
+                           inv_temperature, Xs, xhat, stream);
 }

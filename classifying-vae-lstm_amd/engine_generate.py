@@ -189,16 +189,127 @@ def vary_args(sources, w_enc, w_dec, x0, history, clamp, D, C, device):
 
 
 def vary_samples_numpy(engine, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
-                       z_temperature=1.0, return_xhat=False):
-    """vary_samples_device of both families: engine.vary on host arrays -> [N, T, D] float64 (and x_hat, float64)"""
+                       z_temperature=1.0, return_xhat=False, return_latents=False):
+    """vary_samples_device of both families: engine.vary on host arrays -> [N, T, D] float64 (and x_hat, float64; with
+    return_latents also (z, z_mean, z_log_var), each [N, T, L] float64, last)"""
     temper_args(temperature, z_temperature)
     cfg, d = engine.cfg, engine.device
     sources, w_enc, w_dec, x0, clamp, _ = vary_args(sources, w_enc, w_dec, x0, history, clamp, cfg['D'], cfg['C'], d)
     xhat = torch.zeros_like(sources) if return_xhat else None
+    kw = {}
+    if return_latents:
+        kw['zout'] = torch.zeros(3, sources.shape[0], sources.shape[1], cfg['L'], dtype=torch.float32, device=d)
     Xs = engine.vary(sources, w_enc, w_dec, x0=x0, history=history, seed=int(seed), clamp=clamp, temperature=temperature,
-                     z_temperature=z_temperature, xhat_out=xhat)
+                     z_temperature=z_temperature, xhat_out=xhat, **kw)
+    out = [Xs.cpu().numpy().astype(np.float64)]
+    if return_xhat:
+        out.append(xhat.cpu().numpy().astype(np.float64))
+    if return_latents:
+        zo = kw['zout'].cpu().numpy().astype(np.float64)
+        out.append((zo[2], zo[0], zo[1]))
+    return out[0] if len(out) == 1 else tuple(out)
+
+
+def encode_latents_numpy(engine, sources, w_enc, seed=0, z_temperature=1.0):
+    """encode_latents_device of both families: the latents of engine.vary's loop on host arrays ->
+    (z, z_mean, z_log_var), each [N, T, L] float64.  The encoder sees only the sources and w_enc, so the decoder half of
+    the launch (run under w_enc, free) does not reach them."""
+    return vary_samples_numpy(engine, sources, w_enc, seed=seed, z_temperature=z_temperature, return_latents=True)[1]
+
+
+def decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, C, device):
+    """Validate the arguments of a decoding and return them as contiguous device tensors: (z [N, T, L] fp32,
+    w_dec [N, C], x0 [N, D] or None, history [N, T, D] or None ('own'), the roll or None, noise_rows [N] int32 or None).
+    numpy or torch in; ValueError for a wrong shape, a z whose last dimension is not L, a history that is neither 'own' nor
+    an [N, T, D] array, and noise_rows that are not N integers >= 0."""
+    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32))
+                   ).to(dtype=torch.float32, device=device).contiguous()
+    if z is None or w_dec is None:
+        raise ValueError("decoding needs a latent path z and the decoder's label w_dec")
+    z = t(z)
+    if z.dim() != 3 or z.shape[0] < 1 or z.shape[1] < 1 or z.shape[2] != L:
+        raise ValueError("z must be [N, T, %d] with N, T >= 1, got shape %s" % (L, tuple(z.shape)))
+    N, T = int(z.shape[0]), int(z.shape[1])
+    w_dec = t(w_dec)
+    if tuple(w_dec.shape) != (N, C):
+        raise ValueError("w_dec must have shape %s, got %s" % ((N, C), tuple(w_dec.shape)))
+    if x0 is not None:
+        x0 = t(x0)
+        if tuple(x0.shape) != (N, D):
+            raise ValueError("x0 must have shape %s, got %s" % ((N, D), tuple(x0.shape)))
+    if isinstance(history, str):
+        if history != 'own':
+            raise ValueError("history must be 'own' or an [N, T, %d] array, got %r" % (D, history))
+        history = None
+    else:
+        if history is None:
+            raise ValueError("history must be 'own' or an [N, T, %d] array, got None" % D)
+        history = t(history)
+        if tuple(history.shape) != (N, T, D):
+            raise ValueError("history must have shape %s, got %s" % ((N, T, D), tuple(history.shape)))
+    if noise_rows is not None:
+        nr = noise_rows.cpu().numpy() if isinstance(noise_rows, torch.Tensor) else np.asarray(noise_rows)
+        if nr.dtype == np.bool_ or not np.issubdtype(nr.dtype, np.integer) or nr.shape != (N,):
+            raise ValueError("noise_rows must be %d integers, got dtype %s shape %s" % (N, nr.dtype, nr.shape))
+        if nr.min() < 0 or nr.max() >= 2 ** 31:
+            raise ValueError("noise_rows must lie in [0, 2^31), got [%d, %d]" % (nr.min(), nr.max()))
+        noise_rows = torch.from_numpy(np.ascontiguousarray(nr, dtype=np.int32)).to(device)
+    return z, w_dec, x0, history, clamp_roll(clamp, N, T, D, device), noise_rows
+
+
+def decode_temper(temperature):
+    """the note temperature of a decoding: temper_args without a latent temperature (the path is given) -> inv_T"""
+    t = temper_args(temperature, 1.0)
+    return 1.0 if t is None else t[0]
+
+
+def decode_latents_numpy(engine, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
+                         return_xhat=False):
+    """decode_latents_device of both families: engine.decode_latents on host arrays -> [N, T, D] float64 (and x_hat, float64)"""
+    decode_temper(temperature)
+    cfg, d = engine.cfg, engine.device
+    z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, cfg['D'], cfg['L'],
+                                                        cfg['C'], d)
+    xhat = torch.zeros(z.shape[0], z.shape[1], cfg['D'], dtype=torch.float32, device=d) if return_xhat else None
+    Xs = engine.decode_latents(z, w_dec, x0=x0, history='own' if hist is None else hist, seed=int(seed), clamp=clamp,
+                       temperature=temperature, noise_rows=noise_rows, xhat_out=xhat)
     Xs = Xs.cpu().numpy().astype(np.float64)
     return (Xs, xhat.cpu().numpy().astype(np.float64)) if return_xhat else Xs
+
+
+def lerp_rows(a, ia, b, ib, alpha):
+    """out [R, n] = (1 - alpha[r]) a[ia[r]] + alpha[r] b[ib[r]] on the device (clv_lerp_rows: two fmas, exact at both ends);
+    a [Ra, n], b [Rb, n] float32 device tensors, ia, ib, alpha sequences of R entries"""
+    d = a.device
+    a, b = a.contiguous(), b.contiguous()
+    ia, ib = np.asarray(ia, np.int64), np.asarray(ib, np.int64)
+    R, n = len(ia), int(a.shape[1])
+    if a.dim() != 2 or b.dim() != 2 or int(b.shape[1]) != n or len(ib) != R or len(alpha) != R or R < 1 or n < 1:
+        raise ValueError("lerp_rows: a [Ra, n], b [Rb, n] and R >= 1 entries each of ia, ib, alpha")
+    if ia.min() < 0 or ia.max() >= a.shape[0] or ib.min() < 0 or ib.max() >= b.shape[0]:
+        raise ValueError("lerp_rows: a row index is out of range")
+    i32 = lambda v: torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32)).to(d)
+    out = torch.zeros(R, n, dtype=torch.float32, device=d)
+    ops.lerp_rows(R, n, a, i32(ia), b, i32(ib), torch.as_tensor(np.asarray(alpha, np.float32), device=d), out)
+    return out
+
+
+class _NoiseRows:
+    """a decoding chain's uniforms under noise_rows: drawn for max(noise_rows) + 1 rows, gathered per row (clv_gather_rows)"""
+
+    def __init__(self, noise_rows, N, D, device):
+        self.N, self.D, self.nr = N, D, noise_rows
+        if noise_rows is not None:
+            self.R = int(noise_rows.max().item()) + 1
+            self.idx = noise_rows.to(torch.int64).contiguous()
+            self.u_all = torch.zeros(self.R, D, dtype=torch.float32, device=device)
+
+    def draw(self, u, seed, counter):
+        if self.nr is None:
+            ops.philox_uniform(u, self.N * self.D, seed, 0, 1, 0, step_dev=counter)
+        else:
+            ops.philox_uniform(self.u_all, self.R * self.D, seed, 0, 1, 0, step_dev=counter)
+            ops.gather_rows(self.N, self.D, self.u_all, self.idx, u)
 
 
 def smc_samples_numpy(engine, x_seed, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
@@ -356,7 +467,7 @@ class VaeGenerate:
         return Xs
 
     def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
-             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None):
+             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
         """Re-decode sources [N, T, D]: per frame t the z-encoder on [sources[t], w_enc], z = mean +
         exp(lv / 2) * Tz * eps, the decoder on [w_dec, xp, z] with xp the frame directly before t as in training: x0 (None:
         zeros) at t = 0, then the sample of frame t-1 (history='own') or sources[t-1] ('source': the training forward pass);
@@ -364,7 +475,8 @@ class VaeGenerate:
         another label: key transfer.  Noise as generate's (step = frame).  persistent=True (default where the shapes allow):
         ONE kernel, a workgroup per sequence (the VR instance of csrc/vae_generate.hip; any N); else the layer chain,
         captured once and replayed per frame (N <= batch size), reading its source frame through the device step counter.
-        Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
+        Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities; zout [3, N, T, L]
+         the latents (z_mean, z_log_var, z) of every frame."""
         cfg, d = self.cfg, self.device
         D, L = cfg['D'], cfg['L']
         temper = temper_args(temperature, z_temperature)
@@ -374,10 +486,13 @@ class VaeGenerate:
         Xs = torch.zeros(N, T, D, **f)
         if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
             P = self.P
-            ops.vae_vary(N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], hist_source, seed, sources, x0, w_enc, w_dec,
-                         P.p('h/kernel'), P.p('h/bias'), P.p('zargs/kernel'), P.p('zargs/bias'), P.p('decoder_h/kernel'),
-                         P.p('decoder_h/bias'), P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs, xhat_out,
-                         clamp=clamp, temper=temper)
+            args = (N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], hist_source, seed, sources, x0, w_enc, w_dec,
+                    P.p('h/kernel'), P.p('h/bias'), P.p('zargs/kernel'), P.p('zargs/bias'), P.p('decoder_h/kernel'),
+                    P.p('decoder_h/bias'), P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs)
+            if zout is None:
+                ops.vae_vary(*args, xhat_out, clamp=clamp, temper=temper)
+            else:
+                ops.vae_vary_latents(*args, _zout_ok(zout, N, T, L), xhat_out, clamp=clamp, temper=temper)
             return Xs
         if N > self.B:
             raise ValueError("%d sequences exceed the engine's batch size %d" % (N, self.B))
@@ -398,6 +513,65 @@ class VaeGenerate:
             _vary_sample(N, D, T, self.logits, u, clamp, counter, x_next)
             ops.i32_add(counter, 1)
             xp.copy_(x_src if hist_source else x_next)
+
+        def after(t):
+            Xs[:, t].copy_(x_next)
+            if xhat_out is not None:
+                xhat_out[:, t].copy_(self.logits[:N])
+            if zout is not None:
+                zout[0, :, t].copy_(self.zargs[:N, :L])
+                zout[1, :, t].copy_(self.zargs[:N, L:2 * L])
+                zout[2, :, t].copy_(self.z[:N, :L])
+
+        if zout is not None:
+            _zout_ok(zout, N, T, L)
+        _replay(frame, T, use_graph, after=after)
+        return Xs
+
+    def decode_latents(self, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
+               persistent=True, use_graph=True, xhat_out=None):
+        """Decode the latent path z [N, T, L]: vary's loop without its z-encoder.  Per frame t the decoder on
+        [w_dec, xp, z[:, t]] with xp = x0 (None: zeros) at t = 0, then the sample of frame t-1 (history='own') or
+        history[:, t-1] (an [N, T, D] array: teacher forcing); x ~ Bernoulli(x_hat) with the uniforms of row noise_rows[n]
+        (None: n), then the roll.  No eps is drawn.  persistent=True (default where the shapes allow): ONE kernel, a
+        workgroup per sequence (the ZG instance of csrc/vae_generate.hip); else the layer chain, captured once and replayed
+        per frame (N <= batch size), reading z[:, t] and history[:, t-1] through the device step counter.  Returns Xs
+        [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
+        cfg, d = self.cfg, self.device
+        D, L = cfg['D'], cfg['L']
+        inv_T = decode_temper(temperature)
+        temper = None if inv_T == 1.0 else (inv_T, 1.0)
+        z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, cfg['C'], d)
+        N, T = int(z.shape[0]), int(z.shape[1])
+        f = dict(dtype=torch.float32, device=d)
+        Xs = torch.zeros(N, T, D, **f)
+        if max(N * T * L, N * T * D) >= 2 ** 32:
+            persistent = False
+        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
+            P = self.P
+            ops.vae_decode(N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], seed, z, x0, hist, w_dec, noise_rows,
+                           P.p('decoder_h/kernel'), P.p('decoder_h/bias'), P.p('x_decoded_mean/kernel'),
+                           P.p('x_decoded_mean/bias'), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
+            return Xs
+        if N > self.B:
+            raise ValueError("%d sequences exceed the engine's batch size %d" % (N, self.B))
+        x_next = torch.zeros(N, D, **f)
+        xp = torch.zeros(N, D, **f) if x0 is None else x0.clone()
+        u = torch.zeros(N, D, **f)
+        counter = torch.zeros(1, dtype=torch.int32, device=d)
+        noise = _NoiseRows(noise_rows, N, D, d)
+
+        def frame():
+            ops.take_frame(N, T, L, z, counter, self.z)
+            self.decode(w_dec, self.z, xp if cfg['use_x_prev'] else None, N, act=_head_act(temper))
+            _temper_head(temper, self.logits, N * D)
+            noise.draw(u, seed, counter)
+            _vary_sample(N, D, T, self.logits, u, clamp, counter, x_next)
+            if hist is None:
+                xp.copy_(x_next)
+            else:
+                ops.take_frame(N, T, D, hist, counter, xp)      # history[:, t]: the previous frame of step t+1
+            ops.i32_add(counter, 1)
 
         def after(t):
             Xs[:, t].copy_(x_next)
@@ -465,6 +639,14 @@ class VaeGenerate:
 
         return _smc_drive(_smc_chunks(N, P, self.B, chunk), run_chunk, N, nsteps, D, int(n_out), d,
                           C=None if prior is None else cfg['C'])
+
+
+def _zout_ok(zout, N, T, L):
+    """the latents' output of vary: a contiguous float32 device tensor [3, N, T, L]"""
+    if tuple(zout.shape) != (3, N, T, L) or zout.dtype != torch.float32 or not zout.is_contiguous():
+        raise ValueError("zout must be a contiguous float32 tensor of shape %s, got %s %s" % ((3, N, T, L), zout.dtype,
+                                                                                            tuple(zout.shape)))
+    return zout
 
 
 def _head_act(temper):
@@ -646,7 +828,7 @@ class VrnnGenerate:
         return Xs
 
     def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
-             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None):
+             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
         """Re-decode sources [N, T, D]: from zero LSTM states, per frame t the encoder step on [sources[t],
         w_enc], z = mean + exp(lv / 2) * Tz * eps, the decoder step on [xp, z, w_dec] with xp = x0 (None: zeros) at t = 0,
         then the sample of frame t-1 (history='own') or sources[t-1] ('source': the training forward pass; no effect
@@ -655,7 +837,8 @@ class VrnnGenerate:
         (default where the shapes allow): ONE kernel, a workgroup per sequence (the VR instances of csrc/generate.hip);
         else the per-frame chain, captured once and replayed per frame, reading its source frame through the device step
         counter.  A roll of 2^32 bytes or more takes the chain.  Returns Xs [N, T, D]; xhat_out [N, T, D] receives the
-        unclamped (tempered) probabilities."""
+        unclamped (tempered) probabilities; zout [3, N, T, L] the latents (z_mean, z_log_var, z) of every
+        frame."""
         cfg, d, P = self.cfg, self.device, self.P
         D, H, L, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.off
         temper = temper_args(temperature, z_temperature)
@@ -665,14 +848,22 @@ class VrnnGenerate:
         Xs = torch.zeros(N, T, D, **f)
         if (clamp is not None and clamp.numel() >= 2 ** 32) or T * D * 4 >= 2 ** 32:
             persistent = False
+        if zout is not None:
+            _zout_ok(zout, N, T, L)
+            if zout.numel() >= 3 * 2 ** 32:
+                persistent = False
         if persistent and ops.vrnn_generate_supported(D, H, L, Cn):
             rows = lambda name, r: P.rows(P.params, name, r)
-            ops.vrnn_vary(N, T, D, H, L, Cn, self.gate_act, hist_source, seed, sources, x0, w_enc, w_dec,
-                          P.p('encoder_h/kernel'), rows('encoder_h/kernel', D), P.p('encoder_h/bias'),
-                          P.p('encoder_h/recurrent_kernel'), P.p('Zargs/kernel'), P.p('Zargs/bias'),
-                          P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
-                          rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
-                          P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out, clamp=clamp, temper=temper)
+            args = (N, T, D, H, L, Cn, self.gate_act, hist_source, seed, sources, x0, w_enc, w_dec,
+                    P.p('encoder_h/kernel'), rows('encoder_h/kernel', D), P.p('encoder_h/bias'),
+                    P.p('encoder_h/recurrent_kernel'), P.p('Zargs/kernel'), P.p('Zargs/bias'),
+                    P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
+                    rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
+                    P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs)
+            if zout is None:
+                ops.vrnn_vary(*args, xhat_out, clamp=clamp, temper=temper)
+            else:
+                ops.vrnn_vary_latents(*args, zout, xhat_out, clamp=clamp, temper=temper)
             return Xs
         st = self.new_state(N)
         x_src, x_next = torch.zeros(N, D, **f), torch.zeros(N, D, **f)
@@ -692,6 +883,64 @@ class VrnnGenerate:
             _vary_sample(N, D, T, st['xhat'], u, clamp, counter, x_next)
             ops.i32_add(counter, 1)
             xp.copy_(x_src if hist_source else x_next)
+
+        def after(t):
+            Xs[:, t].copy_(x_next)
+            if xhat_out is not None:
+                xhat_out[:, t].copy_(st['xhat'])
+            if zout is not None:
+                zout[0, :, t].copy_(st['zargs'][:, :L])
+                zout[1, :, t].copy_(st['zargs'][:, L:])
+                zout[2, :, t].copy_(z)
+
+        _replay(frame, T, use_graph, after=after)
+        return Xs
+
+    def decode_latents(self, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
+               persistent=True, use_graph=True, xhat_out=None):
+        """Decode the latent path z [N, T, L]: vary's loop without its encoder.  From zero LSTM state, per
+        frame t the decoder step on [xp, z[:, t], w_dec] with xp = x0 (None: zeros) at t = 0, then the sample of frame t-1
+        (history='own') or history[:, t-1] (an [N, T, D] array: teacher forcing; no effect without use_x_prev);
+        x ~ Bernoulli(x_hat) with the uniforms of row noise_rows[n] (None: n), then the roll clamp [N, T, D].  No eps is
+        drawn.  persistent=True (default where the shapes allow): ONE kernel, a workgroup per sequence (the ZG instances of
+        csrc/generate.hip); else the per-frame chain, captured once and replayed per frame, reading z[:, t] and
+        history[:, t-1] through the device step counter.  N*T*L or N*T*D of 2^32 or more takes the chain.  Returns Xs
+        [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
+        cfg, d, P = self.cfg, self.device, self.P
+        D, H, L, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.off
+        inv_T = decode_temper(temperature)
+        temper = None if inv_T == 1.0 else (inv_T, 1.0)
+        z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, Cn, d)
+        N, T = int(z.shape[0]), int(z.shape[1])
+        f = dict(dtype=torch.float32, device=d)
+        Xs = torch.zeros(N, T, D, **f)
+        if max(N * T * L, N * T * D) >= 2 ** 32:
+            persistent = False
+        if persistent and ops.vrnn_generate_supported(D, H, L, Cn):
+            rows = lambda name, r: P.rows(P.params, name, r)
+            ops.vrnn_decode(N, T, D, H, L, Cn, self.gate_act, seed, z, x0, hist, w_dec, noise_rows,
+                            P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
+                            rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
+                            P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
+            return Xs
+        st = self.new_state(N)
+        x_next, z_t = torch.zeros(N, D, **f), torch.zeros(N, L, **f)
+        xp = torch.zeros(N, D, **f) if x0 is None else x0.clone()
+        u = torch.zeros(N, D, **f)
+        counter = torch.zeros(1, dtype=torch.int32, device=d)
+        noise = _NoiseRows(noise_rows, N, D, d)
+
+        def frame():
+            ops.take_frame(N, T, L, z, counter, z_t)
+            self.dec_step(z_t, xp if cfg['use_x_prev'] else None, w_dec, st, act=_head_act(temper))
+            _temper_head(temper, st['xhat'], N * D)
+            noise.draw(u, seed, counter)
+            _vary_sample(N, D, T, st['xhat'], u, clamp, counter, x_next)
+            if hist is None:
+                xp.copy_(x_next)
+            else:
+                ops.take_frame(N, T, D, hist, counter, xp)      # history[:, t]: the previous frame of step t+1
+            ops.i32_add(counter, 1)
 
         def after(t):
             Xs[:, t].copy_(x_next)

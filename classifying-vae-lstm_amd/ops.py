@@ -431,6 +431,51 @@ def vae_vary(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_en
           "clv_vae_vary")
 
 
+def vrnn_vary_latents(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc,
+                      Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, zout, xhat=None, clamp=None, temper=None):
+    """vrnn_vary that also stores the latents: zout [3,N,T,L] = (z_mean, z_log_var, z) (clv_vrnn_vary_latents)"""
+    inv_T, Tz = (1.0, 1.0) if temper is None else temper
+    check(_lib.lib().clv_vrnn_vary_latents(N, T, D, H, L, Cn, gate_act, int(bool(hist_source)), int(seed), _ptr(sources),
+                                           _ptr(x0), _ptr(w_enc), _ptr(w_dec), _ptr(Kx_enc), _ptr(Kw_enc), _ptr(b_enc),
+                                           _ptr(U_enc), _ptr(Wz), _ptr(bz), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec),
+                                           _ptr(U_dec), _ptr(Wo), _ptr(bo), _ptr(clamp), float(inv_T), float(Tz), _ptr(Xs),
+                                           _ptr(xhat), _ptr(zout), _stream()), "clv_vrnn_vary_latents")
+
+
+def vae_vary_latents(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
+                     Xs, zout, xhat=None, clamp=None, temper=None):
+    """vae_vary that also stores the latents: zout [3,N,T,L] (clv_vae_vary_latents)"""
+    inv_T, Tz = (1.0, 1.0) if temper is None else temper
+    check(_lib.lib().clv_vae_vary_latents(N, T, D, H, L, Cn, int(bool(use_x_prev)), int(bool(hist_source)), int(seed),
+                                          _ptr(sources), _ptr(x0), _ptr(w_enc), _ptr(w_dec), _ptr(Kh), _ptr(bh), _ptr(Kz),
+                                          _ptr(bz), _ptr(Kd), _ptr(bd), _ptr(Ko), _ptr(bo), _ptr(clamp), float(inv_T), float(Tz),
+                                          _ptr(Xs), _ptr(xhat), _ptr(zout), _stream()), "clv_vae_vary_latents")
+
+
+def vrnn_decode(N, T, D, H, L, Cn, gate_act, seed, z_in, x0, history, w_dec, noise_rows, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo,
+                bo, Xs, xhat=None, clamp=None, inv_T=1.0):
+    """cl_vrnn decoding of the latent path z_in [N,T,L] in one persistent launch (clv_vrnn_decode); x0, history
+    [N,T,D], noise_rows [N] int32 (entries >= 0: validated by the caller), clamp, xhat may be None"""
+    check(_lib.lib().clv_vrnn_decode(N, T, D, H, L, Cn, gate_act, int(seed), _ptr(z_in), _ptr(x0), _ptr(history), _ptr(w_dec),
+                                     _ptr(noise_rows), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec), _ptr(U_dec),
+                                     _ptr(Wo), _ptr(bo), _ptr(clamp), float(inv_T), _ptr(Xs), _ptr(xhat), _stream()),
+          "clv_vrnn_decode")
+
+
+def vae_decode(N, T, D, H, L, Cn, use_x_prev, seed, z_in, x0, history, w_dec, noise_rows, Kd, bd, Ko, bo, Xs, xhat=None,
+               clamp=None, inv_T=1.0):
+    """cl_vae decoding of the latent path z_in [N,T,L] in one persistent launch (clv_vae_decode); arguments as vrnn_decode"""
+    check(_lib.lib().clv_vae_decode(N, T, D, H, L, Cn, int(bool(use_x_prev)), int(seed), _ptr(z_in), _ptr(x0), _ptr(history),
+                                    _ptr(w_dec), _ptr(noise_rows), _ptr(Kd), _ptr(bd), _ptr(Ko), _ptr(bo), _ptr(clamp),
+                                    float(inv_T), _ptr(Xs), _ptr(xhat), _stream()), "clv_vae_decode")
+
+
+def lerp_rows(R, n, a, ia, b, ib, alpha, out):
+    """out [R, n] = (1 - alpha[r]) a[ia[r]] + alpha[r] b[ib[r]] as two fmas, exact at both ends (clv_lerp_rows); ia, ib int32"""
+    check(_lib.lib().clv_lerp_rows(int(R), int(n), _ptr(a), _ptr(ia), _ptr(b), _ptr(ib), _ptr(alpha), _ptr(out), _stream()),
+          "clv_lerp_rows")
+
+
 def take_frame(R, T, D, src, step_dev, out):
     """out [R, D] = src[:, *step_dev] of src [R, T, D]: a captured frame chain's read of its source (clv_take_frame)"""
     check(_lib.lib().clv_take_frame(int(R) * int(D), int(T), int(D), _ptr(src), _ptr(step_dev), _ptr(out), _stream()),

@@ -515,6 +515,47 @@ int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_prev, int h
  * step read from the device counter of the captured frame; a step outside [0, T) leaves out untouched. */
 int clv_take_frame(int64_t n, int T, int D, const float* src, const int32_t* step_dev, float* out, void* stream);
 
+/* ------------------------------------- latent paths in and out (encode, decode, morph) --
+ * DESIGN.md 15.  clv_*_vary_latents: clv_*_vary, which additionally stores every frame's latents to zout [3,N,T,L] =
+ * (z_mean | z_log_var | z), z the float32 value the decoder was fed: fma(exp(z_log_var/2), fl(z_temperature * eps), z_mean).
+ * Xs, xhat and every draw are those of clv_*_vary.  zout NULL: exactly clv_*_vary.  CLV_EINVAL for what clv_*_vary refuses
+ * and, with a zout, for N*T*L >= 2^32. */
+int clv_vrnn_vary_latents(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
+                          const float* sources, const float* x0, const float* w_enc, const float* w_dec,
+                          const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                          const float* Wz, const float* bz,
+                          const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                          const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                          float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout, void* stream);
+int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
+                         const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
+                         const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
+                         const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
+                         float z_temperature, float* Xs, float* xhat, float* zout, void* stream);
+/* Decoding a GIVEN latent path z_in [N,T,L]: the loop of clv_*_vary without its encoder.  Per frame t, from zero LSTM state:
+ * the decoder step on [xp, z_in[:, t], w_dec] with xp = x0 [N,D] (NULL: zeros) at t = 0, then the sample of frame t-1
+ * (history NULL) or history[:, t-1] (history [N,T,D]: teacher forcing), x_hat = sigmoid(fl(logit * inv_temperature)),
+ * x = [u <= x_hat] with u = Philox(seed, step t, stream 1, index noise_rows[n]*D + note), then the roll clamp [N,T,D] (NULL:
+ * every note free; row t constrains frame t).  No eps is drawn.  noise_rows [N] int32 (NULL: row n draws as row n): rows with
+ * equal entries share their uniforms.  Every entry must be >= 0: the caller's contract (the host cannot see device memory;
+ * the Python layer validates it).  Xs [N,T,D]; xhat [N,T,D] (optional) the unclamped probabilities.  Shapes as
+ * clv_vrnn_generate_supported / clv_vae_generate_supported.  CLV_EINVAL, before any launch, for a NULL z_in, w_dec or Xs,
+ * N or T < 1, N*T*L or N*T*D >= 2^32, and an inv_temperature that is zero, negative or not finite. */
+int clv_vrnn_decode(int N, int T, int D, int H, int L, int C, int gate_act, uint64_t seed, const float* z_in,
+                    const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
+                    const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                    const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                    float inv_temperature, float* Xs, float* xhat, void* stream);
+int clv_vae_decode(int N, int T, int D, int H, int L, int C, int use_x_prev, uint64_t seed, const float* z_in,
+                   const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
+                   const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
+                   float inv_temperature, float* Xs, float* xhat, void* stream);
+/* Row-wise linear interpolation, one thread per element: out[r,:] = fmaf(alpha[r], b[ib[r],:], fmaf(-alpha[r], a[ia[r],:],
+ * a[ia[r],:])) for R rows of n floats; exact at alpha = 0 (a's row) and alpha = 1 (b's row).  ia, ib [R] int32 row indices
+ * into a and b (in range: the caller's contract). */
+int clv_lerp_rows(int64_t R, int64_t n, const float* a, const int32_t* ia, const float* b, const int32_t* ib,
+                  const float* alpha, float* out, void* stream);
+
 /* ------------------------------------------------------------ pointwise --
  * logistic-normal label sample + its two losses, one thread per row:
  *   w = softmax([mean + exp(lv/2)*eps, 0]); kl_w, w_rec = (C-1)*CCE(onehot, w+1e-10), hit
