@@ -13,11 +13,10 @@ used.  `emulate_fresh_encoder=True` reproduces the reference behaviour.
 import json
 
 import numpy as np
-import torch
 
 from .. import sampling
 from ..engine import VrnnEngine, vrnn_param_shapes
-from ..engine_generate import (clamp_roll, decode_latents_numpy, encode_latents_numpy, smc_args, smc_samples_numpy, temper_args,
+from ..engine_generate import (decode_latents_numpy, device_f32, encode_latents_numpy, generate_samples_numpy, temper_args,
                                vary_samples_numpy)
 from ..initializers import glorot_uniform, init_weights, orthogonal
 from ..keras_like import Layer, Model, get_value
@@ -89,7 +88,7 @@ def generate_sample(dec_model, w_enc_model, z_enc_model, x_seed, nsteps, use_x_p
 # models
 # --------------------------------------------------------------------------- #
 def _dev(a, dev, shape):
-    return torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32), device=dev).reshape(shape)
+    return device_f32(a, dev).reshape(shape)
 
 
 class ClVrnnModel(Model):
@@ -252,25 +251,10 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     temperature (> 0) divides every note's logit before the sigmoid, z_temperature (>= 0) scales the latent noise (0: z is
     its mean): every route then samples the TEMPERED model with the same Philox draws, and the evidence is
     the tempered model's, log p_T(constraints | ...), not the trained model's unless both are 1 (the default)."""
-    temper = dict(temperature=temperature, z_temperature=z_temperature)
-    temper_args(**temper)
-    e = model.engine
-    xs = torch.as_tensor(np.ascontiguousarray(np.asarray(x_seeds), dtype=np.float32), device=e.device)
-    if (w_vals is None) == (w_prior is None):
-        raise ValueError("give exactly one of w_vals and w_prior")
-    if particles is None and (w_prior is not None or return_key):
-        raise ValueError("w_prior and return_key need particles")
-    w = None if w_vals is None else torch.as_tensor(np.ascontiguousarray(np.asarray(w_vals), dtype=np.float32),
-                                                    device=e.device)
-    if particles is not None:
-        smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, e.cfg['D'], e.device)
-        return smc_samples_numpy(e, xs, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
-                                 w_prior=w_prior, return_key=return_key, **temper)
-    if return_evidence:
-        raise ValueError("return_evidence needs particles")
-    clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), e.cfg['D'], e.device)
-    return e.generate(xs, w, int(nsteps), seed=int(seed), z_prior=z_prior, clamp=clamp,
-                      **temper).cpu().numpy().astype(np.float64)
+    temper_args(temperature, z_temperature)         # refused before the model's engine is asked for
+    return generate_samples_numpy(model.engine, x_seeds, nsteps, w_vals, seed=seed, z_prior=z_prior, clamp=clamp,
+                                  particles=particles, resample_threshold=resample_threshold, return_evidence=return_evidence,
+                                  w_prior=w_prior, return_key=return_key, temperature=temperature, z_temperature=z_temperature)
 
 
 def vary_samples_device(model, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,

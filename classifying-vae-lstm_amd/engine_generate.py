@@ -10,8 +10,11 @@ from . import _lib, ops
 from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID
 
 
-def _f(device, *shape):
-    return torch.zeros(*shape, dtype=torch.float32, device=device)
+def device_f32(a, device):
+    """a host array or a tensor as a contiguous float32 tensor on the device"""
+    if not isinstance(a, torch.Tensor):
+        a = torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32))
+    return a.to(dtype=torch.float32, device=device).contiguous()
 
 
 def clamp_roll(clamp, N, nsteps, D, device):
@@ -170,8 +173,7 @@ def vary_args(sources, w_enc, w_dec, x0, history, clamp, D, C, device):
     if w_enc is None:
         raise ValueError("re-decoding needs w_enc, the label the encoder conditions on%s"
                          % ("" if w_dec is None else " (w_dec was given without it)"))
-    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32))
-                   ).to(dtype=torch.float32, device=device).contiguous()
+    t = lambda a: device_f32(a, device)
     sources = t(sources)
     if sources.dim() != 3 or sources.shape[0] < 1 or sources.shape[1] < 1 or sources.shape[2] != D:
         raise ValueError("sources must be [N, T, %d] with N, T >= 1, got shape %s" % (D, tuple(sources.shape)))
@@ -186,6 +188,31 @@ def vary_args(sources, w_enc, w_dec, x0, history, clamp, D, C, device):
         if tuple(x0.shape) != (N, D):
             raise ValueError("x0 must have shape %s, got %s" % ((N, D), tuple(x0.shape)))
     return sources, w_enc, w_dec, x0, clamp_roll(clamp, N, int(sources.shape[1]), D, device), history == 'source'
+
+
+def generate_samples_numpy(engine, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
+                           resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False, temperature=1.0,
+                           z_temperature=1.0):
+    """generate_samples_device of both families: engine.generate, or with particles engine.generate_smc, on host arrays ->
+    [N, nsteps, D] float64 (and what smc_samples_numpy adds)"""
+    temper = dict(temperature=temperature, z_temperature=z_temperature)
+    temper_args(**temper)
+    d = engine.device
+    xs = device_f32(x_seeds, d)
+    if (w_vals is None) == (w_prior is None):
+        raise ValueError("give exactly one of w_vals and w_prior")
+    if particles is None and (w_prior is not None or return_key):
+        raise ValueError("w_prior and return_key need particles")
+    w = None if w_vals is None else device_f32(w_vals, d)
+    if particles is not None:
+        smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, engine.cfg['D'], d)
+        return smc_samples_numpy(engine, xs, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
+                                 w_prior=w_prior, return_key=return_key, **temper)
+    if return_evidence:
+        raise ValueError("return_evidence needs particles")
+    clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), engine.cfg['D'], d)
+    return engine.generate(xs, w, int(nsteps), seed=int(seed), z_prior=z_prior, clamp=clamp,
+                           **temper).cpu().numpy().astype(np.float64)
 
 
 def vary_samples_numpy(engine, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
@@ -222,8 +249,7 @@ def decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, C, device):
     w_dec [N, C], x0 [N, D] or None, history [N, T, D] or None ('own'), the roll or None, noise_rows [N] int32 or None).
     numpy or torch in; ValueError for a wrong shape, a z whose last dimension is not L, a history that is neither 'own' nor
     an [N, T, D] array, and noise_rows that are not N integers >= 0."""
-    t = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(a), dtype=np.float32))
-                   ).to(dtype=torch.float32, device=device).contiguous()
+    t = lambda a: device_f32(a, device)
     if z is None or w_dec is None:
         raise ValueError("decoding needs a latent path z and the decoder's label w_dec")
     z = t(z)
@@ -295,10 +321,11 @@ def lerp_rows(a, ia, b, ib, alpha):
 
 
 class _NoiseRows:
-    """a decoding chain's uniforms under noise_rows: drawn for max(noise_rows) + 1 rows, gathered per row (clv_gather_rows)"""
+    """a frame chain's uniforms: those of its own N rows, or under noise_rows drawn for max(noise_rows) + 1 rows and gathered
+    per row (clv_gather_rows)"""
 
-    def __init__(self, noise_rows, N, D, device):
-        self.N, self.D, self.nr = N, D, noise_rows
+    def __init__(self, noise_rows, N, D, device, first=0):
+        self.N, self.D, self.nr, self.first = N, D, noise_rows, first       # first: the Philox index of own row 0's note 0
         if noise_rows is not None:
             self.R = int(noise_rows.max().item()) + 1
             self.idx = noise_rows.to(torch.int64).contiguous()
@@ -306,7 +333,7 @@ class _NoiseRows:
 
     def draw(self, u, seed, counter):
         if self.nr is None:
-            ops.philox_uniform(u, self.N * self.D, seed, 0, 1, 0, step_dev=counter)
+            ops.philox_uniform(u, self.N * self.D, seed, 0, 1, self.first, step_dev=counter)
         else:
             ops.philox_uniform(self.u_all, self.R * self.D, seed, 0, 1, 0, step_dev=counter)
             ops.gather_rows(self.N, self.D, self.u_all, self.idx, u)
@@ -400,245 +427,29 @@ def _smc_drive(chunks, run_chunk, N, nsteps, D, n_out, device, C=None):
     return out
 
 
-class VaeGenerate:
-    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None,
-                 temperature=1.0, z_temperature=1.0):
-        """N independent sequences of `nsteps` frames on the device: the frame loop of cl_vae/model.py:28-41
-        (z-encoder on the last frame, z ~ N(mean, exp(lv)) or N(0, 1), decoder on (w, z, frame before last),
-        x ~ Bernoulli); eps and u come from the Philox streams 0 / 1 at step = frame index.  x_seed [N,D], w [N,C] device
-        tensors.  persistent=True (default where the shapes allow): the whole loop is ONE kernel, a workgroup per
-        sequence (csrc/vae_generate.hip; any N); otherwise the layer chain captured once as a hipGraph and replayed per
-        frame (N <= batch size).  Same noise, same samples either way.  clamp: constraint roll [N,nsteps,D] (clamp_roll;
-        row t constrains frame t, which is then fed back like a sampled one: clamped ancestral sampling).
-        temperature, z_temperature (temper_args, DESIGN.md 13): sample from the tempered model, x_hat = sigmoid(logit /
-        temperature) and z = mean + exp(lv / 2) * z_temperature * eps, with the same Philox draws; xhat_out then holds the
-        tempered probabilities.  Both 1.0 (default): exactly the untempered launches."""
-        cfg, d = self.cfg, self.device
-        N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
-        clamp = clamp_roll(clamp, N, nsteps, D, d)
-        temper = temper_args(temperature, z_temperature)
-        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
-            P = self.P
-            f = dict(dtype=torch.float32, device=d)
-            Xs = torch.zeros(N, nsteps, D, **f)
-            ops.vae_generate(N, nsteps, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], z_prior, seed,
-                             x_seed.to(**f).contiguous(), w.to(**f).contiguous(), P.p('h/kernel'), P.p('h/bias'),
-                             P.p('zargs/kernel'), P.p('zargs/bias'), P.p('decoder_h/kernel'), P.p('decoder_h/bias'),
-                             P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs, xhat_out, clamp=clamp,
-                             temper=temper)
-            return Xs
-        if N > self.B:
-            raise ValueError("%d sequences exceed the engine's batch size %d" % (N, self.B))
-        f = dict(dtype=torch.float32, device=d)
-        x_in, hist, x_next = x_seed.to(**f).clone(), x_seed.to(**f).clone(), torch.zeros(N, D, **f)
-        eps, u = torch.zeros(N, L, **f), torch.zeros(N, D, **f)
-        counter = torch.zeros(1, dtype=torch.int32, device=d)
-        Xs = torch.zeros(N, nsteps, D, **f)
-        w = w.to(**f).contiguous()
+def _smc_run(eng, S, cap, chain_of, x_seed, w, nsteps, clamp, particles, resample_threshold, n_out, seed, use_graph, chunk,
+             w_prior):
+    """generate_smc of both families: S seed steps, at most cap rows per chunk; chain_of(xs, wr, r0, smc) is the family's
+    frame chain over the chunk's particle rows (seeds xs and labels wr per row, r0 the first global row)"""
+    cfg, d = eng.cfg, eng.device
+    N, D = int(x_seed.shape[0]), cfg['D']
+    clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
+    P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
+    x_seed = x_seed.to(dtype=torch.float32, device=d)
+    w, prior = smc_label_args(w, w_prior, N, cfg['C'], d)
 
-        def frame():
-            self.encode_z(x_in, w, N)
-            ops.philox_normal(eps, N * L, seed, 0, 0, 0, step_dev=counter)
-            if z_prior:
-                self.zargs[:N].zero_()
-            _temper_eps(temper, eps, N * L)
-            ops.gauss_fwd(N, L, self.zargs, eps, self.z, L, None)
-            self.decode(w, self.z, hist if cfg['use_x_prev'] else None, N, act=_head_act(temper))
-            _temper_head(temper, self.logits, N * D)
-            ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
-            if clamp is None:
-                ops.bernoulli_sample(N * D, self.logits, u, x_next)
-            else:
-                ops.bernoulli_sample_clamped(N * D, D, nsteps, 0, self.logits, u, clamp, counter, x_next)
-            ops.i32_add(counter, 1)
-            hist.copy_(x_in)            # the decoder's history lags the encoder input by one frame
-            x_in.copy_(x_next)
+    def run_chunk(m0, m1):
+        if prior is None:
+            wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+        else:
+            wr = torch.zeros((m1 - m0) * P, cfg['C'], dtype=torch.float32, device=d)
+            prior.init_rows(m0, m1, P, seed, wr)
+        smc = _Smc(m1 - m0, P, nsteps, S, D, tau, seed, m0, clamp[m0:m1], d, wr=None if prior is None else wr)
+        chain_of(x_seed[m0:m1].repeat_interleave(P, 0), wr, m0 * P, smc).run(S + nsteps, use_graph)
+        return smc
 
-        graph = None
-        for t in range(nsteps):
-            if use_graph and t == 1:
-                with ops.Graph() as graph:       # frame 0 ran eagerly and sized every workspace
-                    frame()
-            if graph is not None:
-                graph.launch()
-            else:
-                frame()
-            Xs[:, t].copy_(x_next)
-        return Xs
-
-    def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
-             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
-        """Re-decode sources [N, T, D] (DESIGN.md 14): per frame t the z-encoder on [sources[t], w_enc], z = mean +
-        exp(lv / 2) * Tz * eps, the decoder on [w_dec, xp, z] with xp the frame directly before t as in training: x0 (None:
-        zeros) at t = 0, then the sample of frame t-1 (history='own') or sources[t-1] ('source': the training forward pass);
-        x ~ Bernoulli(x_hat), then the roll clamp [N, T, D] (row t constrains frame t).  w_dec=None: w_enc (a variation);
-        another label: key transfer.  Noise as generate's (step = frame).  persistent=True (default where the shapes allow):
-        ONE kernel, a workgroup per sequence (the VR instance of csrc/vae_generate.hip; any N); else the layer chain,
-        captured once and replayed per frame (N <= batch size), reading its source frame through the device step counter.
-        Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities; zout [3, N, T, L]
-        (DESIGN.md 15) the latents (z_mean, z_log_var, z) of every frame."""
-        cfg, d = self.cfg, self.device
-        D, L = cfg['D'], cfg['L']
-        temper = temper_args(temperature, z_temperature)
-        sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, cfg['C'], d)
-        N, T = int(sources.shape[0]), int(sources.shape[1])
-        f = dict(dtype=torch.float32, device=d)
-        Xs = torch.zeros(N, T, D, **f)
-        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
-            P = self.P
-            args = (N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], hist_source, seed, sources, x0, w_enc, w_dec,
-                    P.p('h/kernel'), P.p('h/bias'), P.p('zargs/kernel'), P.p('zargs/bias'), P.p('decoder_h/kernel'),
-                    P.p('decoder_h/bias'), P.p('x_decoded_mean/kernel'), P.p('x_decoded_mean/bias'), Xs)
-            if zout is None:
-                ops.vae_vary(*args, xhat_out, clamp=clamp, temper=temper)
-            else:
-                ops.vae_vary_latents(*args, _zout_ok(zout, N, T, L), xhat_out, clamp=clamp, temper=temper)
-            return Xs
-        if N > self.B:
-            raise ValueError("%d sequences exceed the engine's batch size %d" % (N, self.B))
-        x_src, x_next = torch.zeros(N, D, **f), torch.zeros(N, D, **f)
-        xp = torch.zeros(N, D, **f) if x0 is None else x0.clone()
-        eps, u = torch.zeros(N, L, **f), torch.zeros(N, D, **f)
-        counter = torch.zeros(1, dtype=torch.int32, device=d)
-
-        def frame():
-            ops.take_frame(N, T, D, sources, counter, x_src)
-            self.encode_z(x_src, w_enc, N)
-            ops.philox_normal(eps, N * L, seed, 0, 0, 0, step_dev=counter)
-            _temper_eps(temper, eps, N * L)
-            ops.gauss_fwd(N, L, self.zargs, eps, self.z, L, None)
-            self.decode(w_dec, self.z, xp if cfg['use_x_prev'] else None, N, act=_head_act(temper))
-            _temper_head(temper, self.logits, N * D)
-            ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
-            _vary_sample(N, D, T, self.logits, u, clamp, counter, x_next)
-            ops.i32_add(counter, 1)
-            xp.copy_(x_src if hist_source else x_next)
-
-        def after(t):
-            Xs[:, t].copy_(x_next)
-            if xhat_out is not None:
-                xhat_out[:, t].copy_(self.logits[:N])
-            if zout is not None:
-                zout[0, :, t].copy_(self.zargs[:N, :L])
-                zout[1, :, t].copy_(self.zargs[:N, L:2 * L])
-                zout[2, :, t].copy_(self.z[:N, :L])
-
-        if zout is not None:
-            _zout_ok(zout, N, T, L)
-        _replay(frame, T, use_graph, after=after)
-        return Xs
-
-    def decode_latents(self, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
-               persistent=True, use_graph=True, xhat_out=None):
-        """Decode the latent path z [N, T, L] (DESIGN.md 15): vary's loop without its z-encoder.  Per frame t the decoder on
-        [w_dec, xp, z[:, t]] with xp = x0 (None: zeros) at t = 0, then the sample of frame t-1 (history='own') or
-        history[:, t-1] (an [N, T, D] array: teacher forcing); x ~ Bernoulli(x_hat) with the uniforms of row noise_rows[n]
-        (None: n), then the roll.  No eps is drawn.  persistent=True (default where the shapes allow): ONE kernel, a
-        workgroup per sequence (the ZG instance of csrc/vae_generate.hip); else the layer chain, captured once and replayed
-        per frame (N <= batch size), reading z[:, t] and history[:, t-1] through the device step counter.  Returns Xs
-        [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
-        cfg, d = self.cfg, self.device
-        D, L = cfg['D'], cfg['L']
-        inv_T = decode_temper(temperature)
-        temper = None if inv_T == 1.0 else (inv_T, 1.0)
-        z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, cfg['C'], d)
-        N, T = int(z.shape[0]), int(z.shape[1])
-        f = dict(dtype=torch.float32, device=d)
-        Xs = torch.zeros(N, T, D, **f)
-        if max(N * T * L, N * T * D) >= 2 ** 32:
-            persistent = False
-        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
-            P = self.P
-            ops.vae_decode(N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], seed, z, x0, hist, w_dec, noise_rows,
-                           P.p('decoder_h/kernel'), P.p('decoder_h/bias'), P.p('x_decoded_mean/kernel'),
-                           P.p('x_decoded_mean/bias'), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
-            return Xs
-        if N > self.B:
-            raise ValueError("%d sequences exceed the engine's batch size %d" % (N, self.B))
-        x_next = torch.zeros(N, D, **f)
-        xp = torch.zeros(N, D, **f) if x0 is None else x0.clone()
-        u = torch.zeros(N, D, **f)
-        counter = torch.zeros(1, dtype=torch.int32, device=d)
-        noise = _NoiseRows(noise_rows, N, D, d)
-
-        def frame():
-            ops.take_frame(N, T, L, z, counter, self.z)
-            self.decode(w_dec, self.z, xp if cfg['use_x_prev'] else None, N, act=_head_act(temper))
-            _temper_head(temper, self.logits, N * D)
-            noise.draw(u, seed, counter)
-            _vary_sample(N, D, T, self.logits, u, clamp, counter, x_next)
-            if hist is None:
-                xp.copy_(x_next)
-            else:
-                ops.take_frame(N, T, D, hist, counter, xp)      # history[:, t]: the previous frame of step t+1
-            ops.i32_add(counter, 1)
-
-        def after(t):
-            Xs[:, t].copy_(x_next)
-            if xhat_out is not None:
-                xhat_out[:, t].copy_(self.logits[:N])
-
-        _replay(frame, T, use_graph, after=after)
-        return Xs
-
-    def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
-                     z_prior=False, chunk=None, w_prior=None, temperature=1.0, z_temperature=1.0):
-        """Particle-filter sampling under the constraint roll clamp [N, nsteps, D] (DESIGN.md 11): melody m runs P =
-        `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
-        probability of each frame's clamped notes and resampled (systematic, below an ESS of resample_threshold * P).
-        Row t of the roll constrains frame t.  Melodies are processed in chunks of at most batch-size rows (and at most
-        `chunk` melodies); the Philox keys follow the global row, so the result does not depend on the chunking.
-        x_seed [N, D], w [N, C] device tensors.  Returns SmcResult (Xs [N, n_out, nsteps, D]).
-        w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state, so the filter
-        targets p(w, free notes | seed, constraints) (DESIGN.md 12); returns SmcKeyResult.
-        temperature, z_temperature (temper_args, DESIGN.md 13): the filter runs on the TEMPERED model; its weights are the
-        tempered probabilities of the clamped notes, so log_evidence estimates log p_T(constraints | seed, w), the evidence
-        under the tempered model -- the trained model's only where both are 1."""
-        cfg, d = self.cfg, self.device
-        N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
-        temper = temper_args(temperature, z_temperature)
-        clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
-        P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
-        f = dict(dtype=torch.float32, device=d)
-        x_seed = x_seed.to(**f)
-        w, prior = smc_label_args(w, w_prior, N, cfg['C'], d)
-
-        def run_chunk(m0, m1):
-            G = m1 - m0
-            R, r0 = G * P, m0 * P
-            x_in = x_seed[m0:m1].repeat_interleave(P, 0).contiguous()
-            hist, x_next = x_in.clone(), torch.zeros(R, D, **f)
-            if prior is None:
-                wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
-            else:
-                wr = torch.zeros(R, cfg['C'], **f)
-                prior.init_rows(m0, m1, P, seed, wr)
-            eps, u = torch.zeros(R, L, **f), torch.zeros(R, D, **f)
-            counter = torch.zeros(1, dtype=torch.int32, device=d)
-            smc = _Smc(G, P, nsteps, 0, D, tau, seed, m0, clamp[m0:m1], d, wr=None if prior is None else wr)
-            # x_in becomes the decoder's history below; a particle's own key travels with its state
-            gather = ops.SmcGather(R, P, nsteps, 0, [x_next, x_in] + ([] if prior is None else [wr]))
-
-            def frame():
-                self.encode_z(x_in, wr, R)
-                ops.philox_normal(eps, R * L, seed, 0, 0, r0 * L, step_dev=counter)
-                if z_prior:
-                    self.zargs[:R].zero_()
-                _temper_eps(temper, eps, R * L)
-                ops.gauss_fwd(R, L, self.zargs, eps, self.z, L, None)
-                self.decode(wr, self.z, hist if cfg['use_x_prev'] else None, R, act=_head_act(temper))
-                _temper_head(temper, self.logits, R * D)
-                ops.philox_uniform(u, R * D, seed, 0, 1, r0 * D, step_dev=counter)
-                smc.step(self.logits, u, counter, x_next, gather)
-                ops.i32_add(counter, 1)
-                hist.copy_(x_in)
-                x_in.copy_(x_next)
-
-            _replay(frame, nsteps, use_graph)
-            return smc
-
-        return _smc_drive(_smc_chunks(N, P, self.B, chunk), run_chunk, N, nsteps, D, int(n_out), d,
-                          C=None if prior is None else cfg['C'])
+    return _smc_drive(_smc_chunks(N, P, cap, chunk), run_chunk, N, nsteps, D, int(n_out), d,
+                      C=None if prior is None else cfg['C'])
 
 
 def _zout_ok(zout, N, T, L):
@@ -647,31 +458,6 @@ def _zout_ok(zout, N, T, L):
         raise ValueError("zout must be a contiguous float32 tensor of shape %s, got %s %s" % ((3, N, T, L), zout.dtype,
                                                                                             tuple(zout.shape)))
     return zout
-
-
-def _head_act(temper):
-    """the output head's GEMM epilogue in a frame chain: its own sigmoid, or none where _temper_head applies it"""
-    return ACT_SIGMOID if temper is None or temper[0] == 1.0 else ACT_NONE
-
-
-def _temper_head(temper, a, n):
-    """tempered frame chain: the head's pre-activations a[:n] -> sigmoid(fl32(a * inv_T)), one launch (none at inv_T = 1)"""
-    if temper is not None and temper[0] != 1.0:
-        ops.sigmoid_temper(n, a, temper[0])
-
-
-def _temper_eps(temper, eps, n):
-    """tempered frame chain: eps[:n] -> fl32(Tz * eps) between philox_normal and gauss_fwd, one launch (none at Tz = 1)"""
-    if temper is not None and temper[1] != 1.0:
-        ops.scale_temper(n, eps, temper[1])
-
-
-def _vary_sample(N, D, T, p, u, clamp, counter, x_next):
-    """a re-decoding chain's draw of frame *counter: x_next = [u <= p], then row *counter of the roll (None: all free)"""
-    if clamp is None:
-        ops.bernoulli_sample(N * D, p, u, x_next)
-    else:
-        ops.bernoulli_sample_clamped(N * D, D, T, 0, p, u, clamp, counter, x_next)
 
 
 def _replay(frame, nsteps, use_graph, before=None, after=None):
@@ -690,6 +476,259 @@ def _replay(frame, nsteps, use_graph, before=None, after=None):
             frame()
         if after is not None:
             after(t)
+
+
+class _VaeRows:
+    """cl_vae's part of a frame chain over R rows, at most the batch size: the engine's own buffers and layer chains"""
+
+    def __init__(self, eng, R):
+        if R > eng.B:
+            raise ValueError("%d sequences exceed the engine's batch size %d" % (R, eng.B))
+        self.eng, self.R = eng, R
+        self.zargs, self.z, self.xhat = eng.zargs, eng.z, eng.logits
+
+    def encode(self, x, w):
+        self.eng.encode_z(x, w, self.R)
+
+    def decode(self, w, z, xp, act):
+        self.eng.decode(w, z, xp, self.R, act=act)
+
+    def carried(self, x_enc, x_next):
+        """what a particle hands to its descendants: x_enc too, the decoder's previous frame of the next step"""
+        return [x_next, x_enc]
+
+
+class _VrnnRows:
+    """cl_vrnn's part of a frame chain over R rows (any number): a state of its own, the probabilities in st['xhat']"""
+
+    def __init__(self, eng, R):
+        self.eng, self.R = eng, R
+        self.st = eng.new_state(R)
+        self.zargs, self.xhat = self.st['zargs'], self.st['xhat']
+        self.z = torch.zeros(R, eng.cfg['L'], dtype=torch.float32, device=eng.device)
+
+    def encode(self, x, w):
+        self.eng.enc_step(x, w, self.st)
+
+    def decode(self, w, z, xp, act):
+        self.eng.dec_step(z, xp, w, self.st, act=act)
+
+    def carried(self, x_enc, x_next):
+        """what a particle hands to its descendants: both LSTM states and its sample"""
+        return [self.st[k] for k in ('h_enc', 'c_enc', 'h_dec', 'c_dec')] + [x_next]
+
+
+class _Chain:
+    """The launches of one frame of every device sampling loop (generate, vary, decode_latents and generate_smc of both
+    families) over the rows of a _VaeRows / _VrnnRows, and its replay.  Three frame slots: x_enc, the
+    encoder's input; x_dec, the decoder's previous frame; x_next, the sample.  The call's choices:
+    * x_enc: sources[:, t] of sources [R, nsteps, D] (clv_take_frame through the device step counter), else the sample fed
+      back -- from step S = seed_frames.shape[1] on; before that seed_frames[:, t].
+    * z: z_path[:, t] of z_path [R, nsteps, L] and no encoder, else the encoder on [x_enc, w_enc] with eps of Philox stream 0
+      from index r0 * L; under z_prior its zargs are zeroed.
+    * the uniforms: the rows' own of stream 1 from index r0 * D, or those of rows noise_rows (_NoiseRows).
+    * the draw: free, under row t - S of the roll clamp [R, nsteps, D], or a particle filter's step (smc, an _Smc, which
+      brings its own roll and S) followed by the ancestor gather of the rows' carried buffers.
+    * dec_prev, what x_dec holds at the next step: 'sample'; 'enc_input', this step's x_enc (the decoder then lags the
+      encoder by one frame: cl_vae's generator, and a re-decoding on its source's history); 'shared', x_dec IS x_enc
+      (cl_vrnn's generator); or a history [R, nsteps, D] (history[:, t], clv_take_frame).
+    temper None or (inv_T, Tz) (temper_args): a factor other than 1 takes one more launch each, the head's sigmoid then
+    being sigmoid_temper's."""
+
+    def __init__(self, rows, w_enc, w_dec, nsteps, seed, temper, dec_prev, x_enc=None, x_dec=None, sources=None, z_path=None,
+                 z_prior=False, seed_frames=None, noise_rows=None, r0=0, clamp=None, S=0, smc=None):
+        eng, R = rows.eng, rows.R
+        D, L, d = eng.cfg['D'], eng.cfg['L'], eng.device
+        new = lambda n: torch.zeros(R, n, dtype=torch.float32, device=d)
+        self.rows, self.w_enc, self.w_dec, self.nsteps, self.seed, self.r0 = rows, w_enc, w_dec, nsteps, seed, r0
+        self.inv_T, self.Tz = (1.0, 1.0) if temper is None else temper
+        self.sources, self.z_path, self.z_prior, self.seed_frames = sources, z_path, z_prior, seed_frames
+        self.history, self.dec_prev = (None, dec_prev) if isinstance(dec_prev, str) else (dec_prev, 'history')
+        self.clamp, self.S, self.smc = clamp, S, smc
+        if z_path is None:
+            self.x_enc, self.eps = new(D) if x_enc is None else x_enc, new(L)
+        self.x_dec = self.x_enc if self.dec_prev == 'shared' else new(D) if x_dec is None else x_dec
+        self.x_next, self.u = new(D), new(D)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=d)
+        self.noise = _NoiseRows(noise_rows, R, D, d, first=r0 * D)
+        if smc is not None:
+            self.gather = ops.SmcGather(R, smc.P, smc.nsteps, smc.S, rows.carried(self.x_enc, self.x_next)
+                                        + ([] if smc.wr is None else [smc.wr]))     # a particle's own key travels with it
+
+    def frame(self):
+        rows, R, T, c = self.rows, self.rows.R, self.nsteps, self.counter
+        D, L = rows.eng.cfg['D'], rows.eng.cfg['L']
+        if self.sources is not None:
+            ops.take_frame(R, T, D, self.sources, c, self.x_enc)
+        if self.z_path is None:
+            rows.encode(self.x_enc, self.w_enc)
+            ops.philox_normal(self.eps, R * L, self.seed, 0, 0, self.r0 * L, step_dev=c)
+            if self.z_prior:
+                rows.zargs[:R].zero_()
+            if self.Tz != 1.0:
+                ops.scale_temper(R * L, self.eps, self.Tz)
+            ops.gauss_fwd(R, L, rows.zargs, self.eps, rows.z, L, None)
+        else:
+            ops.take_frame(R, T, L, self.z_path, c, rows.z)
+        rows.decode(self.w_dec, rows.z, self.x_dec if rows.eng.cfg['use_x_prev'] else None,
+                    ACT_SIGMOID if self.inv_T == 1.0 else ACT_NONE)
+        if self.inv_T != 1.0:
+            ops.sigmoid_temper(R * D, rows.xhat, self.inv_T)
+        self.noise.draw(self.u, self.seed, c)
+        if self.smc is not None:
+            self.smc.step(rows.xhat, self.u, c, self.x_next, self.gather)
+        elif self.clamp is None:
+            ops.bernoulli_sample(R * D, rows.xhat, self.u, self.x_next)
+        else:                   # the row of step counter - S: none for the seed steps and the bridge
+            ops.bernoulli_sample_clamped(R * D, D, T, self.S, rows.xhat, self.u, self.clamp, c, self.x_next)
+        if self.dec_prev == 'history':
+            ops.take_frame(R, T, D, self.history, c, self.x_dec)        # history[:, t]: the previous frame of step t+1
+        elif self.dec_prev != 'shared':
+            self.x_dec.copy_(self.x_enc if self.dec_prev == 'enc_input' else self.x_next)
+        if self.sources is None and self.z_path is None:
+            self.x_enc.copy_(self.x_next)
+        ops.i32_add(c, 1)
+
+    def _seed(self, t):
+        if t < self.seed_frames.shape[1]:
+            self.x_enc.copy_(self.seed_frames[:, t])
+
+    def run(self, nframes, use_graph, after=None):
+        _replay(self.frame, nframes, use_graph, None if self.seed_frames is None else self._seed, after)
+
+    def store(self, j, Xs, xhat_out=None, zout=None):
+        """after a frame: its sample to Xs[:, j], its (tempered) probabilities to xhat_out[:, j], its latents (z_mean,
+        z_log_var, z) to zout[:, :, j]"""
+        rows, R, L = self.rows, self.rows.R, self.rows.eng.cfg['L']
+        Xs[:, j].copy_(self.x_next)
+        if xhat_out is not None:
+            xhat_out[:, j].copy_(rows.xhat[:R])
+        if zout is not None:
+            zout[0, :, j].copy_(rows.zargs[:R, :L])
+            zout[1, :, j].copy_(rows.zargs[:R, L:])
+            zout[2, :, j].copy_(rows.z[:R])
+
+
+class VaeGenerate:
+    def _weights(self, encoder=True):
+        """the persistent kernels' weight arguments in the order ops.vae_* take them: the encoder half (vae_decode takes
+        none), the decoder half, the head"""
+        p = self.P.p
+        enc = (p('h/kernel'), p('h/bias'), p('zargs/kernel'), p('zargs/bias')) if encoder else ()
+        return enc + (p('decoder_h/kernel'), p('decoder_h/bias'), p('x_decoded_mean/kernel'), p('x_decoded_mean/bias'))
+
+    def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None,
+                 temperature=1.0, z_temperature=1.0):
+        """N independent sequences of `nsteps` frames on the device: the frame loop of cl_vae/model.py:28-41
+        (z-encoder on the last frame, z ~ N(mean, exp(lv)) or N(0, 1), decoder on (w, z, frame before last),
+        x ~ Bernoulli); eps and u come from the Philox streams 0 / 1 at step = frame index.  x_seed [N,D], w [N,C] device
+        tensors.  persistent=True (default where the shapes allow): the whole loop is ONE kernel, a workgroup per
+        sequence (csrc/vae_generate.hip; any N); otherwise the layer chain captured once as a hipGraph and replayed per
+        frame (N <= batch size).  Same noise, same samples either way.  clamp: constraint roll [N,nsteps,D] (clamp_roll;
+        row t constrains frame t, which is then fed back like a sampled one: clamped ancestral sampling).
+        temperature, z_temperature (temper_args, DESIGN.md 13): sample from the tempered model, x_hat = sigmoid(logit /
+        temperature) and z = mean + exp(lv / 2) * z_temperature * eps, with the same Philox draws; xhat_out then holds the
+        tempered probabilities.  Both 1.0 (default): exactly the untempered launches."""
+        cfg, d = self.cfg, self.device
+        N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
+        clamp = clamp_roll(clamp, N, nsteps, D, d)
+        temper = temper_args(temperature, z_temperature)
+        f = dict(dtype=torch.float32, device=d)
+        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
+            Xs = torch.zeros(N, nsteps, D, **f)
+            ops.vae_generate(N, nsteps, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], z_prior, seed,
+                             x_seed.to(**f).contiguous(), w.to(**f).contiguous(), *self._weights(), Xs, xhat_out, clamp=clamp,
+                             temper=temper)
+            return Xs
+        rows = _VaeRows(self, N)
+        Xs = torch.zeros(N, nsteps, D, **f)
+        w = w.to(**f).contiguous()
+        chain = _Chain(rows, w, w, nsteps, seed, temper, 'enc_input', x_enc=x_seed.to(**f).clone(),
+                       x_dec=x_seed.to(**f).clone(), z_prior=z_prior, clamp=clamp)
+        chain.run(nsteps, use_graph, lambda t: chain.store(t, Xs))
+        return Xs
+
+    def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
+             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
+        """Re-decode sources [N, T, D] (DESIGN.md 14): per frame t the z-encoder on [sources[t], w_enc], z = mean +
+        exp(lv / 2) * Tz * eps, the decoder on [w_dec, xp, z] with xp the frame directly before t as in training: x0 (None:
+        zeros) at t = 0, then the sample of frame t-1 (history='own') or sources[t-1] ('source': the training forward pass);
+        x ~ Bernoulli(x_hat), then the roll clamp [N, T, D] (row t constrains frame t).  w_dec=None: w_enc (a variation);
+        another label: key transfer.  Noise as generate's (step = frame).  persistent=True (default where the shapes allow):
+        ONE kernel, a workgroup per sequence (the VR instance of csrc/vae_generate.hip; any N); else the layer chain,
+        captured once and replayed per frame (N <= batch size), reading its source frame through the device step counter.
+        Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities; zout [3, N, T, L]
+        (DESIGN.md 15) the latents (z_mean, z_log_var, z) of every frame."""
+        cfg, d = self.cfg, self.device
+        D, L = cfg['D'], cfg['L']
+        temper = temper_args(temperature, z_temperature)
+        sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, cfg['C'], d)
+        N, T = int(sources.shape[0]), int(sources.shape[1])
+        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
+        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
+            args = (N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], hist_source, seed, sources, x0, w_enc, w_dec,
+                    *self._weights(), Xs)
+            if zout is None:
+                ops.vae_vary(*args, xhat_out, clamp=clamp, temper=temper)
+            else:
+                ops.vae_vary_latents(*args, _zout_ok(zout, N, T, L), xhat_out, clamp=clamp, temper=temper)
+            return Xs
+        rows = _VaeRows(self, N)
+        if zout is not None:
+            _zout_ok(zout, N, T, L)
+        chain = _Chain(rows, w_enc, w_dec, T, seed, temper, 'enc_input' if hist_source else 'sample',
+                       x_dec=None if x0 is None else x0.clone(), sources=sources, clamp=clamp)
+        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out, zout))
+        return Xs
+
+    def decode_latents(self, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
+               persistent=True, use_graph=True, xhat_out=None):
+        """Decode the latent path z [N, T, L] (DESIGN.md 15): vary's loop without its z-encoder.  Per frame t the decoder on
+        [w_dec, xp, z[:, t]] with xp = x0 (None: zeros) at t = 0, then the sample of frame t-1 (history='own') or
+        history[:, t-1] (an [N, T, D] array: teacher forcing); x ~ Bernoulli(x_hat) with the uniforms of row noise_rows[n]
+        (None: n), then the roll.  No eps is drawn.  persistent=True (default where the shapes allow): ONE kernel, a
+        workgroup per sequence (the ZG instance of csrc/vae_generate.hip); else the layer chain, captured once and replayed
+        per frame (N <= batch size), reading z[:, t] and history[:, t-1] through the device step counter.  Returns Xs
+        [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
+        cfg, d = self.cfg, self.device
+        D, L = cfg['D'], cfg['L']
+        inv_T = decode_temper(temperature)
+        z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, cfg['C'], d)
+        N, T = int(z.shape[0]), int(z.shape[1])
+        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
+        if max(N * T * L, N * T * D) >= 2 ** 32:
+            persistent = False
+        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
+            ops.vae_decode(N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], seed, z, x0, hist, w_dec, noise_rows,
+                           *self._weights(encoder=False), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
+            return Xs
+        chain = _Chain(_VaeRows(self, N), None, w_dec, T, seed, None if inv_T == 1.0 else (inv_T, 1.0),
+                       'sample' if hist is None else hist, x_dec=None if x0 is None else x0.clone(), z_path=z,
+                       noise_rows=noise_rows, clamp=clamp)
+        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out))
+        return Xs
+
+    def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
+                     z_prior=False, chunk=None, w_prior=None, temperature=1.0, z_temperature=1.0):
+        """Particle-filter sampling under the constraint roll clamp [N, nsteps, D] (DESIGN.md 11): melody m runs P =
+        `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
+        probability of each frame's clamped notes and resampled (systematic, below an ESS of resample_threshold * P).
+        Row t of the roll constrains frame t.  Melodies are processed in chunks of at most batch-size rows (and at most
+        `chunk` melodies); the Philox keys follow the global row, so the result does not depend on the chunking.
+        x_seed [N, D], w [N, C] device tensors.  Returns SmcResult (Xs [N, n_out, nsteps, D]).
+        w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state, so the filter
+        targets p(w, free notes | seed, constraints) (DESIGN.md 12); returns SmcKeyResult.
+        temperature, z_temperature (temper_args, DESIGN.md 13): the filter runs on the TEMPERED model; its weights are the
+        tempered probabilities of the clamped notes, so log_evidence estimates log p_T(constraints | seed, w), the evidence
+        under the tempered model -- the trained model's only where both are 1."""
+        temper = temper_args(temperature, z_temperature)
+
+        def chain_of(xs, wr, r0, smc):
+            return _Chain(_VaeRows(self, smc.R), wr, wr, smc.nsteps, seed, temper, 'enc_input', x_enc=xs, x_dec=xs.clone(),
+                          z_prior=z_prior, r0=r0, smc=smc)
+
+        return _smc_run(self, 0, self.B, chain_of, x_seed, w, nsteps, clamp, particles, resample_threshold, n_out, seed,
+                        use_graph, chunk, w_prior)
 
 
 class VrnnGenerate:
@@ -738,6 +777,17 @@ class VrnnGenerate:
         g(st['hs'], P.p('X_decoded_mean/kernel'), st['xhat'], B, D, H, bias=P.p('X_decoded_mean/bias'),
           act=act, ws=ws)
 
+    def _weights(self, encoder=True):
+        """the persistent kernels' weight arguments in the order ops.vrnn_* take them: the encoder half (vrnn_decode takes
+        none), the decoder half, the head"""
+        p, L, off = self.P.p, self.cfg['L'], self.off
+        rows = lambda name, r: self.P.rows(self.P.params, name, r)
+        enc = (p('encoder_h/kernel'), rows('encoder_h/kernel', self.cfg['D']), p('encoder_h/bias'),
+               p('encoder_h/recurrent_kernel'), p('Zargs/kernel'), p('Zargs/bias')) if encoder else ()
+        return enc + (p('decoder_h/kernel') if self.cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
+                      rows('decoder_h/kernel', off + L), p('decoder_h/bias'), p('decoder_h/recurrent_kernel'),
+                      p('X_decoded_mean/kernel'), p('X_decoded_mean/bias'))
+
     def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None,
                  temperature=1.0, z_temperature=1.0):
         """Autoregressive generation of N independent sequences on the device.  persistent=True (default where the
@@ -763,17 +813,12 @@ class VrnnGenerate:
         return self._generate_frames(x_seed, w, nsteps, seed, use_graph, z_prior, clamp, temper)
 
     def _generate_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp=None, temper=None):
-        cfg, P, d = self.cfg, self.P, self.device
-        D, H, L, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.off
+        cfg = self.cfg
         N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
-        Xs = torch.zeros(N, nsteps, D, dtype=torch.float32, device=d)
-        rows = lambda name, r: P.rows(P.params, name, r)
-        ops.vrnn_generate(N, S, nsteps, D, H, L, Cn, self.gate_act, z_prior, seed, x_seed.contiguous() if S else None,
-                          w.contiguous(), P.p('encoder_h/kernel'), rows('encoder_h/kernel', D), P.p('encoder_h/bias'),
-                          P.p('encoder_h/recurrent_kernel'), P.p('Zargs/kernel'), P.p('Zargs/bias'),
-                          P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
-                          rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
-                          P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out, clamp=clamp, temper=temper)
+        Xs = torch.zeros(N, nsteps, cfg['D'], dtype=torch.float32, device=self.device)
+        ops.vrnn_generate(N, S, nsteps, cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.gate_act, z_prior, seed,
+                          x_seed.contiguous() if S else None, w.contiguous(), *self._weights(), Xs, xhat_out, clamp=clamp,
+                          temper=temper)
         return Xs
 
     def _generate_frames(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, clamp=None, temper=None):
@@ -782,49 +827,17 @@ class VrnnGenerate:
         x_seed [N,S,D] device tensor (teacher-forced frames, S may be 0), w [N,C]; returns Xs [N,nsteps,D].
         One frame = encoder step -> z ~ N(mean, exp(lv)) -> decoder step -> x ~ Bernoulli(x_hat); the chain
         is captured once and replayed per frame with no host synchronisation."""
-        cfg, d = self.cfg, self.device
         N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
-        D, L = cfg['D'], cfg['L']
-        f = dict(dtype=torch.float32, device=d)
-        st = self.new_state(N)
-        x_prev, x_next = torch.zeros(N, D, **f), torch.zeros(N, D, **f)
-        eps, u, z = torch.zeros(N, L, **f), torch.zeros(N, D, **f), torch.zeros(N, L, **f)
-        counter = torch.zeros(1, dtype=torch.int32, device=d)
-        Xs = torch.zeros(N, nsteps, D, **f)
+        Xs = torch.zeros(N, nsteps, self.cfg['D'], dtype=torch.float32, device=self.device)
         w = w.contiguous()
+        chain = _Chain(_VrnnRows(self, N), w, w, nsteps, seed, temper, 'shared', z_prior=z_prior, seed_frames=x_seed,
+                       clamp=clamp, S=S)
 
-        def frame():
-            self.enc_step(x_prev, w, st)
-            ops.philox_normal(eps, N * L, seed, 0, 0, 0, step_dev=counter)
-            if z_prior:
-                st['zargs'].zero_()
-            _temper_eps(temper, eps, N * L)
-            ops.gauss_fwd(N, L, st['zargs'], eps, z, L, None)
-            self.dec_step(z, x_prev if cfg['use_x_prev'] else None, w, st, act=_head_act(temper))
-            _temper_head(temper, st['xhat'], N * D)
-            ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
-            if clamp is None:
-                ops.bernoulli_sample(N * D, st['xhat'], u, x_next)
-            else:               # the row of step counter - S: none for the seed steps and the bridge
-                ops.bernoulli_sample_clamped(N * D, D, nsteps, S, st['xhat'], u, clamp, counter, x_next)
-            ops.i32_add(counter, 1)
-            x_prev.copy_(x_next)
-
-        if S == 0:
-            x_prev.zero_()
-        graph = None
-        for t in range(S + nsteps):
-            if t < S:
-                x_prev.copy_(x_seed[:, t])
-            if use_graph and t == 1:
-                with ops.Graph() as graph:       # step 0 ran eagerly and sized every workspace
-                    frame()
-            if graph is not None:
-                graph.launch()
-            else:
-                frame()
+        def after(t):
             if t >= S:
-                Xs[:, t - S].copy_(x_next)
+                chain.store(t - S, Xs)
+
+        chain.run(S + nsteps, use_graph, after)
         return Xs
 
     def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
@@ -839,13 +852,12 @@ class VrnnGenerate:
         counter.  A roll of 2^32 bytes or more takes the chain.  Returns Xs [N, T, D]; xhat_out [N, T, D] receives the
         unclamped (tempered) probabilities; zout [3, N, T, L] the latents (z_mean, z_log_var, z) of every
         frame."""
-        cfg, d, P = self.cfg, self.device, self.P
-        D, H, L, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.off
+        cfg, d = self.cfg, self.device
+        D, H, L, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['C']
         temper = temper_args(temperature, z_temperature)
         sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, Cn, d)
         N, T = int(sources.shape[0]), int(sources.shape[1])
-        f = dict(dtype=torch.float32, device=d)
-        Xs = torch.zeros(N, T, D, **f)
+        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
         if (clamp is not None and clamp.numel() >= 2 ** 32) or T * D * 4 >= 2 ** 32:
             persistent = False
         if zout is not None:
@@ -853,47 +865,15 @@ class VrnnGenerate:
             if zout.numel() >= 3 * 2 ** 32:
                 persistent = False
         if persistent and ops.vrnn_generate_supported(D, H, L, Cn):
-            rows = lambda name, r: P.rows(P.params, name, r)
-            args = (N, T, D, H, L, Cn, self.gate_act, hist_source, seed, sources, x0, w_enc, w_dec,
-                    P.p('encoder_h/kernel'), rows('encoder_h/kernel', D), P.p('encoder_h/bias'),
-                    P.p('encoder_h/recurrent_kernel'), P.p('Zargs/kernel'), P.p('Zargs/bias'),
-                    P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
-                    rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
-                    P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs)
+            args = (N, T, D, H, L, Cn, self.gate_act, hist_source, seed, sources, x0, w_enc, w_dec, *self._weights(), Xs)
             if zout is None:
                 ops.vrnn_vary(*args, xhat_out, clamp=clamp, temper=temper)
             else:
                 ops.vrnn_vary_latents(*args, zout, xhat_out, clamp=clamp, temper=temper)
             return Xs
-        st = self.new_state(N)
-        x_src, x_next = torch.zeros(N, D, **f), torch.zeros(N, D, **f)
-        xp = torch.zeros(N, D, **f) if x0 is None else x0.clone()
-        eps, u, z = torch.zeros(N, L, **f), torch.zeros(N, D, **f), torch.zeros(N, L, **f)
-        counter = torch.zeros(1, dtype=torch.int32, device=d)
-
-        def frame():
-            ops.take_frame(N, T, D, sources, counter, x_src)
-            self.enc_step(x_src, w_enc, st)
-            ops.philox_normal(eps, N * L, seed, 0, 0, 0, step_dev=counter)
-            _temper_eps(temper, eps, N * L)
-            ops.gauss_fwd(N, L, st['zargs'], eps, z, L, None)
-            self.dec_step(z, xp if cfg['use_x_prev'] else None, w_dec, st, act=_head_act(temper))
-            _temper_head(temper, st['xhat'], N * D)
-            ops.philox_uniform(u, N * D, seed, 0, 1, 0, step_dev=counter)
-            _vary_sample(N, D, T, st['xhat'], u, clamp, counter, x_next)
-            ops.i32_add(counter, 1)
-            xp.copy_(x_src if hist_source else x_next)
-
-        def after(t):
-            Xs[:, t].copy_(x_next)
-            if xhat_out is not None:
-                xhat_out[:, t].copy_(st['xhat'])
-            if zout is not None:
-                zout[0, :, t].copy_(st['zargs'][:, :L])
-                zout[1, :, t].copy_(st['zargs'][:, L:])
-                zout[2, :, t].copy_(z)
-
-        _replay(frame, T, use_graph, after=after)
+        chain = _Chain(_VrnnRows(self, N), w_enc, w_dec, T, seed, temper, 'enc_input' if hist_source else 'sample',
+                       x_dec=None if x0 is None else x0.clone(), sources=sources, clamp=clamp)
+        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out, zout))
         return Xs
 
     def decode_latents(self, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
@@ -906,48 +886,22 @@ class VrnnGenerate:
         csrc/generate.hip); else the per-frame chain, captured once and replayed per frame, reading z[:, t] and
         history[:, t-1] through the device step counter.  N*T*L or N*T*D of 2^32 or more takes the chain.  Returns Xs
         [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
-        cfg, d, P = self.cfg, self.device, self.P
-        D, H, L, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.off
+        cfg, d = self.cfg, self.device
+        D, H, L, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['C']
         inv_T = decode_temper(temperature)
-        temper = None if inv_T == 1.0 else (inv_T, 1.0)
         z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, Cn, d)
         N, T = int(z.shape[0]), int(z.shape[1])
-        f = dict(dtype=torch.float32, device=d)
-        Xs = torch.zeros(N, T, D, **f)
+        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
         if max(N * T * L, N * T * D) >= 2 ** 32:
             persistent = False
         if persistent and ops.vrnn_generate_supported(D, H, L, Cn):
-            rows = lambda name, r: P.rows(P.params, name, r)
             ops.vrnn_decode(N, T, D, H, L, Cn, self.gate_act, seed, z, x0, hist, w_dec, noise_rows,
-                            P.p('decoder_h/kernel') if cfg['use_x_prev'] else None, rows('decoder_h/kernel', off),
-                            rows('decoder_h/kernel', off + L), P.p('decoder_h/bias'), P.p('decoder_h/recurrent_kernel'),
-                            P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
+                            *self._weights(encoder=False), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
             return Xs
-        st = self.new_state(N)
-        x_next, z_t = torch.zeros(N, D, **f), torch.zeros(N, L, **f)
-        xp = torch.zeros(N, D, **f) if x0 is None else x0.clone()
-        u = torch.zeros(N, D, **f)
-        counter = torch.zeros(1, dtype=torch.int32, device=d)
-        noise = _NoiseRows(noise_rows, N, D, d)
-
-        def frame():
-            ops.take_frame(N, T, L, z, counter, z_t)
-            self.dec_step(z_t, xp if cfg['use_x_prev'] else None, w_dec, st, act=_head_act(temper))
-            _temper_head(temper, st['xhat'], N * D)
-            noise.draw(u, seed, counter)
-            _vary_sample(N, D, T, st['xhat'], u, clamp, counter, x_next)
-            if hist is None:
-                xp.copy_(x_next)
-            else:
-                ops.take_frame(N, T, D, hist, counter, xp)      # history[:, t]: the previous frame of step t+1
-            ops.i32_add(counter, 1)
-
-        def after(t):
-            Xs[:, t].copy_(x_next)
-            if xhat_out is not None:
-                xhat_out[:, t].copy_(st['xhat'])
-
-        _replay(frame, T, use_graph, after=after)
+        chain = _Chain(_VrnnRows(self, N), None, w_dec, T, seed, None if inv_T == 1.0 else (inv_T, 1.0),
+                       'sample' if hist is None else hist, x_dec=None if x0 is None else x0.clone(), z_path=z,
+                       noise_rows=noise_rows, clamp=clamp)
+        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out))
         return Xs
 
     def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
@@ -964,53 +918,12 @@ class VrnnGenerate:
         temperature, z_temperature (temper_args): the filter runs on the TEMPERED model; its weights are the
         tempered probabilities of the clamped notes, so log_evidence estimates log p_T(constraints | seed, w), the evidence
         under the tempered model -- the trained model's only where both are 1."""
-        cfg, d = self.cfg, self.device
-        N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
-        D, L = cfg['D'], cfg['L']
+        S = int(x_seed.shape[1])
         temper = temper_args(temperature, z_temperature)
-        clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
-        P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
-        f = dict(dtype=torch.float32, device=d)
-        x_seed = x_seed.to(**f)
-        w, prior = smc_label_args(w, w_prior, N, cfg['C'], d)
 
-        def run_chunk(m0, m1):
-            G = m1 - m0
-            R, r0 = G * P, m0 * P
-            xs = x_seed[m0:m1].repeat_interleave(P, 0)
-            if prior is None:
-                wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
-            else:
-                wr = torch.zeros(R, cfg['C'], **f)
-                prior.init_rows(m0, m1, P, seed, wr)
-            st = self.new_state(R)
-            x_prev, x_next = torch.zeros(R, D, **f), torch.zeros(R, D, **f)
-            eps, u, z = torch.zeros(R, L, **f), torch.zeros(R, D, **f), torch.zeros(R, L, **f)
-            counter = torch.zeros(1, dtype=torch.int32, device=d)
-            smc = _Smc(G, P, nsteps, S, D, tau, seed, m0, clamp[m0:m1], d, wr=None if prior is None else wr)
-            gather = ops.SmcGather(R, P, nsteps, S, [st['h_enc'], st['c_enc'], st['h_dec'], st['c_dec'], x_next]
-                                   + ([] if prior is None else [wr]))     # a particle's own key travels with its state
+        def chain_of(xs, wr, r0, smc):
+            return _Chain(_VrnnRows(self, smc.R), wr, wr, smc.nsteps, seed, temper, 'shared', z_prior=z_prior, seed_frames=xs,
+                          r0=r0, smc=smc)
 
-            def frame():
-                self.enc_step(x_prev, wr, st)
-                ops.philox_normal(eps, R * L, seed, 0, 0, r0 * L, step_dev=counter)
-                if z_prior:
-                    st['zargs'].zero_()
-                _temper_eps(temper, eps, R * L)
-                ops.gauss_fwd(R, L, st['zargs'], eps, z, L, None)
-                self.dec_step(z, x_prev if cfg['use_x_prev'] else None, wr, st, act=_head_act(temper))
-                _temper_head(temper, st['xhat'], R * D)
-                ops.philox_uniform(u, R * D, seed, 0, 1, r0 * D, step_dev=counter)
-                smc.step(st['xhat'], u, counter, x_next, gather)
-                ops.i32_add(counter, 1)
-                x_prev.copy_(x_next)
-
-            def before(t):
-                if t < S:
-                    x_prev.copy_(xs[:, t])
-
-            _replay(frame, S + nsteps, use_graph, before)
-            return smc
-
-        return _smc_drive(_smc_chunks(N, P, None, chunk), run_chunk, N, nsteps, D, int(n_out), d,
-                          C=None if prior is None else cfg['C'])
+        return _smc_run(self, S, None, chain_of, x_seed, w, nsteps, clamp, particles, resample_threshold, n_out, seed,
+                        use_graph, chunk, w_prior)
