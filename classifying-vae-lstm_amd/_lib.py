@@ -115,6 +115,21 @@ class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
 
+# The argument lists of the twelve entry points of the persistent sampling kernels, in named pieces: a count is the number
+# of names in its piece, never typed by hand.  gate_act is cl_vrnn's, use_x_prev cl_vae's, at the same place.
+def _args(kind, names):
+    return [kind] * len(names.split())
+
+
+_VRNN_GENERATE = _args(_i, "N S nsteps D H L C gate_act z_prior") + [_u64] + _args(_p, "x_seed w")            # _u64: seed
+_VAE_GENERATE = _args(_i, "N nsteps D H L C use_x_prev z_prior") + [_u64] + _args(_p, "x_seed w")
+_VARY = _args(_i, "N T D H L C gate_act|use_x_prev hist_source") + [_u64] + _args(_p, "sources x0 w_enc w_dec")
+_DECODE = _args(_i, "N T D H L C gate_act|use_x_prev") + [_u64] + _args(_p, "z_in x0 history w_dec noise_rows")
+_VRNN_ENC, _VRNN_DEC = _args(_p, "Kx_enc Kw_enc b_enc U_enc Wz bz"), _args(_p, "Kx_dec Kz Kw_dec b_dec U_dec Wo bo")
+_VAE_ENC, _VAE_DEC = _args(_p, "Kh bh Kz bz"), _args(_p, "Kd bd Ko bo")
+_TEMPER = [_p, _f, _f]                                 # clamp, inv_temperature, z_temperature (decode: the first two)
+_OUT, _OUT_Z = _args(_p, "Xs xhat stream"), _args(_p, "Xs xhat zout stream")
+
 # name -> (restype, argtypes); must list every function of include/clvae.h
 SIGNATURES = {
     "clv_version": (_i, []),
@@ -171,20 +186,20 @@ SIGNATURES = {
     "clv_latent_head_fwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "clv_latent_head_bwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "clv_vrnn_generate_supported": (_i, [_i, _i, _i, _i]),
-    "clv_vrnn_generate": (_i, [_i] * 9 + [_u64] + [_p] * 18),
+    "clv_vrnn_generate": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _OUT),
     "clv_vae_generate_supported": (_i, [_i, _i, _i, _i]),
-    "clv_vae_generate": (_i, [_i] * 8 + [_u64] + [_p] * 13),
-    "clv_vrnn_generate_clamped": (_i, [_i] * 9 + [_u64] + [_p] * 19),
-    "clv_vae_generate_clamped": (_i, [_i] * 8 + [_u64] + [_p] * 14),
-    "clv_vrnn_generate_tempered": (_i, [_i] * 9 + [_u64] + [_p] * 16 + [_f, _f] + [_p] * 3),
-    "clv_vae_generate_tempered": (_i, [_i] * 8 + [_u64] + [_p] * 11 + [_f, _f] + [_p] * 3),
-    "clv_vrnn_vary": (_i, [_i] * 8 + [_u64] + [_p] * 18 + [_f, _f] + [_p] * 3),
-    "clv_vae_vary": (_i, [_i] * 8 + [_u64] + [_p] * 13 + [_f, _f] + [_p] * 3),
+    "clv_vae_generate": (_i, _VAE_GENERATE + _VAE_ENC + _VAE_DEC + _OUT),
+    "clv_vrnn_generate_clamped": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _args(_p, "clamp") + _OUT),
+    "clv_vae_generate_clamped": (_i, _VAE_GENERATE + _VAE_ENC + _VAE_DEC + _args(_p, "clamp") + _OUT),
+    "clv_vrnn_generate_tempered": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _TEMPER + _OUT),
+    "clv_vae_generate_tempered": (_i, _VAE_GENERATE + _VAE_ENC + _VAE_DEC + _TEMPER + _OUT),
+    "clv_vrnn_vary": (_i, _VARY + _VRNN_ENC + _VRNN_DEC + _TEMPER + _OUT),
+    "clv_vae_vary": (_i, _VARY + _VAE_ENC + _VAE_DEC + _TEMPER + _OUT),
     "clv_take_frame": (_i, [_i64, _i, _i, _p, _p, _p, _p]),
-    "clv_vrnn_vary_latents": (_i, [_i] * 8 + [_u64] + [_p] * 18 + [_f, _f] + [_p] * 4),
-    "clv_vae_vary_latents": (_i, [_i] * 8 + [_u64] + [_p] * 13 + [_f, _f] + [_p] * 4),
-    "clv_vrnn_decode": (_i, [_i] * 7 + [_u64] + [_p] * 13 + [_f] + [_p] * 3),
-    "clv_vae_decode": (_i, [_i] * 7 + [_u64] + [_p] * 10 + [_f] + [_p] * 3),
+    "clv_vrnn_vary_latents": (_i, _VARY + _VRNN_ENC + _VRNN_DEC + _TEMPER + _OUT_Z),
+    "clv_vae_vary_latents": (_i, _VARY + _VAE_ENC + _VAE_DEC + _TEMPER + _OUT_Z),
+    "clv_vrnn_decode": (_i, _DECODE + _VRNN_DEC + _TEMPER[:2] + _OUT),
+    "clv_vae_decode": (_i, _DECODE + _VAE_DEC + _TEMPER[:2] + _OUT),
     "clv_lerp_rows": (_i, [_i64, _i64] + [_p] * 7),
     "clv_sigmoid_temper": (_i, [_i64, _p, _f, _p]),
     "clv_scale_temper": (_i, [_i64, _p, _f, _p]),

@@ -464,109 +464,93 @@ extern "C" int clv_vrnn_generate_supported(int D, int H, int L, int C) {
 }
 
 namespace {
-template <bool CL, bool TP>
-void (*pick_vrnn_generate(bool hard, bool wide))(clv::GenArgs) {
-  using namespace clv;
-  return hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, CL, TP> : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, CL, TP>)
-              : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, CL, TP> : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, CL, TP>);
+using GenKernel = void (*)(clv::GenArgs);
+enum class Mode { generate, vary, decode };   // ancestral sampling | re-decoding | a given latent path
+
+// a runtime flag as a template argument: f(std::true_type) or f(std::false_type)
+template <class F>
+GenKernel with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// The one kernel pick.  Every flag becomes a template argument once: first the mode's own tail of (CL, TP, VR, ZO, ZG) --
+// generate takes CL and TP as they come, vary and decode are the clamped, tempered VR instances with ZO or ZG -- then the
+// gate and ZW.  (4 + 2 + 1) tails x 2 gates x 2 widths = the 28 instances, none that the kernel's static_assert forbids.
+template <bool... TAIL>
+GenKernel pick_gate_width(bool hard, bool wide) {
+  return with_bool(hard, [=](auto HARD) { return with_bool(wide, [](auto ZW) -> GenKernel {
+    return clv::vrnn_generate_kernel<decltype(HARD)::value ? CLV_GATE_HARD_SIGMOID : CLV_GATE_SIGMOID, decltype(ZW)::value, TAIL...>; }); });
 }
 
-int vrnn_generate_launch(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior, uint64_t seed,
-                         const float* x_seed, const float* w, const float* Kx_enc, const float* Kw_enc, const float* b_enc,
-                         const float* U_enc, const float* Wz, const float* bz, const float* Kx_dec, const float* Kz,
-                         const float* Kw_dec, const float* b_dec, const float* U_dec, const float* Wo, const float* bo,
-                         const uint8_t* clamp, bool tempered, float inv_T, float Tz, float* Xs, float* xhat, void* stream) {
+GenKernel pick_vrnn_kernel(Mode mode, bool hard, bool wide, bool clamped, bool tempered, bool latents_out) {
+  switch (mode) {
+    case Mode::generate:
+      return with_bool(tempered, [=](auto TP) { return with_bool(clamped, [=](auto CL) {
+        return pick_gate_width<decltype(CL)::value, decltype(TP)::value>(hard, wide); }); });
+    case Mode::vary:
+      return with_bool(latents_out, [=](auto ZO) { return pick_gate_width<true, true, true, decltype(ZO)::value>(hard, wide); });
+    default:                   // Mode::decode
+      return pick_gate_width<true, true, true, false, true>(hard, wide);
+  }
+}
+
+// The one launcher: every refusal of the six entry points, the kernel pick and the launch.  `a` is the call as its entry
+// point filled it (vary and decode: S = 0, nsteps = T; absent inputs null; absent temperatures 1.0f, which is exact).
+int vrnn_launch(const clv::GenArgs& a, Mode mode, bool tempered, int D, int H, int gate_act, void* stream) {
   using namespace clv;
-  if (!clv_vrnn_generate_supported(D, H, L, C) || N <= 0 || S < 0 || nsteps < 0 || S + nsteps <= 0) return CLV_EINVAL;
+  const bool decode = mode == Mode::decode;
+  // ---- every mode: shapes, gate, temperatures, the decoder half with the head, the roll's 32-bit addressing
+  if (!clv_vrnn_generate_supported(D, H, a.L, a.C) || a.N <= 0 || a.S < 0 || a.nsteps < 0 || a.S + a.nsteps <= 0) return CLV_EINVAL;
   if (gate_act != CLV_GATE_HARD_SIGMOID && gate_act != CLV_GATE_SIGMOID) return CLV_EINVAL;
-  if ((S > 0 && !x_seed) || !w || !Kx_enc || !Kw_enc || !b_enc || !U_enc || !Wz || !bz || !Kz || !Kw_dec || !b_dec ||
-      !U_dec || !Wo || !bo || (nsteps > 0 && !Xs))
+  if (!temper_factor_ok(a.inv_T, false) || !temper_factor_ok(a.Tz, true)) return CLV_EINVAL;
+  if (!a.Kz || !a.Kw_dec || !a.b_dec || !a.U_dec || !a.Wo || !a.bo) return CLV_EINVAL;
+  const uint64_t frames = (uint64_t)a.N * a.nsteps;                            // the kernel addresses these in 32 bits:
+  if ((a.clamp || decode) && frames * LH > UINT32_MAX) return CLV_EINVAL;      // the roll (decode: and the history frames)
+  // ---- the modes with an encoder: its label, its half of the weights, Kx_enc staged to LDS in 16-byte pieces
+  if (!decode && (!a.w || !a.Kx_enc || !a.Kw_enc || !a.b_enc || !a.U_enc || !a.Wz || !a.bz || ((uintptr_t)a.Kx_enc) % 16 != 0))
     return CLV_EINVAL;
-  if (((uintptr_t)Kx_enc) % 16 != 0) return CLV_EINVAL;
-  if (clamp && (uint64_t)N * nsteps * LH > UINT32_MAX) return CLV_EINVAL;      // the kernel addresses the roll in 32 bits
+  // ---- each mode's own inputs
+  switch (mode) {
+    case Mode::generate:       // seed frames only if S > 0, samples only if nsteps > 0; a roll constrains at least one step
+      if ((a.S > 0 && !a.x_seed) || (a.nsteps > 0 && !a.Xs) || (a.clamp && a.nsteps <= 0)) return CLV_EINVAL;
+      break;
+    case Mode::vary:           // x_seed: the source frames, a sequence's addressed in 32 bits, as are the latents out
+      if (!a.x_seed || !a.w_dec || !a.Xs) return CLV_EINVAL;
+      if ((uint64_t)a.nsteps * LH * sizeof(float) > UINT32_MAX || (a.zout && frames * a.L > UINT32_MAX)) return CLV_EINVAL;
+      break;
+    case Mode::decode:         // x_seed: the history frames, or null; the latents in are addressed in 32 bits
+      if (!a.z_in || !a.w_dec || !a.Xs || frames * a.L > UINT32_MAX) return CLV_EINVAL;
+      break;
+  }
+  GenKernel kern = pick_vrnn_kernel(mode, gate_act == CLV_GATE_HARD_SIGMOID, a.L > GN_LMAX, a.clamp != nullptr, tempered, a.zout != nullptr);
+  const size_t lds = (size_t)((decode ? 0 : LH * LG) + LH * LH) * sizeof(float);    // Kx_enc (with an encoder) and Wo
+  if (!decode)
+    if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 156 * 1024)) return e;
+  const char* label = decode ? "vrnn_decode" : mode == Mode::vary ? (a.zout ? "vrnn_vary_latents" : "vrnn_vary")
+                      : tempered ? (a.clamp ? "vrnn_generate_tempered_clamped" : "vrnn_generate_tempered")
+                                 : (a.clamp ? "vrnn_generate_clamped" : "vrnn_generate");
   hipStream_t s = (hipStream_t)stream;
-  GenArgs a{N, S, nsteps, L, C, z_prior, Kx_dec != nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), x_seed, w,
-            Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp, inv_T, Tz};
-  const size_t lds = (size_t)(LH * LG + LH * LH) * sizeof(float);
-  const bool hard = gate_act == CLV_GATE_HARD_SIGMOID, wide = L > GN_LMAX;
-  void (*kern)(GenArgs);
-  if (tempered)
-    kern = clamp ? pick_vrnn_generate<true, true>(hard, wide) : pick_vrnn_generate<false, true>(hard, wide);
-  else
-    kern = clamp ? pick_vrnn_generate<true, false>(hard, wide) : pick_vrnn_generate<false, false>(hard, wide);
-  if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 156 * 1024)) return e;
-  ProfScope p(tempered ? (clamp ? "vrnn_generate_tempered_clamped" : "vrnn_generate_tempered")
-                       : (clamp ? "vrnn_generate_clamped" : "vrnn_generate"), s);
-  hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
+  ProfScope p(label, s);
+  hipLaunchKernelGGL(kern, dim3(a.N), dim3(GN_NT), lds, s, a);
   return launch_status();
 }
 
-// re-decoding: the VR instances, always clamped (a null roll is all free) and tempered (1.0f is exact)
-int vrnn_vary_launch(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
-                     const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kx_enc,
-                     const float* Kw_enc, const float* b_enc, const float* U_enc, const float* Wz, const float* bz,
-                     const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec, const float* U_dec,
-                     const float* Wo, const float* bo, const uint8_t* clamp, float inv_T, float Tz, float* Xs, float* xhat,
-                     float* zout, void* stream) {
-  using namespace clv;
-  if (!clv_vrnn_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
-  if (zout && (uint64_t)N * T * L > UINT32_MAX) return CLV_EINVAL;             // the latents are addressed in 32 bits
-  if (gate_act != CLV_GATE_HARD_SIGMOID && gate_act != CLV_GATE_SIGMOID) return CLV_EINVAL;
-  if (!temper_factor_ok(inv_T, false) || !temper_factor_ok(Tz, true)) return CLV_EINVAL;
-  if (!sources || !w_enc || !w_dec || !Kx_enc || !Kw_enc || !b_enc || !U_enc || !Wz || !bz || !Kz || !Kw_dec || !b_dec ||
-      !U_dec || !Wo || !bo || !Xs)
-    return CLV_EINVAL;
-  if (((uintptr_t)Kx_enc) % 16 != 0) return CLV_EINVAL;
-  if (clamp && (uint64_t)N * T * LH > UINT32_MAX) return CLV_EINVAL;          // the kernel addresses the roll in 32 bits
-  if ((uint64_t)T * LH * sizeof(float) > UINT32_MAX) return CLV_EINVAL;       // and a sequence's source frames likewise
-  hipStream_t s = (hipStream_t)stream;
-  GenArgs a{N, 0, T, L, C, 0, Kx_dec != nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), sources, w_enc,
-            Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp, inv_T, Tz,
-            w_dec, x0, hist_source != 0, zout, nullptr, nullptr};
-  const size_t lds = (size_t)(LH * LG + LH * LH) * sizeof(float);
-  const bool hard = gate_act == CLV_GATE_HARD_SIGMOID, wide = L > GN_LMAX;
-  void (*kern)(GenArgs) =
-      zout ? (hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true, true, true, true>
-                           : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true, true, true, true>)
-                   : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true, true, true, true>
-                           : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true, true, true, true>))
-           : (hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true, true, true>
-                           : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true, true, true>)
-                   : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true, true, true>
-                           : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true, true, true>));
-  if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 156 * 1024)) return e;
-  ProfScope p(zout ? "vrnn_vary_latents" : "vrnn_vary", s);
-  hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
-  return launch_status();
+// what every entry point fills alike; everything else starts absent (null, 0) and untempered
+clv::GenArgs vrnn_args(int N, int S, int nsteps, int L, int C, uint64_t seed, const uint8_t* clamp, float* Xs, float* xhat) {
+  clv::GenArgs a{};
+  a.N = N; a.S = S; a.nsteps = nsteps; a.L = L; a.C = C;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
+  a.clamp = clamp; a.inv_T = 1.f; a.Tz = 1.f; a.Xs = Xs; a.xhat = xhat;
+  return a;
 }
 
-// decoding a given latent path: the ZG instances.  No encoder: its weights, label and sources are absent
-int vrnn_decode_launch(int N, int T, int D, int H, int L, int C, int gate_act, uint64_t seed, const float* z_in,
-                       const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
-                       const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec, const float* U_dec,
-                       const float* Wo, const float* bo, const uint8_t* clamp, float inv_T, float* Xs, float* xhat,
-                       void* stream) {
-  using namespace clv;
-  if (!clv_vrnn_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
-  if (gate_act != CLV_GATE_HARD_SIGMOID && gate_act != CLV_GATE_SIGMOID) return CLV_EINVAL;
-  if (!temper_factor_ok(inv_T, false)) return CLV_EINVAL;
-  if (!z_in || !w_dec || !Kz || !Kw_dec || !b_dec || !U_dec || !Wo || !bo || !Xs) return CLV_EINVAL;
-  // the kernel addresses the latents, the roll and a sequence's history frames in 32 bits
-  if ((uint64_t)N * T * L > UINT32_MAX || (uint64_t)N * T * LH > UINT32_MAX) return CLV_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  GenArgs a{N, 0, T, L, C, 0, Kx_dec != nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), history, nullptr,
-            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat, clamp,
-            inv_T, 1.f, w_dec, x0, history != nullptr, nullptr, z_in, noise_rows};
-  const size_t lds = (size_t)(LH * LH) * sizeof(float);
-  const bool hard = gate_act == CLV_GATE_HARD_SIGMOID, wide = L > GN_LMAX;
-  void (*kern)(GenArgs) =
-      hard ? (wide ? vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, true, true, true, true, false, true>
-                   : vrnn_generate_kernel<CLV_GATE_HARD_SIGMOID, false, true, true, true, false, true>)
-           : (wide ? vrnn_generate_kernel<CLV_GATE_SIGMOID, true, true, true, true, false, true>
-                   : vrnn_generate_kernel<CLV_GATE_SIGMOID, false, true, true, true, false, true>);
-  ProfScope p("vrnn_decode", s);
-  hipLaunchKernelGGL(kern, dim3(N), dim3(GN_NT), lds, s, a);
-  return launch_status();
+void set_encoder(clv::GenArgs& a, const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                 const float* Wz, const float* bz) {
+  a.Kx_enc = Kx_enc; a.Kw_enc = Kw_enc; a.b_enc = b_enc; a.U_enc = U_enc; a.Wz = Wz; a.bz = bz;
+}
+
+void set_decoder(clv::GenArgs& a, const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                 const float* U_dec, const float* Wo, const float* bo) {
+  a.has_xp = Kx_dec != nullptr;
+  a.Kx_dec = Kx_dec; a.Kz = Kz; a.Kw_dec = Kw_dec; a.b_dec = b_dec; a.U_dec = U_dec; a.Wo = Wo; a.bo = bo;
 }
 }  // namespace
 
@@ -577,8 +561,11 @@ extern "C" int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, 
                                  const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                                  const float* U_dec, const float* Wo, const float* bo,
                                  float* Xs, float* xhat, void* stream) {
-  return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
-                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, nullptr, false, 1.f, 1.f, Xs, xhat, stream);
+  clv::GenArgs a = vrnn_args(N, S, nsteps, L, C, seed, nullptr, Xs, xhat);
+  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
+  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
+  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w;
+  return vrnn_launch(a, Mode::generate, false, D, H, gate_act, stream);
 }
 
 extern "C" int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
@@ -588,9 +575,12 @@ extern "C" int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H,
                                          const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                                          const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                                          float* Xs, float* xhat, void* stream) {
-  if (!clamp || nsteps <= 0) return CLV_EINVAL;
-  return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
-                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, false, 1.f, 1.f, Xs, xhat, stream);
+  if (!clamp) return CLV_EINVAL;             // this entry point is the roll
+  clv::GenArgs a = vrnn_args(N, S, nsteps, L, C, seed, clamp, Xs, xhat);
+  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
+  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
+  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w;
+  return vrnn_launch(a, Mode::generate, false, D, H, gate_act, stream);
 }
 
 extern "C" int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
@@ -600,23 +590,11 @@ extern "C" int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H
                                           const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                                           const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                                           float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream) {
-  if (!clv::temper_factor_ok(inv_temperature, false) || !clv::temper_factor_ok(z_temperature, true)) return CLV_EINVAL;
-  if (clamp && nsteps <= 0) return CLV_EINVAL;
-  return vrnn_generate_launch(N, S, nsteps, D, H, L, C, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
-                              bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, true, inv_temperature, z_temperature, Xs,
-                              xhat, stream);
-}
-
-extern "C" int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
-                             const float* sources, const float* x0, const float* w_enc, const float* w_dec,
-                             const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                             const float* Wz, const float* bz,
-                             const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                             const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                             float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream) {
-  return vrnn_vary_launch(N, T, D, H, L, C, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc,
-                          U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, inv_temperature, z_temperature, Xs,
-                          xhat, nullptr, stream);
+  clv::GenArgs a = vrnn_args(N, S, nsteps, L, C, seed, clamp, Xs, xhat);
+  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
+  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
+  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
+  return vrnn_launch(a, Mode::generate, true, D, H, gate_act, stream);
 }
 
 extern "C" int clv_vrnn_vary_latents(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
@@ -627,9 +605,27 @@ extern "C" int clv_vrnn_vary_latents(int N, int T, int D, int H, int L, int C, i
                                      const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                                      float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout,
                                      void* stream) {
-  return vrnn_vary_launch(N, T, D, H, L, C, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc,
-                          U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp, inv_temperature, z_temperature, Xs,
-                          xhat, zout, stream);
+  clv::GenArgs a = vrnn_args(N, 0, T, L, C, seed, clamp, Xs, xhat);
+  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
+  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
+  a.x_seed = sources; a.x0 = x0; a.w = w_enc; a.w_dec = w_dec; a.hist_source = hist_source != 0;
+  a.inv_T = inv_temperature; a.Tz = z_temperature; a.zout = zout;
+  return vrnn_launch(a, Mode::vary, true, D, H, gate_act, stream);
+}
+
+extern "C" int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
+                             const float* sources, const float* x0, const float* w_enc, const float* w_dec,
+                             const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                             const float* Wz, const float* bz,
+                             const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                             const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                             float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream) {
+  clv::GenArgs a = vrnn_args(N, 0, T, L, C, seed, clamp, Xs, xhat);
+  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
+  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
+  a.x_seed = sources; a.x0 = x0; a.w = w_enc; a.w_dec = w_dec; a.hist_source = hist_source != 0;
+  a.inv_T = inv_temperature; a.Tz = z_temperature;
+  return vrnn_launch(a, Mode::vary, true, D, H, gate_act, stream);
 }
 
 extern "C" int clv_vrnn_decode(int N, int T, int D, int H, int L, int C, int gate_act, uint64_t seed, const float* z_in,
@@ -637,6 +633,9 @@ extern "C" int clv_vrnn_decode(int N, int T, int D, int H, int L, int C, int gat
                                const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                                const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                                float inv_temperature, float* Xs, float* xhat, void* stream) {
-  return vrnn_decode_launch(N, T, D, H, L, C, gate_act, seed, z_in, x0, history, w_dec, noise_rows, Kx_dec, Kz, Kw_dec, b_dec,
-                            U_dec, Wo, bo, clamp, inv_temperature, Xs, xhat, stream);
+  clv::GenArgs a = vrnn_args(N, 0, T, L, C, seed, clamp, Xs, xhat);
+  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
+  a.x_seed = history; a.hist_source = history != nullptr; a.x0 = x0; a.w_dec = w_dec;
+  a.z_in = z_in; a.noise_rows = noise_rows; a.inv_T = inv_temperature;
+  return vrnn_launch(a, Mode::decode, true, D, H, gate_act, stream);
 }

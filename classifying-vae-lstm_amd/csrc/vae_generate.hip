@@ -245,85 +245,98 @@ extern "C" int clv_vae_generate_supported(int D, int H, int L, int C) {
 }
 
 namespace {
-int vae_generate_launch(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
-                        const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz, const float* bz,
-                        const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp, bool tempered,
-                        float inv_T, float Tz, float* Xs, float* xhat, void* stream) {
+using VaeKernel = void (*)(clv::VaeGenArgs);
+enum class Mode { generate, vary, decode };   // ancestral sampling | re-decoding | a given latent path
+
+// a runtime flag as a template argument: f(std::true_type) or f(std::false_type)
+template <class F>
+VaeKernel with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+// The one kernel pick.  Every flag becomes a template argument once: generate takes CL and TP as they come, vary and decode
+// are the clamped, tempered VR instances with ZO or ZG: the 4 + 2 + 1 instances, none that the kernel's static_assert forbids.
+VaeKernel pick_vae_kernel(Mode mode, bool clamped, bool tempered, bool latents_out) {
   using namespace clv;
-  if (!clv_vae_generate_supported(D, H, L, C) || N <= 0 || nsteps <= 0) return CLV_EINVAL;
-  if (!x_seed || !w || !Kh || !bh || !Kz || !bz || !Kd || !bd || !Ko || !bo || !Xs) return CLV_EINVAL;
+  switch (mode) {
+    case Mode::generate:
+      return with_bool(tempered, [=](auto TP) { return with_bool(clamped, [](auto CL) -> VaeKernel {
+        return vae_generate_kernel<decltype(CL)::value, decltype(TP)::value>; }); });
+    case Mode::vary:
+      return with_bool(latents_out, [](auto ZO) -> VaeKernel { return vae_generate_kernel<true, true, true, decltype(ZO)::value>; });
+    default:                   // Mode::decode
+      return vae_generate_kernel<true, true, true, false, true>;
+  }
+}
+
+// The one launcher: every refusal of the six entry points, the kernel pick and the launch.  `a` is the call as its entry
+// point filled it (vary and decode: nsteps = T; absent inputs null; absent temperatures 1.0f, which is exact).
+int vae_launch(const clv::VaeGenArgs& a, Mode mode, bool tempered, int D, int H, void* stream) {
+  using namespace clv;
+  const bool decode = mode == Mode::decode;
+  // ---- every mode: shapes, temperatures, the decoder half with the output layer, the samples
+  if (!clv_vae_generate_supported(D, H, a.L, a.C) || a.N <= 0 || a.nsteps <= 0) return CLV_EINVAL;
+  if (!temper_factor_ok(a.inv_T, false) || !temper_factor_ok(a.Tz, true)) return CLV_EINVAL;
+  if (!a.Kd || !a.bd || !a.Ko || !a.bo || !a.Xs) return CLV_EINVAL;
+  // ---- the modes with a z-encoder: its frames (x_seed: the seed frame or the sources), its label, its half of the weights
+  if (!decode && (!a.x_seed || !a.w || !a.Kh || !a.bh || !a.Kz || !a.bz)) return CLV_EINVAL;
+  // ---- each mode's own inputs; what the kernel addresses in 32 bits
+  const uint64_t frames = (uint64_t)a.N * a.nsteps;
+  switch (mode) {
+    case Mode::generate:       // nothing more (this family sets no bound on the roll)
+      break;
+    case Mode::vary:           // the latents out
+      if (!a.w_dec || (a.zout && frames * a.L > UINT32_MAX)) return CLV_EINVAL;
+      break;
+    case Mode::decode:         // x_seed: the history frames, or null; the latents in, the roll and the history frames
+      if (!a.z_in || !a.w_dec || frames * a.L > UINT32_MAX || frames * LH > UINT32_MAX) return CLV_EINVAL;
+      break;
+  }
+  VaeKernel kern = pick_vae_kernel(mode, a.clamp != nullptr, tempered, a.zout != nullptr);
+  const size_t lds = (size_t)((decode ? 1 : 2) * LH * LH + VG_LMAX * LH) * sizeof(float);   // K_h's frame rows go with the z-encoder
+  if (!decode)
+    if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 96 * 1024)) return e;
+  const char* label = decode ? "vae_decode" : mode == Mode::vary ? (a.zout ? "vae_vary_latents" : "vae_vary")
+                      : tempered ? (a.clamp ? "vae_generate_tempered_clamped" : "vae_generate_tempered")
+                                 : (a.clamp ? "vae_generate_clamped" : "vae_generate");
   hipStream_t s = (hipStream_t)stream;
-  VaeGenArgs a{N, nsteps, L, C, z_prior, use_x_prev != 0, (uint32_t)seed, (uint32_t)(seed >> 32), x_seed, w, Kh, bh, Kz, bz, Kd, bd,
-               Ko, bo, Xs, xhat, clamp, inv_T, Tz};
-  const size_t lds = (size_t)(2 * LH * LH + VG_LMAX * LH) * sizeof(float);
-  void (*kern)(VaeGenArgs) = tempered ? (clamp ? vae_generate_kernel<true, true> : vae_generate_kernel<false, true>)
-                                      : (clamp ? vae_generate_kernel<true, false> : vae_generate_kernel<false, false>);
-  if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 96 * 1024)) return e;
-  ProfScope p(tempered ? (clamp ? "vae_generate_tempered_clamped" : "vae_generate_tempered")
-                       : (clamp ? "vae_generate_clamped" : "vae_generate"), s);
-  hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
+  ProfScope p(label, s);
+  hipLaunchKernelGGL(kern, dim3(a.N), dim3(VG_NT), lds, s, a);
   return launch_status();
 }
 
-// re-decoding: the VR instance, always clamped (a null roll is all free) and tempered (1.0f is exact)
-int vae_vary_launch(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
-                    const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
-                    const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
-                    const float* bo, const uint8_t* clamp, float inv_T, float Tz, float* Xs, float* xhat, float* zout,
-                    void* stream) {
-  using namespace clv;
-  if (!clv_vae_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
-  if (zout && (uint64_t)N * T * L > UINT32_MAX) return CLV_EINVAL;             // the latents are addressed in 32 bits
-  if (!temper_factor_ok(inv_T, false) || !temper_factor_ok(Tz, true)) return CLV_EINVAL;
-  if (!sources || !w_enc || !w_dec || !Kh || !bh || !Kz || !bz || !Kd || !bd || !Ko || !bo || !Xs) return CLV_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  VaeGenArgs a{N, T, L, C, 0, use_x_prev != 0, (uint32_t)seed, (uint32_t)(seed >> 32), sources, w_enc, Kh, bh, Kz, bz, Kd, bd,
-               Ko, bo, Xs, xhat, clamp, inv_T, Tz, w_dec, x0, hist_source != 0, zout, nullptr, nullptr};
-  const size_t lds = (size_t)(2 * LH * LH + VG_LMAX * LH) * sizeof(float);
-  void (*kern)(VaeGenArgs) = zout ? vae_generate_kernel<true, true, true, true> : vae_generate_kernel<true, true, true>;
-  if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 96 * 1024)) return e;
-  ProfScope p(zout ? "vae_vary_latents" : "vae_vary", s);
-  hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
-  return launch_status();
+// what every entry point fills alike; everything else starts absent (null, 0) and untempered
+clv::VaeGenArgs vae_args(int N, int nsteps, int L, int C, int use_x_prev, uint64_t seed, const uint8_t* clamp, float* Xs, float* xhat) {
+  clv::VaeGenArgs a{};
+  a.N = N; a.nsteps = nsteps; a.L = L; a.C = C; a.has_xp = use_x_prev != 0;
+  a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
+  a.clamp = clamp; a.inv_T = 1.f; a.Tz = 1.f; a.Xs = Xs; a.xhat = xhat;
+  return a;
 }
 
-// decoding a given latent path: the ZG instance.  No z-encoder: its weights, label and sources are absent
-int vae_decode_launch(int N, int T, int D, int H, int L, int C, int use_x_prev, uint64_t seed, const float* z_in,
-                      const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows, const float* Kd,
-                      const float* bd, const float* Ko, const float* bo, const uint8_t* clamp, float inv_T, float* Xs,
-                      float* xhat, void* stream) {
-  using namespace clv;
-  if (!clv_vae_generate_supported(D, H, L, C) || N <= 0 || T <= 0) return CLV_EINVAL;
-  if (!temper_factor_ok(inv_T, false)) return CLV_EINVAL;
-  if (!z_in || !w_dec || !Kd || !bd || !Ko || !bo || !Xs) return CLV_EINVAL;
-  if ((uint64_t)N * T * L > UINT32_MAX || (uint64_t)N * T * LH > UINT32_MAX) return CLV_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  VaeGenArgs a{N, T, L, C, 0, use_x_prev != 0, (uint32_t)seed, (uint32_t)(seed >> 32), history, nullptr, nullptr, nullptr,
-               nullptr, nullptr, Kd, bd, Ko, bo, Xs, xhat, clamp, inv_T, 1.f, w_dec, x0, history != nullptr, nullptr, z_in,
-               noise_rows};
-  const size_t lds = (size_t)(LH * LH + VG_LMAX * LH) * sizeof(float);
-  void (*kern)(VaeGenArgs) = vae_generate_kernel<true, true, true, false, true>;
-  ProfScope p("vae_decode", s);
-  hipLaunchKernelGGL(kern, dim3(N), dim3(VG_NT), lds, s, a);
-  return launch_status();
-}
+void set_encoder(clv::VaeGenArgs& a, const float* Kh, const float* bh, const float* Kz, const float* bz) { a.Kh = Kh; a.bh = bh; a.Kz = Kz; a.bz = bz; }
+void set_decoder(clv::VaeGenArgs& a, const float* Kd, const float* bd, const float* Ko, const float* bo) { a.Kd = Kd; a.bd = bd; a.Ko = Ko; a.bo = bo; }
 }  // namespace
 
 extern "C" int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
                                 const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
                                 const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
                                 float* Xs, float* xhat, void* stream) {
-  return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
-                             nullptr, false, 1.f, 1.f, Xs, xhat, stream);
+  clv::VaeGenArgs a = vae_args(N, nsteps, L, C, use_x_prev, seed, nullptr, Xs, xhat);
+  set_encoder(a, Kh, bh, Kz, bz);
+  set_decoder(a, Kd, bd, Ko, bo);
+  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w;
+  return vae_launch(a, Mode::generate, false, D, H, stream);
 }
 
 extern "C" int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
                                         uint64_t seed, const float* x_seed, const float* w, const float* Kh, const float* bh,
                                         const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
                                         const float* bo, const uint8_t* clamp, float* Xs, float* xhat, void* stream) {
-  if (!clamp) return CLV_EINVAL;
-  return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
-                             clamp, false, 1.f, 1.f, Xs, xhat, stream);
+  if (!clamp) return CLV_EINVAL;             // this entry point is the roll
+  clv::VaeGenArgs a = vae_args(N, nsteps, L, C, use_x_prev, seed, clamp, Xs, xhat);
+  set_encoder(a, Kh, bh, Kz, bz);
+  set_decoder(a, Kd, bd, Ko, bo);
+  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w;
+  return vae_launch(a, Mode::generate, false, D, H, stream);
 }
 
 extern "C" int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
@@ -331,18 +344,11 @@ extern "C" int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L,
                                          const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
                                          const float* bo, const uint8_t* clamp, float inv_temperature, float z_temperature,
                                          float* Xs, float* xhat, void* stream) {
-  if (!clv::temper_factor_ok(inv_temperature, false) || !clv::temper_factor_ok(z_temperature, true)) return CLV_EINVAL;
-  return vae_generate_launch(N, nsteps, D, H, L, C, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
-                             clamp, true, inv_temperature, z_temperature, Xs, xhat, stream);
-}
-
-extern "C" int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
-                            const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
-                            const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
-                            const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
-                            float z_temperature, float* Xs, float* xhat, void* stream) {
-  return vae_vary_launch(N, T, D, H, L, C, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko,
-                         bo, clamp, inv_temperature, z_temperature, Xs, xhat, nullptr, stream);
+  clv::VaeGenArgs a = vae_args(N, nsteps, L, C, use_x_prev, seed, clamp, Xs, xhat);
+  set_encoder(a, Kh, bh, Kz, bz);
+  set_decoder(a, Kd, bd, Ko, bo);
+  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
+  return vae_launch(a, Mode::generate, true, D, H, stream);
 }
 
 extern "C" int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
@@ -351,14 +357,34 @@ extern "C" int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, in
                                     const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
                                     float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout,
                                     void* stream) {
-  return vae_vary_launch(N, T, D, H, L, C, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko,
-                         bo, clamp, inv_temperature, z_temperature, Xs, xhat, zout, stream);
+  clv::VaeGenArgs a = vae_args(N, T, L, C, use_x_prev, seed, clamp, Xs, xhat);
+  set_encoder(a, Kh, bh, Kz, bz);
+  set_decoder(a, Kd, bd, Ko, bo);
+  a.x_seed = sources; a.x0 = x0; a.w = w_enc; a.w_dec = w_dec; a.hist_source = hist_source != 0;
+  a.inv_T = inv_temperature; a.Tz = z_temperature; a.zout = zout;
+  return vae_launch(a, Mode::vary, true, D, H, stream);
+}
+
+extern "C" int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
+                            const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
+                            const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
+                            const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
+                            float z_temperature, float* Xs, float* xhat, void* stream) {
+  clv::VaeGenArgs a = vae_args(N, T, L, C, use_x_prev, seed, clamp, Xs, xhat);
+  set_encoder(a, Kh, bh, Kz, bz);
+  set_decoder(a, Kd, bd, Ko, bo);
+  a.x_seed = sources; a.x0 = x0; a.w = w_enc; a.w_dec = w_dec; a.hist_source = hist_source != 0;
+  a.inv_T = inv_temperature; a.Tz = z_temperature;
+  return vae_launch(a, Mode::vary, true, D, H, stream);
 }
 
 extern "C" int clv_vae_decode(int N, int T, int D, int H, int L, int C, int use_x_prev, uint64_t seed, const float* z_in,
                               const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
                               const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
                               float inv_temperature, float* Xs, float* xhat, void* stream) {
-  return vae_decode_launch(N, T, D, H, L, C, use_x_prev, seed, z_in, x0, history, w_dec, noise_rows, Kd, bd, Ko, bo, clamp,
-                           inv_temperature, Xs, xhat, stream);
+  clv::VaeGenArgs a = vae_args(N, T, L, C, use_x_prev, seed, clamp, Xs, xhat);
+  set_decoder(a, Kd, bd, Ko, bo);
+  a.x_seed = history; a.hist_source = history != nullptr; a.x0 = x0; a.w_dec = w_dec;
+  a.z_in = z_in; a.noise_rows = noise_rows; a.inv_T = inv_temperature;
+  return vae_launch(a, Mode::decode, true, D, H, stream);
 }

@@ -367,6 +367,33 @@ def dense_outer_bf16(Bn, nx, N, X, ldx, G, ldg, out, ldo=None, colsum=None, gdot
                                           _ptr(colsum), _ptr(h), int(ldh), _ptr(hb), _ptr(go), _stream()), "clv_dense_outer_bf16")
 
 
+def _ptrs(*tensors):
+    return [_ptr(t) for t in tensors]
+
+
+def _sample(name, *args):
+    """one entry point of the persistent sampling kernels: name(*args, stream), checked"""
+    check(getattr(_lib.lib(), name)(*args, _stream()), name)
+
+
+def _generate(name, head, clamp, temper, Xs, xhat):
+    """name (no roll), name_clamped (a roll) or name_tempered (the two factors, with or without a roll): the symbol decides
+    the kernel instance"""
+    if temper is not None:
+        _sample(name + "_tempered", *head, _ptr(clamp), float(temper[0]), float(temper[1]), *_ptrs(Xs, xhat))
+    elif clamp is None:
+        _sample(name, *head, *_ptrs(Xs, xhat))
+    else:
+        _sample(name + "_clamped", *head, *_ptrs(clamp, Xs, xhat))
+
+
+def _vary(name, head, clamp, temper, Xs, xhat, zout):
+    """name, or name_latents with a zout: the roll, the two factors and the outputs behind a family's own head"""
+    inv_T, Tz = (1.0, 1.0) if temper is None else temper
+    outs = _ptrs(Xs, xhat) if zout is None else _ptrs(Xs, xhat, zout)
+    _sample(name if zout is None else name + "_latents", *head, _ptr(clamp), float(inv_T), float(Tz), *outs)
+
+
 def vrnn_generate_supported(D, H, L, Cn):
     return bool(_lib.lib().clv_vrnn_generate_supported(D, H, L, Cn))
 
@@ -376,17 +403,9 @@ def vrnn_generate(N, S, nsteps, D, H, L, Cn, gate_act, z_prior, seed, x_seed, w,
     """cl_vrnn frame loop for N sequences in one persistent launch (csrc/generate.hip); clamp: uint8 [N,nsteps,D]
     constraint roll (clv_vrnn_generate_clamped) or None; temper: None or (inv_temperature, z_temperature), the tempered
     model's two factors (clv_vrnn_generate_tempered, with or without a roll)."""
-    args = [N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed), _ptr(x_seed), _ptr(w), _ptr(Kx_enc),
-            _ptr(Kw_enc), _ptr(b_enc), _ptr(U_enc), _ptr(Wz), _ptr(bz), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec),
-            _ptr(U_dec), _ptr(Wo), _ptr(bo)]
-    if temper is not None:
-        check(_lib.lib().clv_vrnn_generate_tempered(*args, _ptr(clamp), float(temper[0]), float(temper[1]), _ptr(Xs), _ptr(xhat),
-                                                    _stream()), "clv_vrnn_generate_tempered")
-    elif clamp is None:
-        check(_lib.lib().clv_vrnn_generate(*args, _ptr(Xs), _ptr(xhat), _stream()), "clv_vrnn_generate")
-    else:
-        check(_lib.lib().clv_vrnn_generate_clamped(*args, _ptr(clamp), _ptr(Xs), _ptr(xhat), _stream()),
-              "clv_vrnn_generate_clamped")
+    _generate("clv_vrnn_generate", [N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed),
+                                    *_ptrs(x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo)],
+              clamp, temper, Xs, xhat)
 
 
 def vae_generate_supported(D, H, L, Cn):
@@ -398,76 +417,53 @@ def vae_generate(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, x_seed, w, K
     """cl_vae frame loop for N sequences in one persistent launch (csrc/vae_generate.hip); clamp: uint8 [N,nsteps,D]
     constraint roll (clv_vae_generate_clamped) or None; temper: None or (inv_temperature, z_temperature)
     (clv_vae_generate_tempered, with or without a roll)."""
-    args = [N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed), _ptr(x_seed), _ptr(w), _ptr(Kh),
-            _ptr(bh), _ptr(Kz), _ptr(bz), _ptr(Kd), _ptr(bd), _ptr(Ko), _ptr(bo)]
-    if temper is not None:
-        check(_lib.lib().clv_vae_generate_tempered(*args, _ptr(clamp), float(temper[0]), float(temper[1]), _ptr(Xs), _ptr(xhat),
-                                                   _stream()), "clv_vae_generate_tempered")
-    elif clamp is None:
-        check(_lib.lib().clv_vae_generate(*args, _ptr(Xs), _ptr(xhat), _stream()), "clv_vae_generate")
-    else:
-        check(_lib.lib().clv_vae_generate_clamped(*args, _ptr(clamp), _ptr(Xs), _ptr(xhat), _stream()),
-              "clv_vae_generate_clamped")
+    _generate("clv_vae_generate", [N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed),
+                                   *_ptrs(x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo)], clamp, temper, Xs, xhat)
 
 
 def vrnn_vary(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
               Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None, temper=None):
     """cl_vrnn re-decoding of sources [N,T,D] in one persistent launch (clv_vrnn_vary); x0, clamp, xhat may be
     None; temper: None or (inv_temperature, z_temperature)."""
-    inv_T, Tz = (1.0, 1.0) if temper is None else temper
-    check(_lib.lib().clv_vrnn_vary(N, T, D, H, L, Cn, gate_act, int(bool(hist_source)), int(seed), _ptr(sources), _ptr(x0),
-                                   _ptr(w_enc), _ptr(w_dec), _ptr(Kx_enc), _ptr(Kw_enc), _ptr(b_enc), _ptr(U_enc), _ptr(Wz),
-                                   _ptr(bz), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec), _ptr(U_dec), _ptr(Wo), _ptr(bo),
-                                   _ptr(clamp), float(inv_T), float(Tz), _ptr(Xs), _ptr(xhat), _stream()), "clv_vrnn_vary")
+    vrnn_vary_latents(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
+                      bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, None, xhat=xhat, clamp=clamp, temper=temper)
 
 
 def vae_vary(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs,
              xhat=None, clamp=None, temper=None):
     """cl_vae re-decoding of sources [N,T,D] in one persistent launch (clv_vae_vary); arguments as vrnn_vary"""
-    inv_T, Tz = (1.0, 1.0) if temper is None else temper
-    check(_lib.lib().clv_vae_vary(N, T, D, H, L, Cn, int(bool(use_x_prev)), int(bool(hist_source)), int(seed), _ptr(sources),
-                                  _ptr(x0), _ptr(w_enc), _ptr(w_dec), _ptr(Kh), _ptr(bh), _ptr(Kz), _ptr(bz), _ptr(Kd), _ptr(bd),
-                                  _ptr(Ko), _ptr(bo), _ptr(clamp), float(inv_T), float(Tz), _ptr(Xs), _ptr(xhat), _stream()),
-          "clv_vae_vary")
+    vae_vary_latents(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
+                     Xs, None, xhat=xhat, clamp=clamp, temper=temper)
 
 
 def vrnn_vary_latents(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc,
                       Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, zout, xhat=None, clamp=None, temper=None):
     """vrnn_vary that also stores the latents: zout [3,N,T,L] = (z_mean, z_log_var, z) (clv_vrnn_vary_latents)"""
-    inv_T, Tz = (1.0, 1.0) if temper is None else temper
-    check(_lib.lib().clv_vrnn_vary_latents(N, T, D, H, L, Cn, gate_act, int(bool(hist_source)), int(seed), _ptr(sources),
-                                           _ptr(x0), _ptr(w_enc), _ptr(w_dec), _ptr(Kx_enc), _ptr(Kw_enc), _ptr(b_enc),
-                                           _ptr(U_enc), _ptr(Wz), _ptr(bz), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec),
-                                           _ptr(U_dec), _ptr(Wo), _ptr(bo), _ptr(clamp), float(inv_T), float(Tz), _ptr(Xs),
-                                           _ptr(xhat), _ptr(zout), _stream()), "clv_vrnn_vary_latents")
+    _vary("clv_vrnn_vary", [N, T, D, H, L, Cn, gate_act, int(bool(hist_source)), int(seed),
+                            *_ptrs(sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec,
+                                   Wo, bo)], clamp, temper, Xs, xhat, zout)
 
 
 def vae_vary_latents(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
                      Xs, zout, xhat=None, clamp=None, temper=None):
     """vae_vary that also stores the latents: zout [3,N,T,L] (clv_vae_vary_latents)"""
-    inv_T, Tz = (1.0, 1.0) if temper is None else temper
-    check(_lib.lib().clv_vae_vary_latents(N, T, D, H, L, Cn, int(bool(use_x_prev)), int(bool(hist_source)), int(seed),
-                                          _ptr(sources), _ptr(x0), _ptr(w_enc), _ptr(w_dec), _ptr(Kh), _ptr(bh), _ptr(Kz),
-                                          _ptr(bz), _ptr(Kd), _ptr(bd), _ptr(Ko), _ptr(bo), _ptr(clamp), float(inv_T), float(Tz),
-                                          _ptr(Xs), _ptr(xhat), _ptr(zout), _stream()), "clv_vae_vary_latents")
+    _vary("clv_vae_vary", [N, T, D, H, L, Cn, int(bool(use_x_prev)), int(bool(hist_source)), int(seed),
+                           *_ptrs(sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo)], clamp, temper, Xs, xhat, zout)
 
 
 def vrnn_decode(N, T, D, H, L, Cn, gate_act, seed, z_in, x0, history, w_dec, noise_rows, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo,
                 bo, Xs, xhat=None, clamp=None, inv_T=1.0):
     """cl_vrnn decoding of the latent path z_in [N,T,L] in one persistent launch (clv_vrnn_decode); x0, history
     [N,T,D], noise_rows [N] int32 (entries >= 0: validated by the caller), clamp, xhat may be None"""
-    check(_lib.lib().clv_vrnn_decode(N, T, D, H, L, Cn, gate_act, int(seed), _ptr(z_in), _ptr(x0), _ptr(history), _ptr(w_dec),
-                                     _ptr(noise_rows), _ptr(Kx_dec), _ptr(Kz), _ptr(Kw_dec), _ptr(b_dec), _ptr(U_dec),
-                                     _ptr(Wo), _ptr(bo), _ptr(clamp), float(inv_T), _ptr(Xs), _ptr(xhat), _stream()),
-          "clv_vrnn_decode")
+    _sample("clv_vrnn_decode", N, T, D, H, L, Cn, gate_act, int(seed),
+            *_ptrs(z_in, x0, history, w_dec, noise_rows, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp), float(inv_T), *_ptrs(Xs, xhat))
 
 
 def vae_decode(N, T, D, H, L, Cn, use_x_prev, seed, z_in, x0, history, w_dec, noise_rows, Kd, bd, Ko, bo, Xs, xhat=None,
                clamp=None, inv_T=1.0):
     """cl_vae decoding of the latent path z_in [N,T,L] in one persistent launch (clv_vae_decode); arguments as vrnn_decode"""
-    check(_lib.lib().clv_vae_decode(N, T, D, H, L, Cn, int(bool(use_x_prev)), int(seed), _ptr(z_in), _ptr(x0), _ptr(history),
-                                    _ptr(w_dec), _ptr(noise_rows), _ptr(Kd), _ptr(bd), _ptr(Ko), _ptr(bo), _ptr(clamp),
-                                    float(inv_T), _ptr(Xs), _ptr(xhat), _stream()), "clv_vae_decode")
+    _sample("clv_vae_decode", N, T, D, H, L, Cn, int(bool(use_x_prev)), int(seed),
+            *_ptrs(z_in, x0, history, w_dec, noise_rows, Kd, bd, Ko, bo, clamp), float(inv_T), *_ptrs(Xs, xhat))
 
 
 def lerp_rows(R, n, a, ia, b, ib, alpha, out):

@@ -415,7 +415,7 @@ int clv_lstm_pair_bwd(int B, int T, int H, int L, int gate_act, float kl_scale,
  * clv_philox_uniform value for (seed, step t, stream 1, index n*D+j).  Kernel pieces are the row blocks of the
  * Keras tensors: encoder_h/kernel = [Kx_enc (D rows) ; Kw_enc (C rows)], decoder_h/kernel = [Kx_dec (D rows,
  * NULL without use_x_prev) ; Kz (L rows) ; Kw_dec (C rows)], Wz = [Z_mean | Z_log_var] kernel [H,2L].
- * clv_vrnn_generate_supported: D == H == 88, L <= 16, C <= 32. */
+ * clv_vrnn_generate_supported: D == H == 88, L <= 32, C <= 32. */
 int clv_vrnn_generate_supported(int D, int H, int L, int C);
 int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
                       uint64_t seed, const float* x_seed, const float* w,
