@@ -115,7 +115,7 @@ class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
 
-# The argument lists of the twelve entry points of the persistent sampling kernels, in named pieces: a count is the number
+# The argument lists of the fourteen entry points of the persistent sampling kernels, in named pieces: a count is the number
 # of names in its piece, never typed by hand.  gate_act is cl_vrnn's, use_x_prev cl_vae's, at the same place.
 def _args(kind, names):
     return [kind] * len(names.split())
@@ -129,6 +129,7 @@ _VRNN_ENC, _VRNN_DEC = _args(_p, "Kx_enc Kw_enc b_enc U_enc Wz bz"), _args(_p, "
 _VAE_ENC, _VAE_DEC = _args(_p, "Kh bh Kz bz"), _args(_p, "Kd bd Ko bo")
 _TEMPER = [_p, _f, _f]                                 # clamp, inv_temperature, z_temperature (decode: the first two)
 _OUT, _OUT_Z = _args(_p, "Xs xhat stream"), _args(_p, "Xs xhat zout stream")
+_RESUME = [_u32] + _args(_p, "state_in state_out")      # _u32: t0, the Philox step of the call's frame 0
 
 # name -> (restype, argtypes); must list every function of include/clvae.h
 SIGNATURES = {
@@ -200,6 +201,8 @@ SIGNATURES = {
     "clv_vae_vary_latents": (_i, _VARY + _VAE_ENC + _VAE_DEC + _TEMPER + _OUT_Z),
     "clv_vrnn_decode": (_i, _DECODE + _VRNN_DEC + _TEMPER[:2] + _OUT),
     "clv_vae_decode": (_i, _DECODE + _VAE_DEC + _TEMPER[:2] + _OUT),
+    "clv_vrnn_generate_resume": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _TEMPER + _RESUME + _OUT),
+    "clv_vae_generate_resume": (_i, _VAE_GENERATE[:-2] + _args(_p, "w") + _VAE_ENC + _VAE_DEC + _TEMPER + _RESUME + _OUT),
     "clv_lerp_rows": (_i, [_i64, _i64] + [_p] * 7),
     "clv_sigmoid_temper": (_i, [_i64, _p, _f, _p]),
     "clv_scale_temper": (_i, [_i64, _p, _f, _p]),

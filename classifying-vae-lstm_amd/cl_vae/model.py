@@ -60,7 +60,7 @@ def generate_sample(dec_model, w_enc_model, z_enc_model, x_seed, nsteps, w_val=N
 
 def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_prior=False, clamp=None, particles=None,
                             resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False,
-                            temperature=1.0, z_temperature=1.0):
+                            temperature=1.0, z_temperature=1.0, state=None, return_state=False):
     """N sequences at once with the frame loop on the device (VaeEngine.generate: one captured hipGraph replayed per
     frame, Philox noise instead of np.random: same distribution, different draws).  x_seeds [N,D], w_vals [N,C];
     returns [N,nsteps,D] float64 like generate_sample does per sequence.  clamp: numpy / torch uint8 [N,nsteps,D]
@@ -71,11 +71,22 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_p
     then log p(constraints | seed); return_key: also the key posterior [N,nsteps,C] and each path's w [N,C].
     temperature (> 0) divides every note's logit before the sigmoid, z_temperature (>= 0) scales the latent noise (0: z is
     its mean): every route then samples the TEMPERED model with the same Philox draws, and the evidence is
-    the tempered model's, log p_T(constraints | ...), not the trained model's unless both are 1 (the default)."""
+    the tempered model's, log p_T(constraints | ...), not the trained model's unless both are 1 (the default).
+    state (an engine_generate.GenState of a cl_vae model with N rows), return_state: resume a piece where an
+    earlier call stopped.  The state holds the last frame and the frame before it (the z-encoder's input and the decoder's
+    history), so x_seeds must then be None; the Philox steps count on from state.t.  With return_state the call returns
+    (frames, GenState after the last frame); a first call with x_seeds and return_state starts the piece.  A piece generated
+    in chunks this way is bit for bit the piece of one call, whatever the chunking; w_vals, clamp and the temperatures may
+    change from call to call (row t of a call's roll constrains that call's frame t).  state.select(index) branches a
+    prefix.  The state is not written.  ValueError for a state together with particles, a state of the other family, a
+    state whose N or width is not the call's, x_seeds together with a state, and a state.t + nsteps that passes the last
+    Philox step 2^32 - 1."""
     temper_args(temperature, z_temperature)         # refused before the model's engine is asked for
+    resume = {} if state is None and not return_state else dict(state=state, return_state=return_state, kind='cl_vae')
     return generate_samples_numpy(model.engine, x_seeds, nsteps, w_vals, seed=seed, z_prior=use_z_prior, clamp=clamp,
                                   particles=particles, resample_threshold=resample_threshold, return_evidence=return_evidence,
-                                  w_prior=w_prior, return_key=return_key, temperature=temperature, z_temperature=z_temperature)
+                                  w_prior=w_prior, return_key=return_key, temperature=temperature, z_temperature=z_temperature,
+                                  **resume)
 
 
 def vary_samples_device(model, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,

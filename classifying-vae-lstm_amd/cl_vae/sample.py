@@ -8,9 +8,10 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS,  # noqa: E402
-                           morph_kwargs, parser_for, temperature_kwargs)
-from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
+                           VARY_FLAGS, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs)
+from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior, voice_constraints  # noqa: E402
+from clvae_amd.stream import generate_chunked  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
@@ -52,9 +53,14 @@ class Sampler:
         seeds, ws = zip(*[self.pick_seed() for _ in names])
         if self.args.infer_w:
             ws = [M.sample_w(self.w_enc.predict(s[None, :]), add_noise=False) for s in seeds]
-        rolls = M.generate_samples_device(self.model, np.stack(seeds), self.args.t, np.vstack(ws),
-                                          seed=getattr(self.args, 'seed', 0), use_z_prior=self.args.use_z_prior,
-                                          **temperature_kwargs(self.args))
+        resume = resume_kwargs(self.args, self.data.key_map, len(names), self.margs['n_classes'])
+        if resume:              # --chunk / --modulate: the same call a chunk at a time
+            rolls = generate_chunked(self.model, np.stack(seeds), self.args.t, np.vstack(ws), seed=getattr(self.args, 'seed', 0),
+                                     z_prior=self.args.use_z_prior, **resume, **temperature_kwargs(self.args))
+        else:
+            rolls = M.generate_samples_device(self.model, np.stack(seeds), self.args.t, np.vstack(ws),
+                                              seed=getattr(self.args, 'seed', 0), use_z_prior=self.args.use_z_prior,
+                                              **temperature_kwargs(self.args))
         for roll, name in zip(rolls, names):
             write_sample(roll, self.args.sample_dir, name, True)
         return list(rolls)
@@ -74,10 +80,16 @@ class Sampler:
             ws = [M.sample_w(self.w_enc.predict(s[None, :]), add_noise=False) for s in seeds]
         else:
             ws = [to_categorical(self.data.test_song_keys[i], self.margs['n_classes']) for i in picks]
-        out = harmonize(self.model, seeds, sources, None if ws is None else np.vstack(ws), voice=voice_of(self.args),
-                        seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior, particles=particles,
-                        return_evidence=particles is not None, **(dict(infer_key=infer_key) if infer_key else {}),
-                        **temperature_kwargs(self.args))
+        resume = resume_kwargs(self.args, self.data.key_map, len(names), self.margs['n_classes'])
+        if resume:              # --chunk / --modulate: harmonize()'s call a chunk at a time, the roll sliced per chunk
+            out = generate_chunked(self.model, seeds, self.args.t, np.vstack(ws), seed=getattr(self.args, 'seed', 0),
+                                   z_prior=self.args.use_z_prior, clamp=voice_constraints(sources, voice_of(self.args)),
+                                   **resume, **temperature_kwargs(self.args))
+        else:
+            out = harmonize(self.model, seeds, sources, None if ws is None else np.vstack(ws), voice=voice_of(self.args),
+                            seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior, particles=particles,
+                            return_evidence=particles is not None, **(dict(infer_key=infer_key) if infer_key else {}),
+                            **temperature_kwargs(self.args))
         rolls = out[0] if particles is not None else out
         if particles is not None:
             print_evidence(names, out[1], self.args.t)
@@ -148,9 +160,10 @@ def voice_of(args):
 def on_device(args):
     """Where the frame loop runs: like the reference (host loop, np.random) for every -n unless --device_loop asks for
     the device-side loop (Philox noise: other samples for the same np.random.seed, so it is opt-in); --harmonize
-    --vary and --morph always run there, and so does a sampling temperature (the parser refuses them next to --host_loop)."""
+    --vary, --morph, --chunk and --modulate always run there, and so does a sampling temperature (the parser refuses them
+    next to --host_loop)."""
     return bool(voice_of(args)) or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
-        temperature_kwargs(args)) or (
+        temperature_kwargs(args)) or resuming(args) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
 
 
@@ -172,4 +185,5 @@ def build_parser():
 
 if __name__ == '__main__':
     sample(parser_for('cl_vae.sample',
-                      DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS).parse_args())
+                      DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
+                      + RESUME_FLAGS).parse_args())

@@ -237,7 +237,7 @@ class Encoder:
 
 def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
                             resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False,
-                            temperature=1.0, z_temperature=1.0):
+                            temperature=1.0, z_temperature=1.0, state=None, return_state=False):
     """Batched, device-resident counterpart of generate_sample: N seeds at once, the whole frame loop as
     replays of one captured hipGraph, Philox noise instead of np.random (so the draws differ from the numpy
     path, the distribution does not).  x_seeds [N,S,88] (S >= 0 teacher-forced frames), w_vals [N,C].
@@ -250,11 +250,24 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     then log p(constraints | seed); return_key: also the key posterior [N,nsteps,C] and each path's w [N,C].
     temperature (> 0) divides every note's logit before the sigmoid, z_temperature (>= 0) scales the latent noise (0: z is
     its mean): every route then samples the TEMPERED model with the same Philox draws, and the evidence is
-    the tempered model's, log p_T(constraints | ...), not the trained model's unless both are 1 (the default)."""
+    the tempered model's, log p_T(constraints | ...), not the trained model's unless both are 1 (the default).
+    state (an engine_generate.GenState of a cl_vrnn model with these widths and N rows), return_state: resume
+    a piece where an earlier call stopped.  The call starts both LSTMs and its first input from the state and counts the
+    Philox steps on from state.t; with return_state it returns (frames, GenState after the last frame).  x_seeds may then be
+    None (or [N,0,88]): the free run goes on from the state's last sample; given, its frames are teacher-forced first, from
+    the state's LSTM states.  nsteps=0 with seed frames and return_state primes a state on the seed (its next input is the
+    bridge sample, which no other call returns).  A piece generated in chunks this way is bit for bit the piece of one
+    call, whatever the chunking; w_vals, clamp and the temperatures may change from call to call (modulation, a roll that
+    arrives in pieces: row j of a call's roll constrains that call's frame j).  state.select(index) branches a prefix.
+    The state is not written.  ValueError for a state together with particles (the filter's per-particle state is not
+    carried), a state of the other family, a state whose N or widths are not the call's, and a state.t + S + nsteps that
+    passes the last Philox step 2^32 - 1."""
     temper_args(temperature, z_temperature)         # refused before the model's engine is asked for
+    resume = {} if state is None and not return_state else dict(state=state, return_state=return_state, kind='cl_vrnn')
     return generate_samples_numpy(model.engine, x_seeds, nsteps, w_vals, seed=seed, z_prior=z_prior, clamp=clamp,
                                   particles=particles, resample_threshold=resample_threshold, return_evidence=return_evidence,
-                                  w_prior=w_prior, return_key=return_key, temperature=temperature, z_temperature=z_temperature)
+                                  w_prior=w_prior, return_key=return_key, temperature=temperature, z_temperature=z_temperature,
+                                  **resume)
 
 
 def vary_samples_device(model, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,

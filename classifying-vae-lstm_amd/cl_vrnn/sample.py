@@ -8,9 +8,10 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS,  # noqa: E402
-                           morph_kwargs, parser_for, temperature_kwargs)
-from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior  # noqa: E402
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
+                           VARY_FLAGS, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs)
+from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior, voice_constraints  # noqa: E402
+from clvae_amd.stream import generate_chunked  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
@@ -45,8 +46,13 @@ def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None)
         ws = [label_of(i) for i in picks]
         if args.infer_w:
             ws = [M.infer_label(w_enc_model, P.x_test[i], margs['seq_length'], discrete=args.discrete_w) for i in picks]
-        rolls = list(M.generate_samples_device(model, np.stack([P.x_test[i] for i in picks]), args.t, np.vstack(ws),
-                                               seed=getattr(args, 'seed', 0), **temperature_kwargs(args)))
+        resume = resume_kwargs(args, P.key_map, len(picks), margs['n_classes'])
+        if resume:              # --chunk / --modulate: the same call a chunk at a time
+            rolls = list(generate_chunked(model, np.stack([P.x_test[i] for i in picks]), args.t, np.vstack(ws),
+                                          seed=getattr(args, 'seed', 0), **resume, **temperature_kwargs(args)))
+        else:
+            rolls = list(M.generate_samples_device(model, np.stack([P.x_test[i] for i in picks]), args.t, np.vstack(ws),
+                                                   seed=getattr(args, 'seed', 0), **temperature_kwargs(args)))
     else:
         rolls = [M.generate_sample(dec_model, w_enc_model, z_enc_model, P.x_test[i], args.t, margs['use_x_prev'],
                                    w_val=label_of(i), w_discrete=args.discrete_w, seq_length=margs['seq_length'])
@@ -75,8 +81,13 @@ def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice
         ws = [label_of(i) for i in picks]
         if args.infer_w:
             ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in seeds]
-        out = harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0),
-                        particles=particles, return_evidence=particles is not None, **temperature_kwargs(args))
+        resume = resume_kwargs(args, P.key_map, len(picks), margs['n_classes'])
+        if resume:              # --chunk / --modulate: harmonize()'s call a chunk at a time, the roll sliced per chunk
+            out = generate_chunked(model, seeds, t, np.vstack(ws), seed=getattr(args, 'seed', 0),
+                                   clamp=voice_constraints(sources, voice), **resume, **temperature_kwargs(args))
+        else:
+            out = harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0),
+                            particles=particles, return_evidence=particles is not None, **temperature_kwargs(args))
     rolls = list(out[0] if particles is not None else out)
     if particles is not None:
         names = ['%s_%d' % (args.run_name, j) for j in range(len(rolls))]
@@ -139,9 +150,9 @@ def sample(args):
     # --harmonize: windows of the seed's t frames and the t frames whose voice is kept
     P = PianoData(args.train_file, batch_size=1, seq_length=2 * args.t if voice else args.t, squeeze_x=False)
     # the reference's host loop (np.random) for every -n; --device_loop opts into the device-side loop (Philox noise), and
-    # a sampling temperature, --vary and --morph imply it (the parser refuses them next to --host_loop)
+    # a sampling temperature, --vary, --morph, --chunk and --modulate imply it (the parser refuses them next to --host_loop)
     on_device = bool(voice) or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
-        temperature_kwargs(args)) or (
+        temperature_kwargs(args)) or resuming(args) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
     return gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
 
@@ -152,4 +163,5 @@ def build_parser():
 
 if __name__ == '__main__':
     sample(parser_for('cl_vrnn.sample',
-                      DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS).parse_args())
+                      DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
+                      + RESUME_FLAGS).parse_args())

@@ -148,6 +148,54 @@ MORPH_FLAGS = [
 ]
 
 
+# resumable generation (not in the reference): the -t frames a chunk at a time, and a change of key on the way
+# (both imply --device_loop)
+RESUME_FLAGS = [
+    Flag(('--chunk',), int, None, 'generate the -t frames in chunks of this many through a Stream that carries the '
+                                  "sampler's state (the same frames as one call; implies --device_loop)"),
+    Flag(('--modulate',), str, None, 'NAME@FRAME[,NAME@FRAME...]: from returned frame FRAME on, the label is the one-hot of '
+                                     "key NAME (a name of the data set's key map); frames strictly increasing, > 0 and "
+                                     'below -t (implies --device_loop)'),
+]
+
+
+def parse_modulate(text, t):
+    """--modulate's NAME@FRAME[,NAME@FRAME...] -> [(name, frame), ...]; ValueError unless every item has a name and an
+    integer frame and the frames are strictly increasing, > 0 and < t"""
+    out = []
+    for item in str(text).split(','):
+        name, at, frame = item.strip().rpartition('@')
+        if not at or not name.strip():
+            raise ValueError("--modulate takes NAME@FRAME[,NAME@FRAME...], got %r" % (item,))
+        try:
+            frame = int(frame)
+        except ValueError:
+            raise ValueError("--modulate: the frame of %r is not an integer" % (item,))
+        out.append((name.strip(), frame))
+    frames = [f for _, f in out]
+    if any(not 0 < f < int(t) for f in frames) or any(b <= a for a, b in zip(frames, frames[1:])):
+        raise ValueError("--modulate: frames must be strictly increasing, > 0 and < -t = %d, got %s" % (t, frames))
+    return out
+
+
+def resuming(args):
+    """whether --chunk or --modulate was given (also for parsers without the flags)"""
+    return getattr(args, 'chunk', None) is not None or getattr(args, 'modulate', None) is not None
+
+
+def resume_kwargs(args, key_map, n, n_classes):
+    """--chunk / --modulate as keyword arguments of stream.generate_chunked: empty without either flag.  The names of
+    --modulate are looked up in key_map (PianoData.key_map) and become one-hot label rows [n, n_classes]."""
+    if not resuming(args):
+        return {}
+    chunk, mod = getattr(args, 'chunk', None), getattr(args, 'modulate', None)
+    kw = dict(chunk=chunk)
+    if mod is not None:
+        from .vary import key_rows
+        kw['changes'] = [(frame, key_rows(name, n, n_classes, key_map)) for name, frame in parse_modulate(mod, args.t)]
+    return kw
+
+
 def temperature_kwargs(args):
     """the sampling tools' --temperature / --z_temperature as keyword arguments of generate_samples_device / harmonize:
     empty where both are 1 (also for parsers without the flags)"""
@@ -168,10 +216,24 @@ class _Parser(argparse.ArgumentParser):
     """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles, a
     temperature other than 1 not with --host_loop (the host loop is the reference's and has none), --vary not with
     --harmonize or --host_loop, --to_key / --vary_history only with --vary, --morph >= 1 and not with --harmonize, --vary or
-    --host_loop"""
+    --host_loop, --chunk >= 1 and a well-formed --modulate, neither with --particles, --vary, --morph or --host_loop"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
+        chunk, mod = getattr(ns, 'chunk', None), getattr(ns, 'modulate', None)
+        if chunk is not None or mod is not None:
+            if chunk is not None and chunk < 1:
+                self.error('--chunk must be >= 1')
+            if mod is not None:
+                try:
+                    parse_modulate(mod, ns.t)
+                except ValueError as e:
+                    self.error(str(e))
+            for flag, on in (('--particles', getattr(ns, 'particles', None) is not None), ('--vary', getattr(ns, 'vary', False)),
+                             ('--morph', getattr(ns, 'morph', None) is not None), ('--host_loop', getattr(ns, 'host_loop', False))):
+                if on:
+                    self.error('--chunk / --modulate carry the state of plain or clamped generation on the device: not '
+                               'with %s' % flag)
         particles = getattr(ns, 'particles', None)
         if particles is not None:
             if not getattr(ns, 'harmonize', None):

@@ -49,6 +49,9 @@ struct GenArgs {
   float* zout;                  // ZO instances: [3,N,T,L] = (z_mean, z_log_var, z) of every frame
   const float* z_in;            // ZG instances: [N,T,L] the latent path that replaces the encoder's
   const int32_t* noise_rows;    // ZG instances: [N] the row whose uniforms sequence n draws, or null (n itself)
+  uint32_t t0;                  // ST instances: the Philox step of local frame 0 (frames, seed frames and rolls stay local)
+  const float* state_in;        // ST instances: [N,5,88] rows h_enc, c_enc, h_dec, c_dec, x (the next input); null: zero start
+  float* state_out;             // ST instances: the same rows after the last frame, or null; may alias state_in
 };
 
 // slice_matvec with half the live registers: the h slice is consumed in two halves of 12 (the kernel is at its
@@ -106,9 +109,15 @@ __device__ __forceinline__ void frame_masks(const float* xbuf, int lane, float& 
 // HISTORY frames (with hist_source) or is null (the decoder runs on its own samples).  The uniforms are those of row
 // noise_rows[n].  Two barriers per frame are left: decoder cell | output head + sample; the z of frame t+1 is parked behind
 // the first of them, after the decoder cell of frame t has read zbuf.  ZG = false folds away.
-template <int GATE, bool ZW, bool CL, bool TP, bool VR = false, bool ZO = false, bool ZG = false>
+// ST = true (with CL and TP, not VR): resumable generation.  Both LSTMs start from state_in instead of zero,
+// the first input is its row x where there is no seed frame, every Philox step is t0 + t, and after the last frame the
+// writer lanes store h (from hb), c and xbuf to state_out.  clamp may be null (every note free).  All of it lies outside the
+// frame loop but the step's scalar add.  ST = false folds away.
+template <int GATE, bool ZW, bool CL, bool TP, bool VR = false, bool ZO = false, bool ZG = false, bool ST = false>
 __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   static_assert((!ZO && !ZG) || (VR && CL && TP && !(ZO && ZG)), "ZO and ZG are variants of the VR instances");
+  static_assert(!ST || (CL && TP && !VR), "ST is a variant of the clamped, tempered generate instances");
+  constexpr bool NR = VR || ST;          // instances whose roll may be null
   constexpr int GN_LQ = (ZW ? GN_LWIDE : GN_LMAX) / PK;
   extern __shared__ __attribute__((aligned(16))) float Kxl[];            // encoder input kernel [88][352], then Wo [88][88]
   float* Wol = ZG ? Kxl : Kxl + LH * LG;                                 // ZG: no encoder, Wo alone
@@ -121,6 +130,11 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   __shared__ uint8_t cbuf[CL ? 128 : 1];        // CL: the constraint byte of the current step, one per writer lane
   __shared__ float xbuf_d[VR ? 128 : 1];        // VR: the decoder's history frame (xbuf is the encoder's input)
   __shared__ float wbuf_d[VR ? GN_CMAX : 1];    // VR: the decoder's label
+  // ST with ZW: the step offset and the state's loads cost the wide instances, which sit at the register budget, one more
+  // live value than their parents have room for, so they park the gate bias in LDS (as CL parks the output bias): 3 KB,
+  // one more LDS read per role and frame, and fewer spilled registers than the parents (PERFLOG.md)
+  constexpr bool RBL = ST && ZW;
+  __shared__ float rb_l[RBL ? GN_NT : 1];       // RBL: rb of every lane; a lane reads only its own slot
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool enc = wave < GN_NW;
@@ -146,13 +160,21 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     }
   }
   for (int i = tid; i < LH * LH; i += GN_NT) Wol[i] = a.Wo[i];
-  for (int i = tid; i < 2 * 2 * PK * PKP; i += GN_NT) (&hb[0][0][0])[i] = 0.f;
+  for (int i = tid; i < 2 * 2 * PK * PKP; i += GN_NT) {
+    float v = 0.f;
+    if (ST && a.state_in) {             // parity 0 of each chain: the h row of its LSTM, unit k at hslot(k)
+      const int chain = i / (2 * PK * PKP), slot = i % (PK * PKP), r = slot % PKP, k = PKK * (slot / PKP) + r;
+      if (((i / (PK * PKP)) & 1) == 0 && r < PKK) v = a.state_in[((size_t)n * 5 + 2 * chain) * LH + k];
+    }
+    (&hb[0][0][0])[i] = v;
+  }
   if (tid < GN_LWIDE) zbuf[tid] = 0.f;
   if (tid < 128) xbuf[tid] = ((VR || a.S > 0) && (!ZG || a.x_seed) && tid < LH) ? a.x_seed[((size_t)n * (VR ? T : a.S)) * LH + tid] : 0.f;
+  if (ST && a.state_in && a.S == 0 && tid < LH) xbuf[tid] = a.state_in[((size_t)n * 5 + 4) * LH + tid];      // this lane wrote the 0
   if (!ZG && tid < a.C) wbuf[tid] = a.w[(size_t)n * a.C + tid];
   if (CL && tid < LH) bo_l[tid] = a.bo[tid];
   if (CL && a.S == 0 && tid < LH)               // step 0's row
-    cbuf[tid] = (VR && !a.clamp) ? (uint8_t)255 : a.clamp[(size_t)n * a.nsteps * LH + tid];
+    cbuf[tid] = (NR && !a.clamp) ? (uint8_t)255 : a.clamp[(size_t)n * a.nsteps * LH + tid];
   if (VR && tid < 128) xbuf_d[tid] = (a.x0 && tid < LH) ? a.x0[(size_t)n * LH + tid] : 0.f;
   if (VR && tid < a.C) wbuf_d[tid] = a.w_dec[(size_t)n * a.C + tid];
   __syncthreads();
@@ -190,6 +212,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     }
     rb = acc;
   }
+  if (RBL) rb_l[tid] = rb;
   // encoder role also owns the output head: unit u = note u, 4 k-slices
   float bor = 0.f, bzr = 0.f;
   // role registers (one allocation for both roles: a wave uses only its own view): decoder: z rows of its input
@@ -224,6 +247,9 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
   const int hslot = PKP * (u / PKK) + (u % PKK);
   const int zpos = lat_ok ? (lat % PK) * GN_LQ + lat / PK : 0;
   float c = 0.f;                       // cell state of this lane's unit (its role's LSTM)
+  // every lane, also those whose u_raw >= LH was clamped to unit 87: they run that unit's cell too and publish the same h
+  if (ST && a.state_in) c = a.state_in[((size_t)n * 5 + (enc ? 1 : 3)) * LH + u];
+  const uint32_t t0 = ST ? a.t0 : 0u;  // the Philox step of local frame 0
   const bool writer = s == 0 && u_raw < LH;        // one lane per unit publishes
 
   // The noise of a frame does not depend on the data: it is drawn one phase (uniform) / one frame (normal) ahead, in
@@ -242,7 +268,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     if (zdraw) zbuf[ZW ? (tid % PK) * GN_LQ + tid / PK : zpos] = e_cur;
     __syncthreads();
   } else {
-    e_cur = zdraw ? philox_normal_at(zidx, a.k0, a.k1, 0u, 0u) : 0.f;
+    e_cur = zdraw ? philox_normal_at(zidx, a.k0, a.k1, 0u, t0) : 0.f;
     if (TP) e_cur = a.Tz * e_cur;
   }
   const uint32_t crow = CL ? ((uint32_t)n * (uint32_t)a.nsteps - (uint32_t)a.S) * (uint32_t)LH : 0u;   // clamp row of step 0
@@ -262,7 +288,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     if (CL && enc && writer && t >= a.S && t > 0) cbuf[u] = (uint8_t)__builtin_bit_cast(uint32_t, seed_carry);
     if (enc && writer && t + 1 < a.S) seed_next = a.x_seed[((size_t)n * a.S + t + 1) * LH + u];
     if (CL && enc && writer && t + 1 >= a.S && t + 1 < T)
-      seed_next = __builtin_bit_cast(float, (VR && !a.clamp) ? 255u
+      seed_next = __builtin_bit_cast(float, (NR && !a.clamp) ? 255u
                                                 : (uint32_t)a.clamp[crow + (uint32_t)(t + 1) * LH + (uint32_t)u]);
     if (CL) seed_carry = seed_next;
     float src_next = 0.f;                          // VR: source frame t+1, the encoder's next input
@@ -274,7 +300,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     if (ZG && enc) {
       // no encoder: nothing to do before the decoder cell
     } else if (enc) {
-      float xv = rb;
+      float xv = RBL ? rb_l[tid] : rb;
       while (m0) {
         const int k = __builtin_ctzll(m0);
         m0 &= m0 - 1;
@@ -381,7 +407,7 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     // ---- phase 3: decoder cell ---------------------------------------------------------------------------------------
     if (!enc) {
       f2 acc2[2];
-      const float xv = xd + rb;
+      const float xv = xd + (RBL ? rb_l[tid] : rb);
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc2[g >> 1][g & 1] = (s == g) ? xv : 0.f;
       {
@@ -408,14 +434,14 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
       hb[1][cur ^ 1][hslot] = h;
     } else {
       // encoder waves are idle here: draw this frame's Bernoulli uniforms and the next frame's latent noise
-      if (writer) u_cur = philox_uniform_at((uint64_t)nrow * LH + u, a.k0, a.k1, 1u, (uint32_t)t);
+      if (writer) u_cur = philox_uniform_at((uint64_t)nrow * LH + u, a.k0, a.k1, 1u, t0 + (uint32_t)t);
       // CL: a clamped note's uniform (drawn and discarded) becomes 2 (forced off: never <= p) or -1 (forced on: always
       // <= p, p in [0, 1]), so phase 4 samples the constraint with no extra work; any other byte leaves the draw
       if (CL && writer && t >= a.S) {
         const uint32_t cb = cbuf[u];
         u_cur = cb == 0u ? 2.f : (cb == 1u ? -1.f : u_cur);
       }
-      if (!ZG && zdraw) e_cur = philox_normal_at(zidx, a.k0, a.k1, 0u, (uint32_t)(t + 1));
+      if (!ZG && zdraw) e_cur = philox_normal_at(zidx, a.k0, a.k1, 0u, t0 + (uint32_t)(t + 1));
       if (!ZG && TP) e_cur = a.Tz * e_cur;
     }
     step_barrier();
@@ -455,6 +481,16 @@ __global__ __launch_bounds__(GN_NT) void vrnn_generate_kernel(GenArgs a) {
     }
     step_barrier();
   }
+  // ST: the state after frame T-1, behind the loop's last barrier: the cells of frame T-1 wrote parity T & 1
+  if (ST && a.state_out && writer) {
+    // a writer lane has s = 0, so s * LH + u is its u: the offset the frame loop keeps for its kernel rows anyway, formed
+    // again here so that nothing new lives across the loop (the kernel is at its register budget)
+    const uint32_t su = (uint32_t)(s * LH + u);            // 32-bit offsets from the sequence's (uniform) base
+    float* so = a.state_out + (size_t)n * 5 * LH;
+    so[(enc ? 0u : 2u) * LH + su] = hb[enc ? 0 : 1][T & 1][PKP * (su / PKK) + (su % PKK)];
+    so[(enc ? 1u : 3u) * LH + su] = c;
+    if (enc) so[4u * LH + su] = xbuf[su];
+  }
 }
 
 }  // namespace clv
@@ -465,15 +501,17 @@ extern "C" int clv_vrnn_generate_supported(int D, int H, int L, int C) {
 
 namespace {
 using GenKernel = void (*)(clv::GenArgs);
-enum class Mode { generate, vary, decode };   // ancestral sampling | re-decoding | a given latent path
+enum class Mode { generate, vary, decode, resume };   // ancestral sampling | re-decoding | a given latent path
+                                                      // | ancestral sampling from and to a state
 
 // a runtime flag as a template argument: f(std::true_type) or f(std::false_type)
 template <class F>
 GenKernel with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 // The one kernel pick.  Every flag becomes a template argument once: first the mode's own tail of (CL, TP, VR, ZO, ZG) --
-// generate takes CL and TP as they come, vary and decode are the clamped, tempered VR instances with ZO or ZG -- then the
-// gate and ZW.  (4 + 2 + 1) tails x 2 gates x 2 widths = the 28 instances, none that the kernel's static_assert forbids.
+// generate takes CL and TP as they come, vary and decode are the clamped, tempered VR instances with ZO or ZG, resume is the
+// clamped, tempered ST instance -- then the gate and ZW.  (4 + 2 + 1 + 1) tails x 2 gates x 2 widths = the 32 instances, none
+// that the kernel's static_asserts forbid.
 template <bool... TAIL>
 GenKernel pick_gate_width(bool hard, bool wide) {
   return with_bool(hard, [=](auto HARD) { return with_bool(wide, [](auto ZW) -> GenKernel {
@@ -487,12 +525,14 @@ GenKernel pick_vrnn_kernel(Mode mode, bool hard, bool wide, bool clamped, bool t
         return pick_gate_width<decltype(CL)::value, decltype(TP)::value>(hard, wide); }); });
     case Mode::vary:
       return with_bool(latents_out, [=](auto ZO) { return pick_gate_width<true, true, true, decltype(ZO)::value>(hard, wide); });
+    case Mode::resume:
+      return pick_gate_width<true, true, false, false, false, true>(hard, wide);
     default:                   // Mode::decode
       return pick_gate_width<true, true, true, false, true>(hard, wide);
   }
 }
 
-// The one launcher: every refusal of the six entry points, the kernel pick and the launch.  `a` is the call as its entry
+// The one launcher: every refusal of the seven entry points, the kernel pick and the launch.  `a` is the call as its entry
 // point filled it (vary and decode: S = 0, nsteps = T; absent inputs null; absent temperatures 1.0f, which is exact).
 int vrnn_launch(const clv::GenArgs& a, Mode mode, bool tempered, int D, int H, int gate_act, void* stream) {
   using namespace clv;
@@ -509,6 +549,9 @@ int vrnn_launch(const clv::GenArgs& a, Mode mode, bool tempered, int D, int H, i
     return CLV_EINVAL;
   // ---- each mode's own inputs
   switch (mode) {
+    case Mode::resume:         // the kernel draws step t0 + T one frame ahead: it must not wrap
+      if ((uint64_t)a.t0 + (uint64_t)a.S + (uint64_t)a.nsteps > UINT32_MAX) return CLV_EINVAL;
+      [[fallthrough]];
     case Mode::generate:       // seed frames only if S > 0, samples only if nsteps > 0; a roll constrains at least one step
       if ((a.S > 0 && !a.x_seed) || (a.nsteps > 0 && !a.Xs) || (a.clamp && a.nsteps <= 0)) return CLV_EINVAL;
       break;
@@ -523,8 +566,10 @@ int vrnn_launch(const clv::GenArgs& a, Mode mode, bool tempered, int D, int H, i
   GenKernel kern = pick_vrnn_kernel(mode, gate_act == CLV_GATE_HARD_SIGMOID, a.L > GN_LMAX, a.clamp != nullptr, tempered, a.zout != nullptr);
   const size_t lds = (size_t)((decode ? 0 : LH * LG) + LH * LH) * sizeof(float);    // Kx_enc (with an encoder) and Wo
   if (!decode)
-    if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 156 * 1024)) return e;
+    // (the wide ST instances hold 3 KB more static LDS: they ask for what they use, so that the sum stays within 160 KB)
+    if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), mode == Mode::resume ? (int)lds : 156 * 1024)) return e;
   const char* label = decode ? "vrnn_decode" : mode == Mode::vary ? (a.zout ? "vrnn_vary_latents" : "vrnn_vary")
+                      : mode == Mode::resume ? "vrnn_generate_resume"
                       : tempered ? (a.clamp ? "vrnn_generate_tempered_clamped" : "vrnn_generate_tempered")
                                  : (a.clamp ? "vrnn_generate_clamped" : "vrnn_generate");
   hipStream_t s = (hipStream_t)stream;
@@ -595,6 +640,22 @@ extern "C" int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H
   set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
   a.z_prior = z_prior; a.x_seed = x_seed; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
   return vrnn_launch(a, Mode::generate, true, D, H, gate_act, stream);
+}
+
+extern "C" int clv_vrnn_generate_resume(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
+                                        uint64_t seed, const float* x_seed, const float* w,
+                                        const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                                        const float* Wz, const float* bz,
+                                        const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                                        const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                                        float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
+                                        float* state_out, float* Xs, float* xhat, void* stream) {
+  clv::GenArgs a = vrnn_args(N, S, nsteps, L, C, seed, clamp, Xs, xhat);
+  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
+  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
+  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
+  a.t0 = t0; a.state_in = state_in; a.state_out = state_out;
+  return vrnn_launch(a, Mode::resume, true, D, H, gate_act, stream);
 }
 
 extern "C" int clv_vrnn_vary_latents(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,

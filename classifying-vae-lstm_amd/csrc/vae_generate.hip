@@ -44,6 +44,9 @@ struct VaeGenArgs {
   float* zout;                  // ZO instance: [3,N,T,L] = (z_mean, z_log_var, z) of every frame
   const float* z_in;            // ZG instance: [N,T,L] the latent path that replaces the z-encoder's
   const int32_t* noise_rows;    // ZG instance: [N] the row whose uniforms sequence n draws, or null (n itself)
+  uint32_t t0;                  // ST instance: the Philox step of local frame 0 (frames and the roll stay local)
+  const float* state_in;        // ST instance: [N,2,88] rows x_in (the last frame), hist (the frame before it); replaces x_seed
+  float* state_out;             // ST instance: the same rows after the last frame, or null; may alias state_in
 };
 
 // sum over the notes that are on (two scalar masks: inputs 0..63 / 64..87) of row n of an LDS-resident [88][88] kernel,
@@ -81,9 +84,14 @@ __device__ __forceinline__ float gather_rows(const float* Kl, int j, unsigned lo
 // LDS copy of K_h).  x_seed holds the given HISTORY frames (with hist_source) or is null (the decoder runs on its own
 // samples); the uniforms are those of row noise_rows[n].  Two barriers per frame are left: the decoder's hidden layer |
 // output layer + sample; the z of frame t+1 is parked behind the first, after the hidden layer of frame t has read zbuf.
-template <bool CL, bool TP, bool VR = false, bool ZO = false, bool ZG = false>
+// ST = true (with CL and TP, not VR): resumable generation.  The z-encoder's first input and the decoder's
+// first history are the two rows of state_in (a fresh start: both the seed frame), every Philox step is t0 + t, and after
+// the last frame the writer lanes store the last two frames to state_out.  clamp may be null.  ST = false folds away.
+template <bool CL, bool TP, bool VR = false, bool ZO = false, bool ZG = false, bool ST = false>
 __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   static_assert((!ZO && !ZG) || (VR && CL && TP && !(ZO && ZG)), "ZO and ZG are variants of the VR instance");
+  static_assert(!ST || (CL && TP && !VR), "ST is a variant of the clamped, tempered generate instance");
+  constexpr bool NR = VR || ST;          // instances whose roll may be null
   extern __shared__ __attribute__((aligned(16))) float vg_lds[];
   float* Khl = vg_lds;                        // [88][88] frame rows of the z-encoder's hidden kernel (ZG: absent)
   float* Kdl = ZG ? vg_lds : Khl + LH * LH;   // [88][88] history rows of the decoder's hidden kernel (has_xp)
@@ -116,7 +124,8 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
   for (int i = tid; i < 2 * PK * PKP; i += VG_NT) (&hbuf[0][0])[i] = 0.f;
   if (tid < VG_LMAX) zbuf[tid] = (ZG && tid < L) ? zi_n[tid] : 0.f;       // ZG: z of frame 0, as it is
   if (tid < 128) {
-    xbuf[0][tid] = (tid < LH && (!ZG || a.x_seed)) ? a.x_seed[(size_t)n * (VR ? a.nsteps : 1) * LH + tid] : 0.f;
+    if (ST) xbuf[0][tid] = tid < LH ? a.state_in[(size_t)n * 2 * LH + tid] : 0.f;
+    else xbuf[0][tid] = (tid < LH && (!ZG || a.x_seed)) ? a.x_seed[(size_t)n * (VR ? a.nsteps : 1) * LH + tid] : 0.f;
     xbuf[1][tid] = xbuf[0][tid];
     if (VR) xhis[tid] = (a.x0 && tid < LH) ? a.x0[(size_t)n * LH + tid] : 0.f;
   }
@@ -150,13 +159,19 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
       const float h0 = xhis[lane], h1 = lane + 64 < LH ? xhis[lane + 64] : 0.f;
       his0 = __ballot(h0 != 0.f); his1 = __ballot(h1 != 0.f);
     }
+    if (ST) {             // the decoder's first history: the state's second row
+      const float* hs = a.state_in + ((size_t)n * 2 + 1) * LH;
+      const float h0 = hs[lane], h1 = lane + 64 < LH ? hs[lane + 64] : 0.f;
+      his0 = __ballot(h0 != 0.f); his1 = __ballot(h1 != 0.f);
+    }
   }
+  const uint32_t t0 = ST ? a.t0 : 0u;    // the Philox step of local frame 0
 
   for (int t = 0; t < a.nsteps; ++t) {
     // this frame's noise, drawn before anything depends on it
-    const float u_cur = writer ? philox_uniform_at((uint64_t)nrow * LH + o, a.k0, a.k1, 1u, (uint32_t)t) : 2.f;
+    const float u_cur = writer ? philox_uniform_at((uint64_t)nrow * LH + o, a.k0, a.k1, 1u, t0 + (uint32_t)t) : 2.f;
     // this frame's constraint, requested three barriers before phase 4 uses it (2: free)
-    const uint32_t cb = (CL && writer && !(VR && !a.clamp)) ? (uint32_t)a.clamp[((size_t)n * a.nsteps + t) * LH + o] : 2u;
+    const uint32_t cb = (CL && writer && !(NR && !a.clamp)) ? (uint32_t)a.clamp[((size_t)n * a.nsteps + t) * LH + o] : 2u;
     // VR: source frame t+1, the z-encoder's next input, requested a whole frame before it is published
     const float src_next = (VR && (!ZG || a.x_seed) && writer && t + 1 < a.nsteps) ? a.x_seed[((size_t)n * a.nsteps + t + 1) * LH + o] : 0.f;
     const bool zdraw = s == 0 && zslot && !(o_raw & 1);                 // the mean slot of latent l = o_raw / 2
@@ -164,7 +179,7 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
     if (ZG) {
       eps = zi_n[min((uint32_t)(t + 1) * (uint32_t)L + zl, zlast)];      // frame t+1's z: unconditional, index clamped
     } else {
-      eps = zdraw ? philox_normal_at((uint64_t)n * L + (o_raw >> 1), a.k0, a.k1, 0u, (uint32_t)t) : 0.f;
+      eps = zdraw ? philox_normal_at((uint64_t)n * L + (o_raw >> 1), a.k0, a.k1, 0u, t0 + (uint32_t)t) : 0.f;
       if (TP) eps = a.Tz * eps;
     }
     // 1. z-encoder hidden layer: relu(x_prev . K_h[frame rows] + (w . K_h[label rows] + b_h))
@@ -236,6 +251,13 @@ __global__ __launch_bounds__(VG_NT) void vae_generate_kernel(VaeGenArgs a) {
       cur0 = __ballot(x0 != 0.f); cur1 = __ballot(x1 != 0.f);
     }
   }
+  // ST: frame nsteps-1 sits in xbuf[nsteps & 1], behind the loop's last barrier; the other parity holds the frame before
+  // it (after one frame: the x_in this call started from)
+  if (ST && a.state_out && writer) {
+    float* so = a.state_out + (size_t)n * 2 * LH;
+    so[o] = xbuf[a.nsteps & 1][o];
+    so[LH + o] = xbuf[(a.nsteps + 1) & 1][o];
+  }
 }
 
 }  // namespace clv
@@ -246,14 +268,16 @@ extern "C" int clv_vae_generate_supported(int D, int H, int L, int C) {
 
 namespace {
 using VaeKernel = void (*)(clv::VaeGenArgs);
-enum class Mode { generate, vary, decode };   // ancestral sampling | re-decoding | a given latent path
+enum class Mode { generate, vary, decode, resume };   // ancestral sampling | re-decoding | a given latent path
+                                                      // | ancestral sampling from and to a state
 
 // a runtime flag as a template argument: f(std::true_type) or f(std::false_type)
 template <class F>
 VaeKernel with_bool(bool b, F f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 
 // The one kernel pick.  Every flag becomes a template argument once: generate takes CL and TP as they come, vary and decode
-// are the clamped, tempered VR instances with ZO or ZG: the 4 + 2 + 1 instances, none that the kernel's static_assert forbids.
+// are the clamped, tempered VR instances with ZO or ZG, resume is the clamped, tempered ST instance: the 4 + 2 + 1 + 1
+// instances, none that the kernel's static_asserts forbid.
 VaeKernel pick_vae_kernel(Mode mode, bool clamped, bool tempered, bool latents_out) {
   using namespace clv;
   switch (mode) {
@@ -262,12 +286,14 @@ VaeKernel pick_vae_kernel(Mode mode, bool clamped, bool tempered, bool latents_o
         return vae_generate_kernel<decltype(CL)::value, decltype(TP)::value>; }); });
     case Mode::vary:
       return with_bool(latents_out, [](auto ZO) -> VaeKernel { return vae_generate_kernel<true, true, true, decltype(ZO)::value>; });
+    case Mode::resume:
+      return vae_generate_kernel<true, true, false, false, false, true>;
     default:                   // Mode::decode
       return vae_generate_kernel<true, true, true, false, true>;
   }
 }
 
-// The one launcher: every refusal of the six entry points, the kernel pick and the launch.  `a` is the call as its entry
+// The one launcher: every refusal of the seven entry points, the kernel pick and the launch.  `a` is the call as its entry
 // point filled it (vary and decode: nsteps = T; absent inputs null; absent temperatures 1.0f, which is exact).
 int vae_launch(const clv::VaeGenArgs& a, Mode mode, bool tempered, int D, int H, void* stream) {
   using namespace clv;
@@ -277,11 +303,15 @@ int vae_launch(const clv::VaeGenArgs& a, Mode mode, bool tempered, int D, int H,
   if (!temper_factor_ok(a.inv_T, false) || !temper_factor_ok(a.Tz, true)) return CLV_EINVAL;
   if (!a.Kd || !a.bd || !a.Ko || !a.bo || !a.Xs) return CLV_EINVAL;
   // ---- the modes with a z-encoder: its frames (x_seed: the seed frame or the sources), its label, its half of the weights
-  if (!decode && (!a.x_seed || !a.w || !a.Kh || !a.bh || !a.Kz || !a.bz)) return CLV_EINVAL;
+  // (resume: the state's two rows stand for the seed frame)
+  if (!decode && (!(mode == Mode::resume ? a.state_in : a.x_seed) || !a.w || !a.Kh || !a.bh || !a.Kz || !a.bz)) return CLV_EINVAL;
   // ---- each mode's own inputs; what the kernel addresses in 32 bits
   const uint64_t frames = (uint64_t)a.N * a.nsteps;
   switch (mode) {
     case Mode::generate:       // nothing more (this family sets no bound on the roll)
+      break;
+    case Mode::resume:         // the last step drawn is t0 + nsteps - 1; the bound is cl_vrnn's, so that the two agree
+      if ((uint64_t)a.t0 + (uint64_t)a.nsteps > UINT32_MAX) return CLV_EINVAL;
       break;
     case Mode::vary:           // the latents out
       if (!a.w_dec || (a.zout && frames * a.L > UINT32_MAX)) return CLV_EINVAL;
@@ -295,6 +325,7 @@ int vae_launch(const clv::VaeGenArgs& a, Mode mode, bool tempered, int D, int H,
   if (!decode)
     if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), 96 * 1024)) return e;
   const char* label = decode ? "vae_decode" : mode == Mode::vary ? (a.zout ? "vae_vary_latents" : "vae_vary")
+                      : mode == Mode::resume ? "vae_generate_resume"
                       : tempered ? (a.clamp ? "vae_generate_tempered_clamped" : "vae_generate_tempered")
                                  : (a.clamp ? "vae_generate_clamped" : "vae_generate");
   hipStream_t s = (hipStream_t)stream;
@@ -349,6 +380,19 @@ extern "C" int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L,
   set_decoder(a, Kd, bd, Ko, bo);
   a.z_prior = z_prior; a.x_seed = x_seed; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
   return vae_launch(a, Mode::generate, true, D, H, stream);
+}
+
+extern "C" int clv_vae_generate_resume(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
+                                       uint64_t seed, const float* w, const float* Kh, const float* bh, const float* Kz,
+                                       const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
+                                       const uint8_t* clamp, float inv_temperature, float z_temperature, uint32_t t0,
+                                       const float* state_in, float* state_out, float* Xs, float* xhat, void* stream) {
+  clv::VaeGenArgs a = vae_args(N, nsteps, L, C, use_x_prev, seed, clamp, Xs, xhat);
+  set_encoder(a, Kh, bh, Kz, bz);
+  set_decoder(a, Kd, bd, Ko, bo);
+  a.z_prior = z_prior; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
+  a.t0 = t0; a.state_in = state_in; a.state_out = state_out;
+  return vae_launch(a, Mode::resume, true, D, H, stream);
 }
 
 extern "C" int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,

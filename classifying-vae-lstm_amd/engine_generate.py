@@ -190,14 +190,154 @@ def vary_args(sources, w_enc, w_dec, x0, history, clamp, D, C, device):
     return sources, w_enc, w_dec, x0, clamp_roll(clamp, N, int(sources.shape[1]), D, device), history == 'source'
 
 
+STATE_FIELDS = {'cl_vrnn': ('h_enc', 'c_enc', 'h_dec', 'c_dec', 'x'), 'cl_vae': ('x_in', 'hist')}
+STEP_MAX = 2 ** 32 - 1                  # the Philox step is a uint32
+
+
+class GenState:
+    """What a device sampler carries from one call to the next: float32 device tensors [N, width] and the
+    Philox step t of the next frame.  cl_vrnn: h_enc, c_enc, h_dec, c_dec [N, H] after the last frame's cells and x [N, D],
+    the input of the next step (the last clamped sample; the bridge sample after priming with nsteps = 0).  cl_vae: x_in
+    [N, D], the last frame, and hist [N, D], the frame before it.  Fields of equal width are views of one tensor `rows`
+    [N, fields, width], the layout the persistent kernels read and write.  A state is never written by a call that takes
+    it, so one state may be continued many times.  Access: state.h_enc, state['x'], state.tensors()."""
+
+    def __init__(self, kind, tensors, t, rows=None):
+        if kind not in STATE_FIELDS:
+            raise ValueError("kind must be one of %s, got %r" % (tuple(STATE_FIELDS), kind))
+        names = STATE_FIELDS[kind]
+        if isinstance(t, (bool, np.bool_)) or int(t) != t or not 0 <= int(t) <= STEP_MAX:
+            raise ValueError("t must be an integer in [0, 2^32), got %r" % (t,))
+        if rows is None:
+            if set(tensors) != set(names):
+                raise ValueError("a %s state holds %s, got %s" % (kind, names, tuple(sorted(tensors))))
+            ts = [tensors[k] for k in names]
+            for k, v in zip(names, ts):
+                if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.dim() != 2 or v.shape[0] != ts[0].shape[0] \
+                        or v.shape[0] < 1 or v.device != ts[0].device:
+                    raise ValueError("%s must be a float32 tensor [N, width] on the state's device, N >= 1" % k)
+            if len({int(v.shape[1]) for v in ts}) == 1:
+                rows = torch.stack(ts, 1).contiguous()
+        elif rows.dim() != 3 or rows.shape[1] != len(names) or rows.dtype != torch.float32 or not rows.is_contiguous():
+            raise ValueError("rows must be a contiguous float32 tensor [N, %d, width]" % len(names))
+        self.kind, self.t, self.rows = kind, int(t), rows
+        self._d = {k: rows[:, i] for i, k in enumerate(names)} if rows is not None else \
+            {k: tensors[k].contiguous() for k in names}
+
+    @classmethod
+    def fresh(cls, kind, cfg, device, N=None, seed_frame=None):
+        """the state a sampler starts from: cl_vrnn zero LSTM states and the zero frame for N sequences; cl_vae x_in = hist =
+        seed_frame [N, D]; t = 0"""
+        f = dict(dtype=torch.float32, device=device)
+        if kind == 'cl_vae':
+            x = device_f32(seed_frame, device)
+            if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != cfg['D']:
+                raise ValueError("seed_frame must be [N, %d] with N >= 1, got shape %s" % (cfg['D'], tuple(x.shape)))
+            return cls(kind, None, 0, rows=torch.stack([x, x], 1).contiguous())
+        return cls(kind, {k: torch.zeros(int(N), cfg['D'] if k == 'x' else cfg['H'], **f) for k in STATE_FIELDS[kind]}, 0)
+
+    @property
+    def N(self):
+        return int(self._d[STATE_FIELDS[self.kind][0]].shape[0])
+
+    @property
+    def device(self):
+        return self._d[STATE_FIELDS[self.kind][0]].device
+
+    def widths(self):
+        return {k: int(v.shape[1]) for k, v in self._d.items()}
+
+    def tensors(self):
+        """name -> tensor, in the family's order"""
+        return dict(self._d)
+
+    def __getitem__(self, name):
+        return self._d[name]
+
+    def __getattr__(self, name):
+        d = self.__dict__.get('_d')
+        if d is not None and name in d:
+            return d[name]
+        raise AttributeError(name)
+
+    def _like(self, f):
+        if self.rows is not None:
+            return GenState(self.kind, None, self.t, rows=f(self.rows).contiguous())
+        return GenState(self.kind, {k: f(v) for k, v in self._d.items()}, self.t)
+
+    def clone(self):
+        return self._like(lambda v: v.clone())
+
+    def select(self, index):
+        """rows by an integer index, repeats allowed: branching.  Row n of a call draws the noise of index n, so two copies
+        of one prefix at different rows continue differently."""
+        idx = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
+        if idx.ndim != 1 or idx.size < 1 or idx.dtype == np.bool_ or not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError("index must be a non-empty 1-D sequence of integers, got %r" % (index,))
+        if idx.min() < 0 or idx.max() >= self.N:
+            raise ValueError("index must lie in [0, %d), got [%d, %d]" % (self.N, idx.min(), idx.max()))
+        ix = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(self.device)
+        return self._like(lambda v: v.index_select(0, ix))
+
+    def to_numpy(self):
+        """a dict of float32 arrays and t (an int64 scalar array) that np.savez can hold"""
+        out = {k: v.detach().cpu().numpy().astype(np.float32, copy=True) for k, v in self._d.items()}
+        out['t'] = np.asarray(self.t, np.int64)
+        return out
+
+    @classmethod
+    def from_numpy(cls, d, device):
+        """the state of to_numpy() (or of np.load of its np.savez) on `device`; the family follows from the names"""
+        names = set(d.keys() if hasattr(d, 'keys') else d) - {'t'}
+        kinds = [k for k, f in STATE_FIELDS.items() if set(f) == names]
+        if not kinds or 't' not in (d.keys() if hasattr(d, 'keys') else d):
+            raise ValueError("not a sampler state: fields %s" % (tuple(sorted(names)),))
+        t = np.asarray(d['t'])
+        if t.size != 1:
+            raise ValueError("t must be one integer, got shape %s" % (t.shape,))
+        return cls(kinds[0], {k: device_f32(np.asarray(d[k]), device) for k in STATE_FIELDS[kinds[0]]}, int(t.reshape(())))
+
+
+def resume_args(state, kind, N, widths, nframes):
+    """Validate a sampler's state argument (None: a fresh start) against the call: a GenState of this family, N rows, the
+    model's widths (dict name -> width), and a last Philox step t + nframes that fits a uint32.  Returns t, the step of the
+    call's frame 0.  ValueError otherwise."""
+    if state is None:
+        t0 = 0
+    else:
+        if not isinstance(state, GenState):
+            raise ValueError("state must be a GenState, got %r" % type(state).__name__)
+        if state.kind != kind:
+            raise ValueError("a %s state cannot continue a %s model" % (state.kind, kind))
+        if N is not None and state.N != int(N):
+            raise ValueError("the state holds %d sequences, the call %d" % (state.N, N))
+        if state.widths() != dict(widths):
+            raise ValueError("the state's widths %s are not the model's %s" % (state.widths(), dict(widths)))
+        t0 = state.t
+    if t0 + int(nframes) > STEP_MAX:
+        raise ValueError("t = %d + %d frames passes the last Philox step 2^32 - 1" % (t0, nframes))
+    return t0
+
+
+def state_widths(kind, cfg):
+    return {k: cfg['H'] if k[0] in 'hc' and kind == 'cl_vrnn' else cfg['D'] for k in STATE_FIELDS[kind]}
+
+
 def generate_samples_numpy(engine, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False, temperature=1.0,
-                           z_temperature=1.0):
+                           z_temperature=1.0, state=None, return_state=False, kind=None):
     """generate_samples_device of both families: engine.generate, or with particles engine.generate_smc, on host arrays ->
-    [N, nsteps, D] float64 (and what smc_samples_numpy adds)"""
+    [N, nsteps, D] float64 (and what smc_samples_numpy adds; with return_state (Xs, GenState)).  kind: the family
+    ('cl_vrnn' | 'cl_vae'; default: the engine's)."""
     temper = dict(temperature=temperature, z_temperature=z_temperature)
     temper_args(**temper)
     d = engine.device
+    if state is not None or return_state:
+        return _resume_samples_numpy(engine, kind or engine.STATE_KIND, x_seeds, nsteps, w_vals, seed, z_prior, clamp,
+                                     particles is not None or w_prior is not None or return_evidence or return_key, temper,
+                                     state, return_state)
+    if x_seeds is None:
+        raise ValueError("give x_seeds (or a state to resume from)")
     xs = device_f32(x_seeds, d)
     if (w_vals is None) == (w_prior is None):
         raise ValueError("give exactly one of w_vals and w_prior")
@@ -213,6 +353,41 @@ def generate_samples_numpy(engine, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     clamp = clamp_roll(clamp, xs.shape[0], int(nsteps), engine.cfg['D'], d)
     return engine.generate(xs, w, int(nsteps), seed=int(seed), z_prior=z_prior, clamp=clamp,
                            **temper).cpu().numpy().astype(np.float64)
+
+
+def _resume_samples_numpy(engine, kind, x_seeds, nsteps, w_vals, seed, z_prior, clamp, smc, temper, state, return_state):
+    """generate_samples_numpy from and / or to a state: every refusal, then engine.generate"""
+    cfg, d = engine.cfg, engine.device
+    if smc:
+        raise ValueError("a state does not combine with particles (the filter's per-particle state is not carried)")
+    if w_vals is None:
+        raise ValueError("give w_vals")
+    if state is not None and not isinstance(state, GenState):
+        raise ValueError("state must be a GenState, got %r" % type(state).__name__)
+    if kind == 'cl_vae' and state is not None and x_seeds is not None:
+        raise ValueError("a cl_vae state holds its last two frames: give no x_seeds with it")
+    if x_seeds is None:
+        if state is None:
+            raise ValueError("give x_seeds or a state")
+        N = state.N
+        xs = torch.zeros(N, 0, cfg['D'], dtype=torch.float32, device=d) if kind == 'cl_vrnn' else None
+    else:
+        xs = device_f32(x_seeds, d)
+        if xs.dim() != (3 if kind == 'cl_vrnn' else 2) or xs.shape[0] < 1 or xs.shape[-1] != cfg['D']:
+            raise ValueError("x_seeds must be %s, got shape %s" % ("[N, S, %d]" % cfg['D'] if kind == 'cl_vrnn'
+                                                                    else "[N, %d]" % cfg['D'], tuple(xs.shape)))
+        N = int(xs.shape[0])
+    S = int(xs.shape[1]) if kind == 'cl_vrnn' else 0
+    resume_args(state, kind, N, state_widths(kind, cfg), S + int(nsteps))
+    w = device_f32(w_vals, d)
+    if tuple(w.shape) != (N, cfg['C']):
+        raise ValueError("w_vals must have shape %s, got %s" % ((N, cfg['C']), tuple(w.shape)))
+    clamp = clamp_roll(clamp, N, int(nsteps), cfg['D'], d)
+    out = engine.generate(xs, w, int(nsteps), seed=int(seed), z_prior=z_prior, clamp=clamp, state=state,
+                          return_state=return_state, **temper)
+    if return_state:
+        return out[0].cpu().numpy().astype(np.float64), out[1]
+    return out.cpu().numpy().astype(np.float64)
 
 
 def vary_samples_numpy(engine, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
@@ -331,11 +506,12 @@ class _NoiseRows:
             self.idx = noise_rows.to(torch.int64).contiguous()
             self.u_all = torch.zeros(self.R, D, dtype=torch.float32, device=device)
 
-    def draw(self, u, seed, counter):
+    def draw(self, u, seed, counter, step=0):
+        """the uniforms of Philox step `step` + the device counter (clv_philox_uniform adds the two)"""
         if self.nr is None:
-            ops.philox_uniform(u, self.N * self.D, seed, 0, 1, self.first, step_dev=counter)
+            ops.philox_uniform(u, self.N * self.D, seed, step, 1, self.first, step_dev=counter)
         else:
-            ops.philox_uniform(self.u_all, self.R * self.D, seed, 0, 1, 0, step_dev=counter)
+            ops.philox_uniform(self.u_all, self.R * self.D, seed, step, 1, 0, step_dev=counter)
             ops.gather_rows(self.N, self.D, self.u_all, self.idx, u)
 
 
@@ -533,10 +709,12 @@ class _Chain:
       encoder by one frame: cl_vae's generator, and a re-decoding on its source's history); 'shared', x_dec IS x_enc
       (cl_vrnn's generator); or a history [R, nsteps, D] (history[:, t], clv_take_frame).
     temper None or (inv_T, Tz) (temper_args): a factor other than 1 takes one more launch each, the head's sigmoid then
-    being sigmoid_temper's."""
+    being sigmoid_temper's.
+    t0 (DESIGN.md 16): the Philox step of the chain's frame 0, a host value the noise kernels add to the device counter;
+    the roll's row, the source frame and the seed hook keep counting from the chain's own frame 0."""
 
     def __init__(self, rows, w_enc, w_dec, nsteps, seed, temper, dec_prev, x_enc=None, x_dec=None, sources=None, z_path=None,
-                 z_prior=False, seed_frames=None, noise_rows=None, r0=0, clamp=None, S=0, smc=None):
+                 z_prior=False, seed_frames=None, noise_rows=None, r0=0, clamp=None, S=0, smc=None, t0=0):
         eng, R = rows.eng, rows.R
         D, L, d = eng.cfg['D'], eng.cfg['L'], eng.device
         new = lambda n: torch.zeros(R, n, dtype=torch.float32, device=d)
@@ -544,7 +722,7 @@ class _Chain:
         self.inv_T, self.Tz = (1.0, 1.0) if temper is None else temper
         self.sources, self.z_path, self.z_prior, self.seed_frames = sources, z_path, z_prior, seed_frames
         self.history, self.dec_prev = (None, dec_prev) if isinstance(dec_prev, str) else (dec_prev, 'history')
-        self.clamp, self.S, self.smc = clamp, S, smc
+        self.clamp, self.S, self.smc, self.t0 = clamp, S, smc, int(t0)
         if z_path is None:
             self.x_enc, self.eps = new(D) if x_enc is None else x_enc, new(L)
         self.x_dec = self.x_enc if self.dec_prev == 'shared' else new(D) if x_dec is None else x_dec
@@ -562,7 +740,7 @@ class _Chain:
             ops.take_frame(R, T, D, self.sources, c, self.x_enc)
         if self.z_path is None:
             rows.encode(self.x_enc, self.w_enc)
-            ops.philox_normal(self.eps, R * L, self.seed, 0, 0, self.r0 * L, step_dev=c)
+            ops.philox_normal(self.eps, R * L, self.seed, self.t0, 0, self.r0 * L, step_dev=c)
             if self.z_prior:
                 rows.zargs[:R].zero_()
             if self.Tz != 1.0:
@@ -574,7 +752,7 @@ class _Chain:
                     ACT_SIGMOID if self.inv_T == 1.0 else ACT_NONE)
         if self.inv_T != 1.0:
             ops.sigmoid_temper(R * D, rows.xhat, self.inv_T)
-        self.noise.draw(self.u, self.seed, c)
+        self.noise.draw(self.u, self.seed, c, self.t0)
         if self.smc is not None:
             self.smc.step(rows.xhat, self.u, c, self.x_next, self.gather)
         elif self.clamp is None:
@@ -610,6 +788,8 @@ class _Chain:
 
 
 class VaeGenerate:
+    STATE_KIND = 'cl_vae'
+
     def _weights(self, encoder=True):
         """the persistent kernels' weight arguments in the order ops.vae_* take them: the encoder half (vae_decode takes
         none), the decoder half, the head"""
@@ -618,7 +798,7 @@ class VaeGenerate:
         return enc + (p('decoder_h/kernel'), p('decoder_h/bias'), p('x_decoded_mean/kernel'), p('x_decoded_mean/bias'))
 
     def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None,
-                 temperature=1.0, z_temperature=1.0):
+                 temperature=1.0, z_temperature=1.0, state=None, return_state=False):
         """N independent sequences of `nsteps` frames on the device: the frame loop of cl_vae/model.py:28-41
         (z-encoder on the last frame, z ~ N(mean, exp(lv)) or N(0, 1), decoder on (w, z, frame before last),
         x ~ Bernoulli); eps and u come from the Philox streams 0 / 1 at step = frame index.  x_seed [N,D], w [N,C] device
@@ -628,8 +808,15 @@ class VaeGenerate:
         row t constrains frame t, which is then fed back like a sampled one: clamped ancestral sampling).
         temperature, z_temperature (temper_args): sample from the tempered model, x_hat = sigmoid(logit /
         temperature) and z = mean + exp(lv / 2) * z_temperature * eps, with the same Philox draws; xhat_out then holds the
-        tempered probabilities.  Both 1.0 (default): exactly the untempered launches."""
+        tempered probabilities.  Both 1.0 (default): exactly the untempered launches.
+        state, return_state: continue from a GenState (x_seed is then None: the state holds the last two
+        frames) with the Philox steps counted on from state.t, and / or return (Xs, GenState after the last frame).  A
+        piece generated in several such calls is bit for bit the piece of one call; the state is the same on both routes
+        and is not written.  Neither given (default): exactly the launches above."""
         cfg, d = self.cfg, self.device
+        if state is not None or return_state:
+            return self._generate_resume(x_seed, w, nsteps, seed, use_graph, z_prior, persistent, xhat_out, clamp,
+                                         temper_args(temperature, z_temperature), state, return_state)
         N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
         clamp = clamp_roll(clamp, N, nsteps, D, d)
         temper = temper_args(temperature, z_temperature)
@@ -647,6 +834,36 @@ class VaeGenerate:
                        x_dec=x_seed.to(**f).clone(), z_prior=z_prior, clamp=clamp)
         chain.run(nsteps, use_graph, lambda t: chain.store(t, Xs))
         return Xs
+
+    def _generate_resume(self, x_seed, w, nsteps, seed, use_graph, z_prior, persistent, xhat_out, clamp, temper, state,
+                         return_state):
+        """generate from a state (None: x_in = hist = x_seed, t = 0) and / or to one: the ST instance of the persistent
+        kernel, or the frame chain started from the state's two frames"""
+        cfg, d = self.cfg, self.device
+        D, L, nsteps = cfg['D'], cfg['L'], int(nsteps)
+        if state is None:
+            state = GenState.fresh('cl_vae', cfg, d, seed_frame=x_seed)
+        elif x_seed is not None:
+            raise ValueError("a cl_vae state holds its last two frames: give no x_seed with it")
+        N = int(w.shape[0])
+        t0 = resume_args(state, 'cl_vae', N, state_widths('cl_vae', cfg), nsteps)
+        if nsteps < 1:
+            raise ValueError("nsteps must be >= 1, got %r" % (nsteps,))
+        clamp = clamp_roll(clamp, N, nsteps, D, d)
+        f = dict(dtype=torch.float32, device=d)
+        Xs = torch.zeros(N, nsteps, D, **f)
+        w = w.to(**f).contiguous()
+        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
+            out = torch.empty(N, 2, D, **f) if return_state else None
+            ops.vae_generate_resume(N, nsteps, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], z_prior, seed, w, *self._weights(),
+                                    Xs, t0, state.rows, out, xhat=xhat_out, clamp=clamp, temper=temper)
+            return (Xs, GenState('cl_vae', None, t0 + nsteps, rows=out)) if return_state else Xs
+        chain = _Chain(_VaeRows(self, N), w, w, nsteps, seed, temper, 'enc_input', x_enc=state.x_in.clone(),
+                       x_dec=state.hist.clone(), z_prior=z_prior, clamp=clamp, t0=t0)
+        chain.run(nsteps, use_graph, lambda t: chain.store(t, Xs))
+        if not return_state:
+            return Xs
+        return Xs, GenState('cl_vae', None, t0 + nsteps, rows=torch.stack([chain.x_enc, chain.x_dec], 1).contiguous())
 
     def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
              z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
@@ -732,6 +949,8 @@ class VaeGenerate:
 
 
 class VrnnGenerate:
+    STATE_KIND = 'cl_vrnn'
+
     # -- stateful single-step inference (the reference's stateful batch-1 sub-models,
     #    cl_vrnn/model.py:116-162; here for any batch of independent sequences) -------------
     def new_state(self, B):
@@ -789,7 +1008,7 @@ class VrnnGenerate:
                       p('X_decoded_mean/kernel'), p('X_decoded_mean/bias'))
 
     def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None,
-                 temperature=1.0, z_temperature=1.0):
+                 temperature=1.0, z_temperature=1.0, state=None, return_state=False):
         """Autoregressive generation of N independent sequences on the device.  persistent=True (default where the
         shapes allow): the whole frame loop is ONE kernel, a workgroup per sequence (csrc/generate.hip); otherwise the
         per-frame chain below, captured once and replayed per frame.  Same Philox noise either way.
@@ -800,17 +1019,76 @@ class VrnnGenerate:
         temperature, z_temperature (temper_args): sample from the tempered model, x_hat = sigmoid(logit /
         temperature) and z = mean + exp(lv / 2) * z_temperature * eps, with the same Philox draws (runs that differ only in
         the temperature share their uniforms); xhat_out then holds the tempered probabilities.  Both 1.0 (default):
-        exactly the untempered launches."""
+        exactly the untempered launches.
+        state, return_state: start both LSTMs and the first input from a GenState instead of zero, with the
+        Philox steps counted on from state.t, and / or return (Xs, GenState after the last frame).  With a state x_seed
+        may be None or [N,0,D] (the free run goes on from the state's x) or hold more teacher-forced frames.  nsteps = 0
+        with seed frames primes a state: its x is then the bridge sample.  A piece generated in several such calls is bit
+        for bit the piece of one call; the state is the same on both routes and is not written.  Neither given (default):
+        exactly the launches above."""
         cfg = self.cfg
         temper = temper_args(temperature, z_temperature)
-        clamp = clamp_roll(clamp, int(x_seed.shape[0]), nsteps, cfg['D'], self.device)
+        resume = state is not None or return_state
+        if x_seed is None:
+            if state is None:
+                raise ValueError("give x_seed or a state")
+            x_seed = torch.zeros(state.N, 0, cfg['D'], dtype=torch.float32, device=self.device)
+        N, S, nsteps = int(x_seed.shape[0]), int(x_seed.shape[1]), int(nsteps)
+        t0 = resume_args(state, 'cl_vrnn', N, state_widths('cl_vrnn', cfg), S + nsteps) if resume else 0
+        if resume and S + nsteps < 1:
+            raise ValueError("nothing to run: no seed frame and nsteps = 0")
+        clamp = clamp_roll(clamp, N, nsteps, cfg['D'], self.device)
         if clamp is not None and nsteps == 0:
             clamp = None                # nothing is returned, so nothing is constrained
         if clamp is not None and clamp.numel() >= 2 ** 32:
             persistent = False
-        if persistent and ops.vrnn_generate_supported(cfg['D'], cfg['H'], cfg['L'], cfg['C']):
+        persistent = persistent and ops.vrnn_generate_supported(cfg['D'], cfg['H'], cfg['L'], cfg['C'])
+        if resume:
+            run = self._resume_persistent if persistent else self._resume_frames
+            kw = {} if persistent else dict(use_graph=use_graph)
+            x_seed = x_seed.to(dtype=torch.float32, device=self.device).contiguous()
+            return run(x_seed, w.to(dtype=torch.float32, device=self.device).contiguous(), nsteps, seed, z_prior, xhat_out,
+                       clamp, temper, t0, state, return_state, **kw)
+        if persistent:
             return self._generate_persistent(x_seed, w, nsteps, seed, z_prior, xhat_out, clamp, temper)
         return self._generate_frames(x_seed, w, nsteps, seed, use_graph, z_prior, clamp, temper)
+
+    def _resume_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp, temper, t0, state, return_state):
+        """the ST instances of csrc/generate.hip (they need D = H: one row width)"""
+        cfg = self.cfg
+        N, S, D = int(x_seed.shape[0]), int(x_seed.shape[1]), cfg['D']
+        f = dict(dtype=torch.float32, device=self.device)
+        Xs = torch.zeros(N, nsteps, D, **f)
+        out = torch.empty(N, 5, D, **f) if return_state else None
+        ops.vrnn_generate_resume(N, S, nsteps, D, cfg['H'], cfg['L'], cfg['C'], self.gate_act, z_prior, seed,
+                                 x_seed if S else None, w, *self._weights(), Xs if nsteps else None, t0,
+                                 None if state is None else state.rows, out, xhat=xhat_out, clamp=clamp, temper=temper)
+        return (Xs, GenState('cl_vrnn', None, t0 + S + nsteps, rows=out)) if return_state else Xs
+
+    def _resume_frames(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp, temper, t0, state, return_state,
+                       use_graph=True):
+        """_generate_frames with the rows' LSTM states and the first input taken from the state and read back"""
+        N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
+        Xs = torch.zeros(N, nsteps, self.cfg['D'], dtype=torch.float32, device=self.device)
+        rows = _VrnnRows(self, N)
+        chain = _Chain(rows, w, w, nsteps, seed, temper, 'shared', z_prior=z_prior, seed_frames=x_seed, clamp=clamp, S=S,
+                       t0=t0)
+        lstm = ('h_enc', 'c_enc', 'h_dec', 'c_dec')
+        if state is not None:
+            for k in lstm:
+                rows.st[k].copy_(state[k])
+            chain.x_enc.copy_(state.x)
+
+        def after(t):
+            if t >= S:
+                chain.store(t - S, Xs)
+
+        chain.run(S + nsteps, use_graph, after)
+        if not return_state:
+            return Xs
+        tensors = {k: rows.st[k].clone() for k in lstm}
+        tensors['x'] = chain.x_enc.clone()
+        return Xs, GenState('cl_vrnn', tensors, t0 + S + nsteps)
 
     def _generate_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp=None, temper=None):
         cfg = self.cfg

@@ -421,6 +421,28 @@ def vae_generate(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, x_seed, w, K
                                    *_ptrs(x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo)], clamp, temper, Xs, xhat)
 
 
+def vrnn_generate_resume(N, S, nsteps, D, H, L, Cn, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
+                         Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, t0, state_in, state_out, xhat=None, clamp=None,
+                         temper=None):
+    """vrnn_generate from and to a state (clv_vrnn_generate_resume): t0 the Philox step of the call's frame 0,
+    state_in / state_out [N,5,88] (h_enc, c_enc, h_dec, c_dec, x; either may be None, they may be one tensor); x_seed None
+    with S = 0, Xs None with nsteps = 0; clamp, temper as vrnn_generate's (None: no roll, both factors 1)"""
+    inv_T, Tz = (1.0, 1.0) if temper is None else temper
+    _sample("clv_vrnn_generate_resume", N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed),
+            *_ptrs(x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp),
+            float(inv_T), float(Tz), int(t0), *_ptrs(state_in, state_out, Xs, xhat))
+
+
+def vae_generate_resume(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs, t0, state_in,
+                        state_out, xhat=None, clamp=None, temper=None):
+    """vae_generate from and to a state (clv_vae_generate_resume): state_in [N,2,88] (x_in, hist) stands for the
+    seed frame, state_out may be None or state_in; the rest as vrnn_generate_resume"""
+    inv_T, Tz = (1.0, 1.0) if temper is None else temper
+    _sample("clv_vae_generate_resume", N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed),
+            *_ptrs(w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, clamp), float(inv_T), float(Tz), int(t0),
+            *_ptrs(state_in, state_out, Xs, xhat))
+
+
 def vrnn_vary(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
               Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None, temper=None):
     """cl_vrnn re-decoding of sources [N,T,D] in one persistent launch (clv_vrnn_vary); x0, clamp, xhat may be

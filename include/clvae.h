@@ -550,6 +550,34 @@ int clv_vae_decode(int N, int T, int D, int H, int L, int C, int use_x_prev, uin
                    const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
                    const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
                    float inv_temperature, float* Xs, float* xhat, void* stream);
+
+/* ------------------------------------------------ resumable generation (chunks, modulation, branching) --
+ * DESIGN.md 16.  clv_*_generate_tempered (roll nullable, both factors 1.0f exact) FROM and TO a state, with the Philox steps
+ * offset by t0: local frame t of the call draws step t0 + t, so a piece generated in several calls, each starting at the t
+ * the one before ended at, is bit for bit the piece of one call.  Seed frames, Xs, xhat and the roll stay indexed by the
+ * call's own frames.
+ * cl_vrnn: state_in / state_out [N,5,88] float32, rows h_enc, c_enc, h_dec, c_dec after the last frame's cells and x, the
+ * input of the next step (the last clamped sample; the bridge sample of step S-1 when nsteps = 0).  state_in NULL: the zero
+ * start of clv_vrnn_generate (x then matters only for S = 0: the zero frame).  With S = 0 the first input is row x, with
+ * S > 0 the seed frames are teacher-forced from the given LSTM states.  nsteps = 0 (priming on the seed) is allowed.
+ * cl_vae: state_in / state_out [N,2,88], rows x_in (the last frame) and hist (the frame before it); a fresh start is both
+ * rows = the seed frame, t0 = 0.  state_in is required (there is no seed argument).
+ * state_out NULL: not stored; it may alias state_in.  CLV_EINVAL for everything clv_*_generate_tempered refuses and for
+ * t0 + S + nsteps > UINT32_MAX (cl_vae: t0 + nsteps). */
+int clv_vrnn_generate_resume(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
+                             uint64_t seed, const float* x_seed, const float* w,
+                             const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
+                             const float* Wz, const float* bz,
+                             const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
+                             const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                             float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
+                             float* state_out, float* Xs, float* xhat, void* stream);
+int clv_vae_generate_resume(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
+                            const float* w, const float* Kh, const float* bh, const float* Kz, const float* bz,
+                            const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
+                            float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
+                            float* state_out, float* Xs, float* xhat, void* stream);
+
 /* Row-wise linear interpolation, one thread per element: out[r,:] = fmaf(alpha[r], b[ib[r],:], fmaf(-alpha[r], a[ia[r],:],
  * a[ia[r],:])) for R rows of n floats; exact at alpha = 0 (a's row) and alpha = 1 (b's row).  ia, ib [R] int32 row indices
  * into a and b (in range: the caller's contract). */
