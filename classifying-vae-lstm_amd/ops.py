@@ -889,6 +889,24 @@ def smc_take_w(G, P, Cn, n_out, picks, wr, w_out):
     check(_lib.lib().clv_smc_take_w(G, P, Cn, n_out, _ptr(picks), _ptr(wr), _ptr(w_out), _stream()), "clv_smc_take_w")
 
 
+def key_track_windows(N, T, D, Hd, Cn, hop, K, frames, piece_off, win_off, Kh, bh, Ka, ba, seed, piece0, wargs, logp):
+    """the label head on every window of N pieces of the uint8 roll frames [F, D] (clv_key_track_windows):
+    window j of piece n starts at frame j * hop and goes to row win_off[n] + j of wargs [Wtot, 2(Cn-1)] and logp [Wtot, Cn];
+    piece_off, win_off int64 [N+1] on the device; K = 0 the noise-free label, K >= 1 the mean over K label samples."""
+    check(_lib.lib().clv_key_track_windows(int(N), int(T), int(D), int(Hd), int(Cn), int(hop), int(K), _ptr(frames),
+                                           _ptr(piece_off), _ptr(win_off), _ptr(Kh), _ptr(bh), _ptr(Ka), _ptr(ba), int(seed),
+                                           int(piece0), _ptr(wargs), _ptr(logp), _stream()), "clv_key_track_windows")
+
+
+def key_track_smooth(N, Cn, win_off, logp, log_prior, log_trans, kappa, post, path, log_evidence, piece_post):
+    """forward-backward and Viterbi over the rows win_off[n] .. win_off[n+1] of logp [Wtot, Cn] per piece, in fp64
+    (clv_key_track_smooth): post [Wtot, Cn], path [Wtot] int32, log_evidence [N], piece_post [N, Cn]; log_prior [Cn] fp64
+    or None (uniform), log_trans [Cn, Cn] fp64 (row = from), 0 < kappa <= 1."""
+    check(_lib.lib().clv_key_track_smooth(int(N), int(Cn), _ptr(win_off), _ptr(logp), _ptr(log_prior), _ptr(log_trans),
+                                          float(kappa), _ptr(post), _ptr(path), _ptr(log_evidence), _ptr(piece_post),
+                                          _stream()), "clv_key_track_smooth")
+
+
 class Graph:
     """Capture the kernels enqueued inside the ``with`` block on the current stream; replay with launch()."""
 

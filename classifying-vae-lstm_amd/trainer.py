@@ -31,6 +31,9 @@ SMC_STREAM = 0xFFFFFFFD
 # and, for the keys of the particles when the filter infers the key (step 0: the categorical allocation's
 # uniform, index = GLOBAL melody; step 1: the logistic-normal eps, index = GLOBAL row * (C-1) + class), the one below that:
 SMC_W_STREAM = 0xFFFFFFFC
+# and, for the label noise of the key tracker (keytrack.py; step = sample k, index = (((GLOBAL piece) << 24) +
+# the window's first frame) * 32 + class; drawn inside csrc/key_track.hip), the one below that:
+KEY_STREAM = 0xFFFFFFFB
 
 
 class DevWindows:

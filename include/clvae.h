@@ -1005,6 +1005,41 @@ int clv_smc_w_posterior(int G, int P, int C, int nsteps, int S, const double* lo
                         double* out, void* stream);
 int clv_smc_take_w(int G, int P, int C, int n_out, const int32_t* picks, const float* wr, float* w_out, void* stream);
 
+/* ------------------------------------------------------------- key tracking --
+ * The label head at every offset of a piece, and its HMM smoothing.
+ *
+ * clv_key_track_windows: the label head of both families (cl_vrnn: T = seq_length, Hd = D; cl_vae: T = 1, Hd = class_dim_0)
+ * on every window of N pieces, straight from the byte roll.  frames [F, D] uint8 0/1 holds the pieces one after another,
+ * piece_off [N+1] (device int64) the first frame of piece n with piece_off[N] = F, win_off [N+1] (device int64) the first
+ * output row of piece n (win_off[N] is not read here; clv_key_track_smooth reads it).  With P_n = piece_off[n+1] -
+ * piece_off[n], window j < J_n = max(0, (P_n - T) / hop + 1) of piece n starts at frame t = j * hop of the piece and goes to
+ * row win_off[n] + j; no window reads past its piece, a piece shorter than T has no rows.  Per row:
+ *   hW = relu(flat(window) . Kh + bh) over the window's set notes only (the listed rows of Kh [T*D, Hd] added one after
+ *        another in ascending row order), wargs = hW . Ka + ba = [mean | log_var], Ka [Hd, 2(C-1)];
+ *   K = 0:  logp = log softmax([mean, 0]), shifted by its maximum -- the noise-free label;
+ *   K >= 1: logp_c = log((1/K) sum_k softmax([mean + exp(log_var / 2) * eps_k, 0])_c), k ascending, K <= 1024, with
+ *           eps_k[c] = the clv_philox_normal value of (seed, step k, stream 0xFFFFFFFB, index (((piece0 + n) << 24) + t) * 32
+ *           + c): a window's noise depends on its piece's global number and its start frame only.
+ * A row's results are bit for bit independent of what else the launch holds (other pieces, hop, N, its place in a tile); no
+ * atomics.  The entry cannot read the device-side offsets: the caller keeps every P_n below 2^24 (a longer piece gets no
+ * rows) and the rows of wargs [Wtot, 2(C-1)] and logp [Wtot, C] apart.  CLV_EINVAL before any device work unless N >= 1,
+ * T >= 1, D and Hd even and in [2, 128], 2 <= C <= 32, T * D <= 8192, hop >= 1, 0 <= K <= 1024, piece0 >= 0, no pointer
+ * NULL, Kh 8-byte aligned.
+ *
+ * clv_key_track_smooth: forward-backward and Viterbi over each piece's rows j < J_n = win_off[n+1] - win_off[n] (win_off
+ * ascending) in fp64, one workgroup per piece.  The emission of row j is exp(kappa * (logp[j, :] - max logp[j, :])),
+ * 0 < kappa <= 1; log_prior [C] (NULL: uniform), log_trans [C, C] (row = from), both finite.  post [Wtot, C] = the smoothed
+ * marginals, path [Wtot] = the Viterbi path (first index at every maximum), log_evidence [N] = the log normaliser,
+ * piece_post [N, C] = softmax(log_prior + kappa * sum_j logp[j, :]) (j ascending).  A piece without rows gets piece_post =
+ * softmax(log_prior), log_evidence = 0 and nothing else.  Fixed summation orders: bitwise reproducible. */
+int clv_key_track_windows(int N, int T, int D, int Hd, int C, int hop, int K, const uint8_t* frames,
+                          const int64_t* piece_off, const int64_t* win_off, const float* Kh, const float* bh,
+                          const float* Ka, const float* ba, uint64_t seed, int64_t piece0, float* wargs, float* logp,
+                          void* stream);
+int clv_key_track_smooth(int N, int C, const int64_t* win_off, const float* logp, const double* log_prior,
+                         const double* log_trans, double kappa, double* post, int32_t* path, double* log_evidence,
+                         double* piece_post, void* stream);
+
 /* ----------------------------------------------------------------- graphs --
  * thin wrappers so a host without HIP bindings can capture a step once and
  * replay it (launch-bound inner loops: SURVEY.md 7.1 step 8). */
