@@ -98,6 +98,8 @@ def test_gemm_strided_views(dev):
 
 
 def test_colsum_and_sum(dev):
+    """One shape, the two-stage path.  colsum_small_kernel, every chunk count of the final kernel, beta, ldx and sum_strided at its
+    edges, each against an fp64 reference with per-element bounds: tests/test_gpu_pointwise.py."""
     from clvae_amd import ops
     rng = np.random.default_rng(1)
     X = rng.standard_normal((3000, 90))
@@ -262,6 +264,8 @@ def test_lstm_seq_bwd_z_also_returns_the_latent_gradient(dev, B, Tn, nz, gate):
 
 
 def test_label_gauss_bernoulli(dev):
+    """One shape of each, tensor-wide tolerances.  Every gauss_fwd instantiation, C = 2 .. 32, the clip-out branch, padded leading
+    dimensions, the optional outputs and per-element bounds against an fp64 reference: tests/test_gpu_pointwise.py."""
     from clvae_amd import ops
     rng = np.random.default_rng(3)
     B, Cn, L, D = 37, 10, 3, 88
@@ -468,6 +472,8 @@ def test_gemm_grouped_tn(dev):
 
 
 def test_loss_sums(dev):
+    """One launch of short terms.  The four-in-flight float4 and scalar loops, their tails and the misaligned contiguous route,
+    against an fp64 reference: tests/test_gpu_pointwise.py."""
     from clvae_amd import ops
     rng = np.random.default_rng(6)
     a, b, c = rng.standard_normal(5000), rng.standard_normal(37), rng.standard_normal((29, 3))
