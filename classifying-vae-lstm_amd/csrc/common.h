@@ -123,7 +123,9 @@ __device__ __forceinline__ void bf16_split_pair_dot2(float a, float b, unsigned 
 
 // Keras 2.0.0 hard_sigmoid: clip(0.2*x + 0.5, 0, 1)
 __device__ __forceinline__ float hard_sigmoid(float z) { return fminf(fmaxf(0.2f * z + 0.5f, 0.0f), 1.0f); }
-// derivative; TF's clip passes the gradient at ties
+// derivative; like TF's clip it passes the gradient where y is 0 or 1 itself.  y is contracted to fma(0.2f, z, 0.5f), as in
+// lstm_common.h's gate_grad: at z = -2.5 that is -7.45e-9, below the range, so the gradient there is 0 (a separately
+// rounded product would give y = 0 and pass); it is the only float32 near +-2.5 at which the two roundings decide differently
 __device__ __forceinline__ float hard_sigmoid_grad(float z) {
   float y = 0.2f * z + 0.5f;
   return (y >= 0.0f && y <= 1.0f) ? 0.2f : 0.0f;

@@ -39,8 +39,12 @@ __device__ __forceinline__ float gate_fn(float z) {
   return GATE == CLV_GATE_HARD_SIGMOID ? hard_sigmoid(z) : sigmoidf_(z);
 }
 // y = gate_fn(z).  hard_sigmoid: the clip changes the value exactly when it is out of range, so "gradient passes"
-// (inside the range, ties included, like TF's clip) == "clipped value equals the unclipped one": one compare against
-// the fma the forward expression already holds instead of two range compares.
+// (inside the range, 0 and 1 themselves included, like TF's clip) == "clipped value equals the unclipped one": one compare
+// against the fma the forward expression already holds instead of two range compares.  The unclipped value is the FUSED
+// fma(0.2f, z, 0.5f) (hipcc contracts the expression, here and in hard_sigmoid): at z = -2.5 it is -7.45e-9, not the 0 that
+// a separately rounded product gives, so that one float32 is clipped and its gradient is 0, in every instance of
+// lstm_bwd_kernel and in lstm_any_bwd_kernel; no other float32 near +-2.5 depends on the rounding (+2.5 and +2.5 + 1 ulp
+// give 1 either way and pass).  tests/test_gpu_seq.py::test_the_tie_at_minus_2p5 reads it off dz.
 template <int GATE>
 __device__ __forceinline__ float gate_grad(float z, float y) {
   return GATE == CLV_GATE_HARD_SIGMOID ? ((0.2f * z + 0.5f) == y ? 0.2f : 0.0f) : y * (1.f - y);

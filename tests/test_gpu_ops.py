@@ -117,6 +117,8 @@ def test_colsum_and_sum(dev):
 
 @pytest.mark.parametrize("B,Tn,gate", [(3, 9, 0), (5, 1, 0), (4, 17, 1), (258, 4, 0), (516, 3, 1), (1024, 3, 0), (2048, 2, 0)])
 def test_lstm_seq_fwd_bwd(dev, B, Tn, gate):
+    """One tolerance per tensor.  Every stored value of every step, the edges of T, B and H and the KS = 8 instances, each against an fp64 reference
+    with per-element bounds: tests/test_gpu_seq.py."""
     from clvae_amd import ops
     H = 88
     rng = np.random.default_rng(B + Tn)
@@ -163,7 +165,9 @@ def test_lstm_seq_fwd_bwd_at_any_width(dev, monkeypatch, H, B, Tn, gate):
     """clv_lstm_seq_fwd / _bwd for H != 88 (csrc/lstm_any.hip; H == 88: the same kernels forced by CLV_LSTM_ANY=1): states,
     stored gates, final state, dz and its column sums against the oracle's LSTM (cl_vrnn/model.py:196-199 under K.rnn /
     K.gradients); 1, 2, 4, 8 k-slices per unit, widths beyond the 256 threads (two and four units per owner thread), an
-    initial state; then the stateful single-step form of sampling (T = 1, no cell / gate buffers, state in and out)."""
+    initial state; then the stateful single-step form of sampling (T = 1, no cell / gate buffers, state in and out).
+    Every stored value of every step, the edges of T, B and H and the KS = 8 instances, each against an fp64 reference
+    with per-element bounds: tests/test_gpu_seq.py."""
     from clvae_amd import ops
     if H == 88:
         monkeypatch.setenv("CLV_LSTM_ANY", "1")
@@ -213,7 +217,9 @@ def test_lstm_seq_fwd_bwd_at_any_width(dev, monkeypatch, H, B, Tn, gate):
 @pytest.mark.parametrize("B,Tn,gate", [(1027, 7, 0), (768, 3, 1), (2050, 2, 0), (769, 1, 0)])
 def test_lstm_seq_fwd_at_large_batches(dev, B, Tn, gate):
     """clv_lstm_seq_fwd at batches far beyond one row per CU (the generic chain's forward: dropout, CLV_USE_MX=0): 1, 2 or 4
-    rows per workgroup by what divides the batch."""
+    rows per workgroup by what divides the batch.
+    Every stored value of every step, the edges of T, B and H and the KS = 8 instances, each against an fp64 reference
+    with per-element bounds: tests/test_gpu_seq.py."""
     from clvae_amd import ops
     H = 88
     rng = np.random.default_rng(B + Tn)
@@ -240,7 +246,9 @@ def test_lstm_seq_fwd_at_large_batches(dev, B, Tn, gate):
 
 @pytest.mark.parametrize("B,Tn,nz,gate", [(6, 9, 32, 0), (1028, 3, 32, 0), (514, 4, 5, 1), (3, 1, 40, 0)])
 def test_lstm_seq_bwd_z_also_returns_the_latent_gradient(dev, B, Tn, nz, gate):
-    """clv_lstm_seq_bwd_z == clv_lstm_seq_bwd, plus dZ = dz . Kz^T from the same launch."""
+    """clv_lstm_seq_bwd_z == clv_lstm_seq_bwd, plus dZ = dz . Kz^T from the same launch.
+    Every stored value of every step, the edges of T, B and H and the KS = 8 instances, each against an fp64 reference
+    with per-element bounds: tests/test_gpu_seq.py."""
     from clvae_amd import ops
     H = 88
     rng = np.random.default_rng(B + nz)
