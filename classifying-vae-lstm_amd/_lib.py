@@ -145,6 +145,7 @@ SIGNATURES = {
     "clv_splitk_reduce_multi_outer": (_i, [_p, _i, _p, _p, _p, _i, _p, _p, _i,
                                            _i, _i, _i, _p, _i, _i, _p, _i, _p, _i, _p, _p, _i, _p, _p, _p]),
     "clv_lstm_wgrad_supported": (_i, [_i, _i, _i, _i, _i]),
+    "clv_lstm_wgrad_rows_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "clv_lstm_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "clv_lstm_wgrad_pair_supported": (_i, [_p, _p]),
     "clv_lstm_wgrad_pair_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),

@@ -16,7 +16,9 @@
 // (96 cycles per 16x16 tile and 32 k) replace 8 f32 MFMAs (256 cycles).  -DWB_PRODUCTS=9 keeps all nine (measured, us per
 // launch: 36.0 -> 33.8 at K = 32768, 218 -> 196 at K = 262144 with six; profiles/r04_out_head_log.txt).  Frames that are
 // exactly representable in bf16 (0/1 piano-roll, any uint8) need one piece: their 3 MFMAs are all kept, those products
-// stay exact.  The kernel is then bound by its data-moving waves (profiles/r04_mx_log.txt section 13), not by the matrix pipe.
+// stay exact.  A 32-row stage takes about 4000 cycles against 2592 of MFMAs: the MFMA waves' stage (their LDS reads included)
+// is 3400-3450 cycles, the data-moving waves' 3850 with two stages of counted loads in flight (it was 4450-4500 and a 4750-cycle
+// stage while their loop drained to vmcnt(0) every stage: PERFLOG "Kernel-gradient product: two stages of loads in flight").
 //
 // Decomposition: a workgroup (4 waves, one per SIMD) owns ALL output rows x half of the 4H columns (176 = 11 column
 // tiles, padded to 12) for K / splits rows; accumulators stay in registers (up to 168 per lane).  Per 32-row stage the
@@ -147,6 +149,21 @@ __device__ __forceinline__ float4 wb_widen(const float4& raw) {      // four byt
   return make_float4((float)(v & 0xffu), (float)((v >> 8) & 0xffu), (float)((v >> 16) & 0xffu), (float)(v >> 24));
 }
 
+// buffer loads: an offset outside the descriptor's records reads 0 and touches no memory
+typedef __amdgpu_buffer_rsrc_t wb_rsrc_t;
+typedef unsigned wb_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ wb_rsrc_t wb_rsrc(const void* p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ float wb_u2f(unsigned u) { return __builtin_bit_cast(float, u); }   // (by value: see wb_widen)
+__device__ __forceinline__ float4 wb_load4(wb_rsrc_t r, unsigned voff, unsigned soff) {
+  const wb_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
+  return make_float4(wb_u2f(v[0]), wb_u2f(v[1]), wb_u2f(v[2]), wb_u2f(v[3]));
+}
+__device__ __forceinline__ float wb_load1(wb_rsrc_t r, unsigned voff, unsigned soff) {
+  return wb_u2f(__builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
+}
+
 template <int HM, int XP, bool XU8 = false>
 __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
   static_assert(!XU8 || XP == 1, "byte frames are one bf16 piece");
@@ -215,55 +232,49 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
       z_g[i] = 4u * (unsigned)((ez / nz1) * a.ldz + ez % nz1);
       z_l[i] = (((ez / nz1) * HPB + 2 * (a.nh + ez % nz1)) ^ WB_SWZ_OF(ez / nz1)) | (ok ? 0 : IDLE);
     }
-    // A stage is "interior" when all of its 32 rows exist, the shifted H rows exist, and a window start can only be its
-    // first row or its 17th (h_zero_period a multiple of 16 -- the reference's default seq_length is 16; k_begin is a
-    // multiple of 32 by construction).  Interior stages take the fast path: no clamps, no masks, one select for the H
-    // rows of a window start.
+    // One load sequence per stage, the same on every path (buffer loads: what lies outside the descriptor reads as 0 and
+    // touches no memory).  Each operand's descriptor covers exactly the rows of this workgroup's range, so the rows of a
+    // ragged last stage, whole stages beyond the range (the pipeline requests them: no load sits behind a condition) and
+    // the H row in front of row 0 need neither clamps nor masks; an absent Z has no records at all.  The stage's row offset
+    // travels in the scalar offset (the range check of gfx950 includes it: tools/probes/buffer_oob_probe.hip), except for H,
+    // whose offset can be negative (row k - h_shift of the first range): added per lane in 32 bits, it wraps beyond the
+    // records.  Why one sequence: between a request and its use the compiler must be able to COUNT the memory operations
+    // on every path, or it waits for all of them (vmcnt(0)) -- tools/wgrad_waits.py checks the loop that comes out.
+    const int rows = max(k_end - k_begin, 0);
+    auto span = [](int r, int ld, int n, int esz) { return r > 0 ? (int)(((unsigned)(r - 1) * (unsigned)ld + (unsigned)n) * (unsigned)esz) : 0; };
+    const int hrow0 = max(k_begin - a.h_shift, 0);            // first row of H this range reads
+    const wb_rsrc_t r_dz = wb_rsrc(a.dz + (size_t)k_begin * a.lddz, span(rows, a.lddz, a.N, 4));
+    const wb_rsrc_t r_h = wb_rsrc(a.H + (size_t)hrow0 * a.ldh, span(k_end - a.h_shift - hrow0, a.ldh, a.nh, 4));
+    const wb_rsrc_t r_x = wb_rsrc(static_cast<const char*>(a.X) + (size_t)k_begin * a.ldx * (XU8 ? 1 : 4), span(rows, a.ldx, a.nx, XU8 ? 1 : 4));
+    const wb_rsrc_t r_z = wb_rsrc(a.nz > 0 ? a.Z + (size_t)k_begin * a.ldz : nullptr, a.nz > 0 ? span(rows, a.ldz, a.nz, 4) : 0);
+    const int h_first = (k_begin - a.h_shift - hrow0) * a.ldh * 4;      // <= 0: byte offset of the H row of the range's first dz row
+    // a window start can only be row 0 or row 16 of a stage when h_zero_period is a multiple of 16 (the reference's default
+    // seq_length is 16; k_begin is a multiple of 32 by construction): one select per flagged slot instead of a division
     const bool aligned = a.h_zero_period == 0 || a.h_zero_period % (WB_KS / 2) == 0;
-    auto interior = [&](int s) { const int k0 = k_begin + s * WB_KS; return aligned && k0 + WB_KS <= k_end && k0 >= a.h_shift; };
 
     // Two stages of operands in flight per thread (register sets A and B): one stage of MFMAs (~1.5 us) is less than a
     // load takes under load, with one set the producers waited for memory every stage.
     struct Regs { float4 dz[DZ_L], h[A_L], x[A_L]; float z[Z_L]; };
     Regs ra, rb;
-    auto load_stage = [&](Regs& q, int s) {        // nothing uses the values until store_stage()
+    auto load_stage = [&](Regs& q, int s) {        // nothing uses the values until store_stage(); issue order = use order
       if (WB_ABLATE == 3 && s > 2) return;
-      const int k0 = k_begin + s * WB_KS;
-      if (interior(s)) {                           // uniform base + per-lane 32-bit offset
-        const char* dzb = reinterpret_cast<const char*>(a.dz + (size_t)k0 * a.lddz);
-        const char* hb = reinterpret_cast<const char*>(a.H + (size_t)(k0 - a.h_shift) * a.ldh);
-        const char* xb = static_cast<const char*>(a.X) + (size_t)k0 * a.ldx * (XU8 ? 1 : 4);
+      // (readfirstlane: the loop's strength-reduced offsets otherwise live in vector registers, and every load with such a
+      // scalar offset becomes a waterfall loop of its own)
+      const unsigned us = (unsigned)__builtin_amdgcn_readfirstlane(s);
+      const unsigned so_dz = us * (unsigned)(WB_KS * 4) * (unsigned)a.lddz;
+      const unsigned so_x = us * (unsigned)(WB_KS * (XU8 ? 1 : 4)) * (unsigned)a.ldx;
+      const unsigned so_z = us * (unsigned)(WB_KS * 4) * (unsigned)a.ldz;
+      const unsigned vo_h = (unsigned)h_first + us * (unsigned)(WB_KS * 4) * (unsigned)a.ldh;
 #pragma unroll
-        for (int i = 0; i < DZ_L; ++i) q.dz[i] = *reinterpret_cast<const float4*>(dzb + dz_g[i]);
-#pragma unroll
-        for (int i = 0; i < A_L; ++i) {
-          q.h[i] = *reinterpret_cast<const float4*>(hb + h_g[i]);
-          if (XU8) q.x[i].x = *reinterpret_cast<const float*>(xb + x_g[i]);       // (raw dword = four frames' bytes: widened in store_stage)
-          else q.x[i] = *reinterpret_cast<const float4*>(xb + x_g[i]);
-        }
-        if (a.nz > 0) {
-          const char* zb = reinterpret_cast<const char*>(a.Z + (size_t)k0 * a.ldz);
-#pragma unroll
-          for (int i = 0; i < Z_L; ++i) q.z[i] = *reinterpret_cast<const float*>(zb + z_g[i]);
-        }
-        return;
-      }
-      // first / last stage of the matrix: row indices clamped into it (the values of rows outside are masked later)
-      auto row = [&](unsigned g, int ld, int shift, unsigned esz = 4u) { const int r = (int)(g / esz) / ld; return min(max(k0 + r - shift, 0), a.K - 1) - r; };
-#pragma unroll
-      for (int i = 0; i < DZ_L; ++i)
-        q.dz[i] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(a.dz + (size_t)row(dz_g[i] - 4u * n0, a.lddz, 0) * a.lddz) + dz_g[i]);
+      for (int i = 0; i < DZ_L; ++i) q.dz[i] = wb_load4(r_dz, dz_g[i], so_dz);
 #pragma unroll
       for (int i = 0; i < A_L; ++i) {
-        q.h[i] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(a.H + (size_t)row(h_g[i], a.ldh, a.h_shift) * a.ldh) + h_g[i]);
-        if (XU8) q.x[i].x = *reinterpret_cast<const float*>(static_cast<const char*>(a.X) + (size_t)row(x_g[i], a.ldx, 0, 1u) * a.ldx + x_g[i]);
-        else q.x[i] = *reinterpret_cast<const float4*>(static_cast<const char*>(a.X) + (size_t)row(x_g[i], a.ldx, 0) * a.ldx * 4 + x_g[i]);
+        q.h[i] = wb_load4(r_h, h_g[i] + vo_h, 0u);
+        if (XU8) q.x[i].x = wb_load1(r_x, x_g[i], so_x);       // (raw dword = four frames' bytes: widened in store_stage)
+        else q.x[i] = wb_load4(r_x, x_g[i], so_x);
       }
-      if (a.nz > 0) {
 #pragma unroll
-        for (int i = 0; i < Z_L; ++i)
-          q.z[i] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.Z + (size_t)row(z_g[i], a.ldz, 0) * a.ldz) + z_g[i]);
-      }
+      for (int i = 0; i < Z_L; ++i) q.z[i] = wb_load1(r_z, z_g[i], so_z);
     };
     auto keep = [](const float4& v, bool live) { return live ? v : make_float4(0.f, 0.f, 0.f, 0.f); };
     auto store_stage = [&](const Regs& q, int s) {    // fp32 -> bf16 pieces -> LDS images of buffer s & 1
@@ -271,31 +282,26 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
       char* dzi = lds + (s & 1) * BUF;
       char* hi = dzi + G::DZ_BYTES;
       char* xi = hi + G::H_BYTES;
-      const bool fast = interior(s);
       const bool wstart = a.h_zero_period != 0 && k0 % a.h_zero_period == 0;     // row 0 of the stage starts a window
       const bool wstart16 = a.h_zero_period != 0 && (k0 + WB_KS / 2) % a.h_zero_period == 0;      // ... row 16 does
 #pragma unroll
-      for (int i = 0; i < DZ_L; ++i) {
-        const int r = (dz_l[i] & OFFM) / WB_DZP;
-        const float4 v = fast ? q.dz[i] : keep(q.dz[i], k0 + r < k_end);
-        if (i + 1 < DZ_L || !(dz_l[i] & IDLE)) put4<3>(dzi + (dz_l[i] & OFFM), WB_KS * WB_DZP, v);
-      }
+      for (int i = 0; i < DZ_L; ++i)
+        if (i + 1 < DZ_L || !(dz_l[i] & IDLE)) put4<3>(dzi + (dz_l[i] & OFFM), WB_KS * WB_DZP, q.dz[i]);
 #pragma unroll
       for (int i = 0; i < A_L; ++i) {
-        const int rh = (h_l[i] & OFFM) / HPB, rx = (x_l[i] & OFFM) / WB_AP, k = k0 + rh;
         // H'_k = h of the previous step; zero at the start of a window
-        const bool live = fast ? !((wstart && (h_l[i] & ROW0)) || (wstart16 && (h_l[i] & ROW16)))
-                               : (k < k_end && k >= a.h_shift && (a.h_zero_period == 0 || k % a.h_zero_period != 0));
+        bool live;
+        if (aligned) live = !((wstart && (h_l[i] & ROW0)) || (wstart16 && (h_l[i] & ROW16)));
+        else live = (k0 + (h_l[i] & OFFM) / HPB) % a.h_zero_period != 0;
         if (i + 1 < A_L || !(h_l[i] & IDLE)) put4<3>(hi + (h_l[i] & OFFM), WB_KS * HPB, keep(q.h[i], live));
         const float4 xv = XU8 ? wb_widen(q.x[i]) : q.x[i];
-        if (i + 1 < A_L || !(x_l[i] & IDLE)) put4<XP>(xi + (x_l[i] & OFFM), WB_KS * WB_AP, fast ? xv : keep(xv, k0 + rx < k_end));
+        if (i + 1 < A_L || !(x_l[i] & IDLE)) put4<XP>(xi + (x_l[i] & OFFM), WB_KS * WB_AP, xv);
       }
       if (a.nz > 0) {
 #pragma unroll
         for (int i = 0; i < Z_L; ++i) {
           unsigned p[3];
-          const int r = (z_l[i] & OFFM) / HPB;
-          split_pair((fast || k0 + r < k_end) ? q.z[i] : 0.f, 0.f, p);
+          split_pair(q.z[i], 0.f, p);
           if (!(z_l[i] & IDLE)) {
 #pragma unroll
             for (int w = 0; w < 3; ++w) *reinterpret_cast<unsigned short*>(hi + w * WB_KS * HPB + (z_l[i] & OFFM)) = (unsigned short)p[w];
@@ -303,30 +309,34 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a) {
         }
       }
     };
-    // stage s lives in set A for even s, set B for odd s
-    if (nstage > 0) {
-      load_stage(ra, 0);
-      if (nstage > 1) load_stage(rb, 1);
-      store_stage(ra, 0);
-      if (nstage > 2) load_stage(ra, 2);
-    }
+    // stage s lives in set A for even s, set B for odd s.  Stages beyond the range are requested and converted like the
+    // others (zeros, into the buffer nobody reads any more), so that the loop holds no conditional load.
+    load_stage(ra, 0);
+    load_stage(rb, 1);
+    store_stage(ra, 0);
+    load_stage(ra, 2);
     stage_barrier();
     // during stage s (consumers on buffer s & 1): convert stage s + 1 into the other buffer (last read in stage s - 1,
     // i.e. before the barrier every wave has passed), then request stage s + 3 into the registers that just emptied
-    for (int s = 0; s < nstage; s += 2) {
+    for (int s = 0; s + 1 < nstage; s += 2) {
       WBSTAMP(0, s);
-      if (s + 1 < nstage) store_stage(rb, s + 1);
-      if (s + 3 < nstage) load_stage(rb, s + 3);
+      store_stage(rb, s + 1);
+      load_stage(rb, s + 3);
       WBSTAMP(1, s);
       stage_barrier();
-      if (s + 1 < nstage) {
-        WBSTAMP(0, s + 1);
-        if (s + 2 < nstage) store_stage(ra, s + 2);
-        if (s + 4 < nstage) load_stage(ra, s + 4);
-        WBSTAMP(1, s + 1);
-        stage_barrier();
-      }
+      WBSTAMP(0, s + 1);
+      store_stage(ra, s + 2);
+      load_stage(ra, s + 4);
+      WBSTAMP(1, s + 1);
+      stage_barrier();
     }
+    if (nstage & 1) {                             // the last stage of an odd count is converted already: its barrier
+      WBSTAMP(0, nstage - 1);
+      WBSTAMP(1, nstage - 1);
+      stage_barrier();
+    }
+    // (the loads still in flight lie beyond the range: nothing to wait for, but no wave ends with requests outstanding)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     return;
   }
 
@@ -446,6 +456,15 @@ extern "C" int clv_debug_wb_wg(unsigned long long* host_out) {
 
 static bool wgrad_wide(int nh, int nz) { return nh + nz > 96 || nz > 8; }
 
+// The producers address every operand through a buffer descriptor with 32-bit byte offsets, and request up to 4 stages
+// plus one stage of rows beyond a range (those read as 0): K + 160 rows of every operand have to stay below 2 GiB.
+extern "C" int clv_lstm_wgrad_rows_supported(int K, int ldx, int x_exact_bf16, int ldh, int ldz, int nz, int lddz) {
+  if (K <= 0 || ldx <= 0 || ldh <= 0 || lddz <= 0 || (nz > 0 && ldz <= 0)) return 0;
+  const unsigned long long rows = (unsigned long long)K + 160, lim = 1ull << 31;
+  return rows * (unsigned)ldx * (x_exact_bf16 == CLV_FRAMES_U8 ? 1 : 4) < lim && rows * (unsigned)ldh * 4 < lim &&
+         rows * (unsigned)lddz * 4 < lim && (nz == 0 || rows * (unsigned)ldz * 4 < lim);
+}
+
 extern "C" int clv_lstm_wgrad_supported(int N, int nx, int nh, int nz, int x_exact_bf16) {
   if (!(N == 352 && nx > 0 && nx <= 96 && nx % 4 == 0 && nh > 0 && nh <= 96 && nh % 4 == 0 && nz >= 0 && nz <= 32 &&
         nh + nz <= 128))
@@ -482,6 +501,7 @@ extern "C" int clv_lstm_wgrad(int K, int N, const void* X, int ldx, int nx, int 
     return CLV_EINVAL;
   const bool xu8 = x_exact_bf16 == CLV_FRAMES_U8;           // the frames as bytes (ldx in bytes): 4-byte aligned rows
   if (ldx % 4 || ldh % 4 || lddz % 4 || ((uintptr_t)H | (uintptr_t)dz) % 16 || ((uintptr_t)X) % (xu8 ? 4 : 16)) return CLV_EINVAL;
+  if (!clv_lstm_wgrad_rows_supported(K, ldx, x_exact_bf16, ldh, ldz, nz, lddz)) return CLV_EINVAL;
   if (clv_lstm_wgrad_workspace_bytes(K, N, nx, nh, nz, split_scale) > ws_bytes || !ws || ((uintptr_t)ws) % 16) return CLV_EWORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const int splits = wgrad_splits(K, split_scale);
@@ -524,6 +544,7 @@ static bool wgrad_problem_ok(const clv_wgrad_problem& p) {
   if (!clv_lstm_wgrad_supported(p.N, p.nx, p.nh, p.nz, p.x_exact_bf16) || p.K <= 0 || !p.X || !p.H || !p.dz || !p.dKx || !p.dU ||
       (p.nz > 0 && (!p.Z || !p.dKz)))
     return false;
+  if (!clv_lstm_wgrad_rows_supported(p.K, p.ldx, p.x_exact_bf16, p.ldh, p.ldz, p.nz, p.lddz)) return false;
   return !(p.ldx % 4 || p.ldh % 4 || p.lddz % 4 || ((uintptr_t)p.H | (uintptr_t)p.dz) % 16 ||
            ((uintptr_t)p.X) % (p.x_exact_bf16 == CLV_FRAMES_U8 ? 4 : 16));
 }

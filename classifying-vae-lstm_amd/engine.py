@@ -743,6 +743,8 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         if not (self.bf16_wgrad and nx > 0 and ops.lstm_wgrad_supported(4 * H, nx, H, nz, self.frames_exact_bf16)):
             return None
         xs, xs_ld = (X_in, x_ld) if (x8 is None or nx == 0) else (x8, nx)
+        if not ops.lstm_wgrad_rows_supported(self.B * T, 4 * H, xs, xs_ld, self.frames_exact_bf16, H, x_ld, nz):
+            return None                               # an operand of 2 GiB or more: the f32 grouped GEMM
         return (self.B * T, 4 * H, xs, xs_ld, nx, self.frames_exact_bf16, hs, H, H, T, X_in[:, nx:] if nz else None, x_ld, nz,
                 dz, P.g(name + '/kernel'), P.g(name + '/recurrent_kernel'),
                 P.rows(P.grads, name + '/kernel', nx) if nz else None)

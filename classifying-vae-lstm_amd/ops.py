@@ -153,6 +153,11 @@ def lstm_wgrad_supported(N, nx, nh, nz, x_exact_bf16):
     return bool(_lib.lib().clv_lstm_wgrad_supported(N, nx, nh, nz, int(bool(x_exact_bf16))))
 
 
+def lstm_wgrad_rows_supported(K, N, X, ldx, x_exact_bf16, ldh, ldz, nz):
+    """Do K rows of these strides stay inside the kernel's 32-bit offsets (every operand below 2 GiB: include/clvae.h)?"""
+    return bool(_lib.lib().clv_lstm_wgrad_rows_supported(K, ldx, _frames_mode(X, x_exact_bf16), ldh, ldz, nz, N))
+
+
 def lstm_wgrad(K, N, X, ldx, nx, x_exact_bf16, H, ldh, nh, T, Z, ldz, nz, dz, dKx, dU, dKz, ws, defer=None, beta=0.0,
                split_scale=1):
     """All kernel gradients of one LSTM in one pass over dz (split-bf16 products, 6 of the 9 piece pairs: fp32-rounding

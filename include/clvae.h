@@ -235,6 +235,11 @@ int clv_splitk_reduce_multi_outer(const clv_reduce_job* jobs, int njobs, const f
 #define CLV_FRAMES_F32_EXACT 1   /* float rows whose values are exactly bf16 numbers */
 #define CLV_FRAMES_U8        2   /* uint8 rows */
 int clv_lstm_wgrad_supported(int N, int nx, int nh, int nz, int x_exact_bf16);
+/* The kernel addresses X, H, Z and dz through buffer descriptors with 32-bit byte offsets and requests up to 160 rows
+ * beyond a row range (they read as 0 and touch no memory): (K + 160) rows of every operand -- (K + 160) * ld * element
+ * size -- must stay below 2 GiB.  clv_lstm_wgrad answers CLV_EINVAL and clv_lstm_wgrad_pair_supported 0 otherwise; a
+ * caller asks here first and hands larger problems to clv_gemm_grouped_tn. */
+int clv_lstm_wgrad_rows_supported(int K, int ldx, int x_exact_bf16, int ldh, int ldz, int nz, int lddz);
 /* split_scale (1..8): that many times as many, proportionally shorter row ranges (and slabs).  1 = one workgroup per CU,
  * the fastest grid on an idle GPU; 2 is what the data-parallel step uses: the gradient all-reduce's kernel holds a few
  * CUs while these products run, and a grid of exactly one workgroup per CU would then need a whole second round. */
