@@ -11,6 +11,7 @@ layer/weight order), each starting on a 16-byte boundary of one flat fp32
 buffer; gradients, Adam m/v use the same layout; the weight-norm column state
 (s, m_g, v_g) is a second flat layout over the last axis of every matrix.
 """
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -100,7 +101,40 @@ def _f(device, *shape):
     return torch.empty(*shape, dtype=torch.float32, device=device)
 
 
+# Where a pass draws its noise: the Philox streams of eps_w / eps_z, their first indices (global rows), the step (plus the
+# device counter step_dev).  What TrainStep.noise_spec() returns; a plain 7-tuple in this order is accepted wherever one is.
+NoiseSpec = collections.namedtuple('NoiseSpec', 'seed stream_w stream_z first_w first_z step step_dev')
+
+
+class _Pass:
+    """What one cl_vrnn pass (VrnnEngine.forward / loss_and_grads, up to grads_tail) knows about itself: how it was asked
+    to run, and what its launches have done already."""
+    __slots__ = ('f8', 'noise', 'stage', 'adjacent', 'train', 'keep_logits', 'nll_done', 'head_done', 'head_grad_done',
+                 'loss_terms', 'hw_outer')
+
+    def __init__(self, f8=None, stage=None, adjacent=False, train=False, keep_logits=True):
+        self.f8 = f8                     # (X8, Xp8): the pass reads its frames from these uint8 batches
+        self.noise = None                # the noise_draw structs of (eps_W, eps_Z) when the kernels draw them themselves
+        self.stage = stage               # ops.label_stage: the label launch assembles the mini-batch
+        self.adjacent = adjacent         # nothing reads the gradients between the two halves of the backward pass
+        self.train = train               # LSTM(dropout=p) applies
+        self.keep_logits = keep_logits
+        self.nll_done = self.head_done = self.head_grad_done = False      # NLL / output head's / latent head's gradients formed
+        self.loss_terms = None           # the loss means when they ride in the reduction launch that ends grads_tail()
+        self.hw_outer = None             # the hW kernel gradient's arguments while it waits for that launch
+
+
+# One LSTM's kernel-gradient products: per-step inputs X [rows x B*T] (x8: their frame rows as a uint8 batch), outputs hs, dz
+_Wgrad = collections.namedtuple('_Wgrad', 'name X ldx rows hs dz x8')
+
+
 class _EngineBase:
+    # What TrainStep asks of an engine; VaeEngine / VrnnEngine override what they implement.
+    keep_logits = True           # the training pass stores its logits
+    off = 0                      # history-frame rows in front of the decoder kernel
+    fuse_notes = False           # the staging launch leaves note lists (notes_enc / notes_dec; notes_valid: they describe the batch)
+    gdot = None                  # sum g.V of the largest kernel, left by the backward pass when gdot_fresh
+
     def __init__(self, cfg, batch_size, shapes, device, head_pairs=(), grads_pre=0):
         _lib.require_gpu()
         self.cfg = dict(cfg)
@@ -117,6 +151,26 @@ class _EngineBase:
         self.kl_weight = float(cfg.get('kl_weight', 1.0))
         self.w_kl_weight = float(cfg.get('w_kl_weight', 1.0))
         self.class_weight = float(cfg.get('class_weight', 1.0))
+        # per staged batch (TrainStep).  frames_exact_bf16: every frame value is exactly a bf16 number (the data set is kept as uint8;
+        # the frame rows of the kernel-gradient products then use one bf16 piece instead of three); notes_valid: of the note lists
+        self.frames_exact_bf16 = bool(cfg.get('frames_exact_bf16', False))
+        self.notes_valid = False
+        self.gdot_fresh = False
+
+    def frames_u8_route(self):
+        """How a training pass can take its frames as bytes (loss_and_grads(frames8=...)): 'gather', 'label' or None"""
+        return None
+
+    def can_stage_in_label(self):
+        """Can the step's first launch assemble the mini-batch itself (loss_and_grads(stage=ops.label_stage(...)))?"""
+        return False
+
+    def tail_range(self):
+        """(offset, numel) of the gradient bucket that is complete before grads_tail()"""
+        return 0, 0
+
+    def grads_tail(self, X, frames8=None):
+        """The late part of a loss_and_grads(do_tail=False) pass: nothing unless the engine splits its backward pass"""
 
     def losses(self):
         """Host copy of the last step's loss terms (one small D2H)."""
@@ -160,9 +214,9 @@ class VaeEngine(VaeGenerate, _EngineBase):
         B, D, H, L, Hc, Cn = self.B, cfg['D'], cfg['H'], cfg['L'], cfg['Hc'], cfg['C']
         d = self.device
         self.xoff = D if cfg['use_x_prev'] else 0      # decoder_h kernel rows: [w | xp | z]
+        self._last_xp = None         # the history frames of the last forward(), for x_hat() without hidden layers
         L_ = _lib.lib()
         self.fused = H > 0 and bool(cfg.get('fused_step', True)) and bool(L_.clv_vae_fused_supported(D, H, Hc, Cn, L))
-        self.stage_spec = None       # set by TrainStep for one fused step: see _fused_step
         names = ['h_w', 'wargs', 'h', 'zargs', 'decoder_h', 'x_decoded_mean']
         self._offs = (C.c_int64 * 12)(*[self.P.offsets.get('%s/%s' % (n, w), 0) for n in names for w in ('kernel', 'bias')])
         ws_bytes = L_.clv_vae_fused_workspace_bytes(B, D, H, Hc, Cn, L, int(cfg['use_x_prev'])) if self.fused else 0
@@ -256,7 +310,7 @@ class VaeEngine(VaeGenerate, _EngineBase):
         ops.gauss_fwd(B, L, self.zargs, eps_z, self.z, L, self.rowkl)
         self.decode(self.w, self.z, xp)
 
-    def _fused_step(self, x, xp, w_true, eps_w, eps_z, need_grads, target=None, noise=None, bump=False):
+    def _fused_step(self, x, xp, w_true, eps_w, eps_z, need_grads, target=None, noise=None, bump=False, stage=None):
         """The whole step as ONE kernel (csrc/vae_fused.hip) + one launch that sums the gradient slabs, takes the loss
         means and (bump) advances the step counter."""
         cfg, P, B = self.cfg, self.P, self.B
@@ -265,15 +319,14 @@ class VaeEngine(VaeGenerate, _EngineBase):
         opts.loss_means = p_(self.scal)
         opts.bf16 = int(bool(cfg.get('bf16', False)))
         if noise is not None:
-            (opts.noise_seed, opts.stream_w, opts.stream_z, opts.first_w, opts.first_z, opts.step), step_dev = noise[:6], noise[6]
-            opts.draw, opts.step_dev = 1, p_(step_dev)
+            opts.noise_seed, opts.stream_w, opts.stream_z, opts.step = noise.seed, noise.stream_w, noise.stream_z, noise.step
+            opts.first_w, opts.first_z, opts.draw, opts.step_dev = noise.first_w, noise.first_z, 1, p_(noise.step_dev)
         if bump and need_grads:
             opts.bump_iterations = p_(P.iterations)
         tail = (p_(eps_w), p_(eps_z), p_(P.params), self._offs, P.n, float(cfg['w_log_var_prior']), self.class_weight,
                 self.kl_weight, self.w_kl_weight, int(need_grads), p_(P.grads), p_(self._fused_ws), self._fused_ws.numel(),
                 p_(self.logits), p_(self.w), p_(self.wargs), p_(self.zargs), p_(self.rownll), p_(self.rowkl),
                 p_(self.rowloss), C.byref(opts), ops._stream())
-        stage, self.stage_spec = self.stage_spec, None
         # stage: TrainStep handed over the mini-batch assembly (ops.label_stage): the kernel reads its rows' byte frames itself
         staged = stage is not None and target is None
         _lib.check(_lib.lib().clv_vae_fused_step(
@@ -289,21 +342,22 @@ class VaeEngine(VaeGenerate, _EngineBase):
         own launches (the fused kernel): the caller then skips its own draw and passes advanced=True to adam_step."""
         return bool(self.fused and w_true is not None)
 
-    def loss_and_grads(self, x, xp, w_true, eps_w, eps_z, need_grads=True, target=None, noise=None, bump=False):
+    def loss_and_grads(self, x, xp, w_true, eps_w, eps_z, need_grads=True, target=None, noise=None, bump=False, stage=None):
         """One forward + 4 losses (+ gradients of the weighted total into P.grads).  target: what the decoder output is
         scored against (default x; the next frame under --predict_next).
-        noise = (seed, stream_w, stream_z, first_w, first_z, step, step_dev): draw eps_w / eps_z (into the buffers
-        passed) instead of reading them; bump: advance P.iterations once the gradients are in (only honoured together
-        with folds_step())."""
+        noise (a NoiseSpec, or its 7 values): draw eps_w / eps_z (into the buffers passed) instead of reading them; bump:
+        advance P.iterations once the gradients are in (only honoured together with folds_step()); stage (ops.label_stage,
+        where can_stage_in_label()): the fused kernel assembles the mini-batch itself."""
         cfg, P, B = self.cfg, self.P, self.B
         D, H, L, Hc, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['Hc'], cfg['C']
         C1 = Cn - 1
         inv = 1.0 / B
+        noise = None if noise is None else NoiseSpec(*noise)
         if self.fused and w_true is not None:
-            return self._fused_step(x, xp, w_true, eps_w, eps_z, need_grads, target, noise, bump)
+            return self._fused_step(x, xp, w_true, eps_w, eps_z, need_grads, target, noise, bump, stage)
         if noise is not None:
-            ops.philox_normal2(eps_w, B * C1, noise[1], noise[3], eps_z, B * L, noise[2], noise[4], noise[0], noise[5],
-                               step_dev=noise[6])
+            ops.philox_normal2(eps_w, B * C1, noise.stream_w, noise.first_w, eps_z, B * L, noise.stream_z, noise.first_z,
+                               noise.seed, noise.step, step_dev=noise.step_dev)
         self.forward(x, xp, eps_w, eps_z, w_true)
         ops.bernoulli_nll(B, D, self.logits, x if target is None else target, D, inv, self.rownll,
                           self.dlogits if need_grads else None)
@@ -398,7 +452,7 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         self.dropout = float(cfg.get('dropout', 0.0) or 0.0)
         if not 0.0 <= self.dropout < 1.0:
             raise ValueError("dropout must be in [0, 1)")
-        self._train_pass = False
+        self._pending = None         # the pass between loss_and_grads(do_tail=False) and grads_tail(): the only per-pass state here
         # which kernels the chains take: SWITCHES (cfg key -> what it selects), each narrowed by what the shapes support
         sw = lambda key: switch(cfg, key)
         self.fuse_pair = sw('fuse_pair') and ops.lstm_pair_supported(L, H) and not self.dropout
@@ -406,19 +460,13 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         self.pair_pack = _f(d, ops.lstm_pair_pack_floats()) if self.fuse_pair else None
         self.sparse_inputs = sw('sparse_inputs') and ops.sparse_proj_supported(D, 4 * H)
         self.fuse_head = sw('fuse_head') and ops.out_head_train_supported(H, D)
-        self._head_done = False
         self.keep_logits = sw('keep_logits')
         self.bf16_wgrad = sw('bf16_wgrad')
-        # every staged frame value is exactly a bf16 number (TrainStep sets it when the data set is kept as uint8): the frame
-        # rows of the kernel-gradient products then use one bf16 piece instead of three
-        self.frames_exact_bf16 = bool(cfg.get('frames_exact_bf16', False))
         self.wgrad_pair = sw('wgrad_pair')
         self.dense_hw_grad = sw('dense_hw_grad')
         # (from 512 batch rows on: at 256 rows the note-walking gather is as fast, 20.5 against 12.5 + 11.7 us)
         self.dense_hw_fwd = sw('dense_hw_fwd') and B >= int(os.environ.get('CLV_DENSE_HW_FWD_ROWS', '512'))
         self.ws_hw = None
-        self.stage_spec = None       # set by TrainStep for one forward pass: see _forward_pair
-        self._f8 = None              # the pass's uint8 frames (forward(frames8=...))
         self.ws_b = None
         self.label_in_pair = sw('label_in_pair') and self.fuse_pair
         self.fuse_latent = sw('fuse_latent') and ops.latent_head_supported(H, L)
@@ -427,14 +475,15 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         self.frames_u8 = sw('frames_u8')
         self.front_fused = sw('front_fused')
         # the hW kernel gradient rides in the reduction launch that ends grads_tail() -- when nothing reads it in between:
-        # loss_and_grads(do_tail=True) knows that by itself; a caller that runs the two halves one after the other sets
-        # halves_adjacent for one pass (TrainStep: exactly when it has no all-reduce to start between them)
+        # loss_and_grads(do_tail=True) knows that by itself; a caller that runs the two halves one after the other says so
+        # with adjacent=True (TrainStep: exactly when it has no all-reduce to start between them)
         self.tail_launch = sw('tail_launch')
-        self.halves_adjacent = False
-        self._hw_outer = None        # the product's arguments while it is pending (loss_and_grads -> grads_tail)
-        # notes_valid: the note lists describe the frames now in X / XZ (TrainStep sets it per staged batch)
+        # (notes_valid: the note lists describe the frames now in X / XZ; TrainStep sets it per staged batch)
         self.fuse_notes = sw('fuse_notes') and self.fuse_pair and self.sparse_inputs and D == ops.NOTE_NONE
-        self.notes_valid = False
+        # shape predicates that several chains must agree on
+        self.label_walks_notes = self.sparse_inputs and D % 2 == 0      # the note-walking label kernel runs (vrnn_label_fwd_x)
+        self.dense_window_ok = ops.dense_window_fwd_bf16_supported(B, T * D, D, T * D, D)     # the dense hW forward product
+        self.skinny_label_rows = Cn + 1 <= 16 and B <= 4096      # both LSTMs' label rows + biases in one launch (grads_tail)
         if self.fuse_notes:
             self.notes_enc = torch.full((BT, ops.NOTE_ROW), ops.NOTE_NONE, dtype=torch.uint8, device=d)
             self.notes_dec = torch.full((BT, ops.NOTE_ROW), ops.NOTE_NONE, dtype=torch.uint8, device=d)
@@ -473,7 +522,6 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         # sum_j hW/kernel[j,c] * its gradient[j,c] (FlatParams.adam_step): in front of the gradient buffer, so that the
         # data-parallel step averages it with the hW kernel's bucket
         self.gdot = self.P.grads_pre[:D] if (self.P.grads_pre.numel() >= D and self.P.offsets['hW/kernel'] == 0) else _f(d, D)
-        self.gdot_fresh = False
         if self.dropout:
             in_e, in_d = D + Cn, self.off + L + Cn
             self.u_enc, self.u_dec = _f(d, B, 4, in_e), _f(d, B, 4, in_d)          # the masks uniforms [row][gate][input] (clv_dropout_rows)
@@ -489,7 +537,7 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
     def folds_noise(self):
         """True when forward(noise=...) draws eps_W / eps_Z inside the label kernel and the pair kernels / the latent head of the
         large-batch path (no Philox launch)."""
-        return bool((self.fuse_pair or (self.use_mx and self.fuse_latent)) and self.sparse_inputs and self.cfg['D'] % 2 == 0)
+        return bool((self.fuse_pair or (self.use_mx and self.fuse_latent)) and self.label_walks_notes)
 
     def frames_u8_route(self):
         """How a training pass can get its frames as BYTES (frames8 of forward / loss_and_grads / grads_tail: a uint8 batch copied out
@@ -506,7 +554,7 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                 and ops.lstm_wgrad_supported(4 * H, D, H, 0, 2) and (not self.off or ops.lstm_wgrad_supported(4 * H, D, H, L, 2))):
             return None
         if self.use_mx:
-            return 'gather' if (self.dense_hw_fwd and ops.dense_window_fwd_bf16_supported(B, T * D, D, T * D, D)) else None
+            return 'gather' if (self.dense_hw_fwd and self.dense_window_ok) else None
         if self.fuse_pair and self.can_stage_in_label():
             return 'label'
         return None
@@ -514,49 +562,50 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
     def frames_u8_supported(self):
         return self.frames_u8_route() is not None
 
-    def forward(self, X, Xp, eps_W, eps_Z, w_true=None, keep_gates=True, nll=None, target=None, noise=None, frames8=None):
+    def forward(self, X, Xp, eps_W, eps_Z, w_true=None, keep_gates=True, nll=None, target=None, noise=None, frames8=None,
+                pass_=None):
         """nll = (scale, need_grads): fuse the Bernoulli NLL of the output head into its GEMM; target = the frames the
         output is scored against (default X).
         frames8 = (X8, Xp8): uint8 [B,T,D] copies of the batch's current / history frames (Xp8 None without history) -- the pass
         then reads its frames from THEM, as bytes, and X / Xp are not read at all (frames_u8_supported(); training passes
         whose target is X).
-        noise = (seed, stream_w, stream_z, first_w, first_z, step, step_dev): draw eps_W / eps_Z (into the buffers passed)
-        instead of reading them -- inside the label and pair kernels where they run, else with one Philox launch."""
+        noise (a NoiseSpec, or its 7 values): draw eps_W / eps_Z (into the buffers passed) instead of reading them -- inside
+        the label and pair kernels where they run, else with one Philox launch.
+        pass_: the pass's record when loss_and_grads() runs this as its first half (its f8 is frames8)."""
         if frames8 is not None and (target is not None or not self.frames_exact_bf16 or not self.frames_u8_supported()):
             raise ValueError("frames8 needs the large-batch path (frames_u8_supported()), frames_exact_bf16 and the input frames as "
                              "the target")
-        self._f8 = frames8
+        pass_ = _Pass(f8=frames8, keep_logits=self.keep_logits) if pass_ is None else pass_
         target = X if target is None else target
         cfg, P, B = self.cfg, self.P, self.B
-        self._nll_done = False
-        self._noise = None
         if noise is not None:
+            n = noise = NoiseSpec(*noise)
             if self.folds_noise():
-                seed, sw, sz, fw, fz, step, step_dev = noise
-                self._noise = (ops.noise_draw(seed, sw, fw, step, step_dev), ops.noise_draw(seed, sz, fz, step, step_dev))
+                pass_.noise = (ops.noise_draw(n.seed, n.stream_w, n.first_w, n.step, n.step_dev),
+                               ops.noise_draw(n.seed, n.stream_z, n.first_z, n.step, n.step_dev))
             else:
-                ops.philox_normal2(eps_W, B * (cfg['C'] - 1), noise[1], noise[3], eps_Z, B * cfg['T'] * cfg['L'], noise[2],
-                                   noise[4], noise[0], noise[5], step_dev=noise[6])
+                ops.philox_normal2(eps_W, B * (cfg['C'] - 1), n.stream_w, n.first_w, eps_Z, B * cfg['T'] * cfg['L'], n.stream_z,
+                                   n.first_z, n.seed, n.step, step_dev=n.step_dev)
         D, H, L, T, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['T'], cfg['C']
         C1, BT, G4 = Cn - 1, B * T, 4 * H
         g, ws = ops.gemm, self.ws
         if cfg['use_x_prev'] and frames8 is None and Xp.data_ptr() != self.XZ.data_ptr():
             self.XZ.view(B, T, self.xz_ld)[:, :, :D].copy_(Xp.view(B, T, D))     # staging copy only
         if self.fuse_pair:
-            return self._forward_pair(X, eps_W, eps_Z, w_true, nll, target)
+            return self._forward_pair(pass_, X, eps_W, eps_Z, w_true, nll, target)
         if self.use_mx:
-            return self._forward_mx(X, eps_W, eps_Z, w_true, nll, target)
-        if self.dropout and self._train_pass:
+            return self._forward_mx(pass_, X, eps_W, eps_Z, w_true, nll, target)
+        if self.dropout and pass_.train:
             if noise is not None:      # this step's masks: uniforms of the streams 2 (encoder) and 3 (decoder), by GLOBAL row
-                row0 = int(noise[3]) // max(cfg['C'] - 1, 1)
+                row0 = int(noise.first_w) // max(cfg['C'] - 1, 1)
                 for u, sid in ((self.u_enc, 2), (self.u_dec, 3)):
                     per_row = u.shape[1] * u.shape[2]
-                    ops.philox_uniform(u, B * per_row, noise[0], noise[5], sid, row0 * per_row, step_dev=noise[6])
+                    ops.philox_uniform(u, B * per_row, noise.seed, noise.step, sid, row0 * per_row, step_dev=noise.step_dev)
                 self._masks_given = True
             elif not self._masks_given:
                 raise RuntimeError("training pass with dropout=%g and neither noise=... nor set_dropout_uniforms(): the masks "
                                    "would come from uninitialised memory" % self.dropout)
-            return self._forward_dropout(X, eps_W, eps_Z, w_true, nll, target)
+            return self._forward_dropout(pass_, X, eps_W, eps_Z, w_true, nll, target)
         if self.sparse_inputs:     # add the kernel rows of the notes that are on (csrc/sparse_proj.hip)
             ops.sparse_proj(BT, D, G4, X, D, P.p('encoder_h/kernel'), self.gates_enc)
         else:
@@ -564,64 +613,71 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                 g(X, P.p('encoder_h/kernel'), self.gates_enc, BT, G4, D, ws=self.ws2)
         # label path (:174-191)
         off = self.off
-        self._label_forward(X, eps_W, w_true)
+        self._label_forward(pass_, X, eps_W, w_true)
         self._join()
         ops.lstm_seq_fwd(B, T, self.gates_enc, self.wk_enc, P.p('encoder_h/recurrent_kernel'), self.hs_enc,
                          self.cs_enc, self.gates_enc, gate_act=self.gate_act, H=H)
-        # latent heads + sample (:200-216)
-        if self.fuse_latent:       # one launch on the matrix cores (csrc/latent_head.hip)
-            ops.latent_head_fwd(BT, H, L, self.hs_enc, P.p('Zargs/kernel'), P.p('Zargs/bias'), eps_Z, self.zargs, self.Z,
-                                self.xz_ld, self.rowkl)
-        else:
-            g(self.hs_enc, P.p('Zargs/kernel'), self.zargs, BT, 2 * L, H, bias=P.p('Zargs/bias'), ws=ws)
-            ops.gauss_fwd(BT, L, self.zargs, eps_Z, self.Z, self.xz_ld, self.rowkl)
+        self._latent_fwd(pass_, eps_Z)      # latent heads + sample (:200-216)
         # decoder LSTM on [Xp, Z, repeat(W)] (:218-228): one projection of the [Xp | Z] rows
         self._join()
         g(self.XZ, P.p('decoder_h/kernel'), self.gates_dec, BT, G4, off + L, lda=self.xz_ld, ws=ws)
         ops.lstm_seq_fwd(B, T, self.gates_dec, self.wk_dec, P.p('decoder_h/recurrent_kernel'), self.hs_dec,
                          self.cs_dec, self.gates_dec, gate_act=self.gate_act, H=H)
         # output head (:229-234), with the NLL fused into its epilogue when the caller wants the loss
-        self._output_head(target, nll)
+        self._output_head(pass_, target, nll)
 
-    def _forward_mx(self, X, eps_W, eps_Z, w_true, nll, target):
+    def _latent_fwd(self, pass_, eps_Z):
+        """zargs = hs_enc . Zargs/kernel + bias, the sample Z (into [Xp | Z]) and the rows' KL: one launch on the matrix cores
+        (csrc/latent_head.hip; eps_Z drawn in it when the pass folds its noise), or GEMM + pointwise."""
+        cfg, P = self.cfg, self.P
+        H, L, BT = cfg['H'], cfg['L'], self.B * cfg['T']
+        if self.fuse_latent:
+            ops.latent_head_fwd(BT, H, L, self.hs_enc, P.p('Zargs/kernel'), P.p('Zargs/bias'), eps_Z, self.zargs, self.Z,
+                                self.xz_ld, self.rowkl, noise=pass_.noise[1] if pass_.noise else None)
+        else:
+            ops.gemm(self.hs_enc, P.p('Zargs/kernel'), self.zargs, BT, 2 * L, H, bias=P.p('Zargs/bias'), ws=self.ws)
+            ops.gauss_fwd(BT, L, self.zargs, eps_Z, self.Z, self.xz_ld, self.rowkl)
+
+    def _latent_bwd(self, pass_, eps_Z, dZ, defer):
+        """dzargs and dL/dh_enc (into self.dhs) from dZ.  The one-launch form keeps dzargs on chip and forms the head's own
+        kernel / bias gradient too (pass_.head_grad_done; defer: the queue that takes its slabs); else the caller owes it."""
+        cfg, P = self.cfg, self.P
+        H, L, BT = cfg['H'], cfg['L'], self.B * cfg['T']
+        if self.fuse_latent:
+            ops.latent_head_bwd(BT, H, L, self.hs_enc, P.p('Zargs/kernel'), self.zargs, eps_Z, dZ, L,
+                                self.kl_weight / BT, self.dhs, P.g('Zargs/kernel'), P.g('Zargs/bias'), self.ws, defer=defer)
+            pass_.head_grad_done = True
+        else:
+            ops.gauss_bwd(BT, L, self.zargs, eps_Z, dZ, L, self.kl_weight / BT, self.dzargs)
+            ops.gemm(self.dzargs, P.p('Zargs/kernel'), self.dhs, BT, H, 2 * L, tb=True, ws=self.ws)
+
+    def _forward_mx(self, pass_, X, eps_W, eps_Z, w_true, nll, target):
         """Forward for large batches: label path, encoder LSTM, latent head, decoder LSTM, output head; the LSTMs' input
         products (frame rows gathered from LDS, z_t . K_z as one more MFMA k-step) run inside csrc/lstm_mx.hip."""
         cfg, P, B = self.cfg, self.P, self.B
         D, H, L, T = cfg['D'], cfg['H'], cfg['L'], cfg['T']
         BT, off = B * T, self.off
-        f8 = self._f8
+        f8 = pass_.f8
         if f8 is not None:       # the frames as bytes: the batch the staging launch copied out of the frame store
             X = f8[0]
-        self._label_forward(X, eps_W, w_true)
+        self._label_forward(pass_, X, eps_W, w_true)
         ops.lstm_mx_fwd(B, T, X, D, D, P.p('encoder_h/kernel'), None, 0, 0, None, self.wk_enc,
                         P.p('encoder_h/recurrent_kernel'), self.hs_enc, self.gates_enc, self.cs_enc, gate_act=self.gate_act)
-        if self.fuse_latent:
-            nz = getattr(self, '_noise', None)          # (set by forward(noise=...) when folds_noise(): eps_Z is drawn in the launch)
-            ops.latent_head_fwd(BT, H, L, self.hs_enc, P.p('Zargs/kernel'), P.p('Zargs/bias'), eps_Z, self.zargs, self.Z,
-                                self.xz_ld, self.rowkl, noise=nz[1] if nz else None)
-        else:
-            ops.gemm(self.hs_enc, P.p('Zargs/kernel'), self.zargs, BT, 2 * L, H, bias=P.p('Zargs/bias'), ws=self.ws)
-            ops.gauss_fwd(BT, L, self.zargs, eps_Z, self.Z, self.xz_ld, self.rowkl)
+        self._latent_fwd(pass_, eps_Z)
         hist, hist_ld = (f8[1], D) if (f8 is not None and off) else (self.XZ if off else None, self.xz_ld)
         ops.lstm_mx_fwd(B, T, hist, hist_ld, off, P.p('decoder_h/kernel') if off else None,
                         self.Z, self.xz_ld, L, P.rows(P.params, 'decoder_h/kernel', off), self.wk_dec,
                         P.p('decoder_h/recurrent_kernel'), self.hs_dec, self.gates_dec, self.cs_dec, gate_act=self.gate_act)
-        self._output_head(X if f8 is not None else target, nll)
-
-    def _dense_hw_fwd_now(self):
-        cfg = self.cfg
-        return self.dense_hw_fwd and self.frames_exact_bf16 and \
-            ops.dense_window_fwd_bf16_supported(self.B, cfg['T'] * cfg['D'], cfg['D'], cfg['T'] * cfg['D'], cfg['D'])
+        self._output_head(pass_, X if f8 is not None else target, nll)
 
     def can_stage_in_label(self):
         """Can the label forward launch assemble the step's mini-batch itself (ops.label_stage; TrainStep decides per bound
         batch source)?  The fused pair path with the note-walking label kernel: its workgroup per batch row reads the row's
         byte frames for its scan anyway."""
-        return self.fuse_pair and self.sparse_inputs and self.cfg['D'] % 2 == 0 and not self.fuse_notes and \
-            not (self.dense_hw_fwd and ops.dense_window_fwd_bf16_supported(self.B, self.cfg['T'] * self.cfg['D'], self.cfg['D'],
-                                                                         self.cfg['T'] * self.cfg['D'], self.cfg['D']))
+        return self.fuse_pair and self.label_walks_notes and not self.fuse_notes and \
+            not (self.dense_hw_fwd and self.dense_window_ok)
 
-    def _label_forward(self, X, eps_W, w_true, pack=None, stage=None, proj=None):
+    def _label_forward(self, pass_, X, eps_W, w_true, pack=None, stage=None, proj=None):
         """Label path (:174-191): hW Dense layer over the flattened window, Wargs head, logistic-normal sample, label
         losses and both per-row LSTM biases (W.K_w + b).  One launch when the window is handled sparsely."""
         cfg, P, B = self.cfg, self.P, self.B
@@ -631,10 +687,10 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                 P.rows(P.params, 'encoder_h/kernel', D), P.p('encoder_h/bias'),
                 P.rows(P.params, 'decoder_h/kernel', off + L), P.p('decoder_h/bias'),
                 self.wargs, self.W, self.rowloss, self.wk_enc, self.wk_dec)
-        if self.sparse_inputs and D % 2 == 0:
-            nz = getattr(self, '_noise', None)
+        if self.label_walks_notes:
+            nz = pass_.noise
             parts = None
-            if stage is None and self._dense_hw_fwd_now():
+            if stage is None and self.dense_hw_fwd and self.frames_exact_bf16 and self.dense_window_ok:
                 # byte-valued frames: the product dense on the bf16 matrix cores (split-K partial sums, summed by the label
                 # launch) instead of the note-walking gather
                 if self.ws_hw is None:
@@ -646,11 +702,10 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
             ops.gemm(X, P.p('hW/kernel'), self.hW, B, D, T * D, bias=P.p('hW/bias'), act=ACT_RELU, ws=self.ws)
             ops.vrnn_label_fwd(B, D, Cn, G4, self.hW, *tail)
 
-    def _output_head(self, X, nll):
+    def _output_head(self, pass_, X, nll):
         """X: the frames the output is scored against"""
         cfg, P = self.cfg, self.P
         D, H, BT = cfg['D'], cfg['H'], self.B * cfg['T']
-        self._head_done = False
         if nll is not None:
             scale, need_grads = nll
             if need_grads and self.fuse_head:
@@ -658,17 +713,17 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                 # the weight-gradient slabs are summed with the other pending reductions in grads_tail()
                 ops.out_head_train(BT, H, D, self.hs_dec, P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), X, scale,
                                    self.rownll, self.dhs, P.g('X_decoded_mean/kernel'), P.g('X_decoded_mean/bias'),
-                                   self.ws, logits=self.logits if self.keep_logits else None, defer=self._rq())
-                self._head_done = True
+                                   self.ws, logits=self.logits if pass_.keep_logits else None, defer=self._rq())
+                pass_.head_done = True
             else:
                 ops.gemm_bce(self.hs_dec, P.p('X_decoded_mean/kernel'), P.p('X_decoded_mean/bias'), X, scale, self.logits,
                              self.dlogits if need_grads else None, self.rownll, BT, D, H)
-            self._nll_done = True
+            pass_.nll_done = True
         else:
             ops.gemm(self.hs_dec, P.p('X_decoded_mean/kernel'), self.logits, BT, D, H, bias=P.p('X_decoded_mean/bias'),
                      ws=self.ws)
 
-    def _forward_pair(self, X, eps_W, eps_Z, w_true, nll=None, target=None):
+    def _forward_pair(self, pass_, X, eps_W, eps_Z, w_true, nll=None, target=None):
         """Forward with both LSTMs, the latent head and the z projection in one persistent kernel."""
         cfg, P, B = self.cfg, self.P, self.B
         D, H, L, T, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['T'], cfg['C']
@@ -678,14 +733,12 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         # by-product of the label kernel's launch where that runs, else a launch of its own
         pack = (L, P.p('encoder_h/recurrent_kernel'), P.p('decoder_h/recurrent_kernel'),
                 P.rows(P.params, 'decoder_h/kernel', off), P.p('Zargs/kernel'), self.pair_pack)
-        pack_in_label = self.sparse_inputs and D % 2 == 0
-        if not pack_in_label:
+        if not self.label_walks_notes:
             ops.lstm_pair_pack(*pack)
-        # TrainStep handed over the mini-batch assembly (stage_spec: ops.label_stage): the label launch goes FIRST and fills X,
+        # TrainStep handed over the mini-batch assembly (stage: ops.label_stage): the label launch goes FIRST and fills X,
         # the history frames and the labels for everything behind it
-        stage = self.stage_spec if pack_in_label else None
-        self.stage_spec = None
-        f8 = self._f8
+        stage = pass_.stage if self.label_walks_notes else None
+        f8 = pass_.f8
         if f8 is not None and stage is None:
             raise ValueError("frames8 on the pair path: the byte batch is what the label launch's own stage leaves (ops.label_stage)")
         # the frame projections inside the label launch (csrc/label_head.hip: vrnn_front_kernel), from the byte stores the stage names
@@ -695,7 +748,7 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
             proj = (T, G4, P.p('encoder_h/kernel'), self.gates_enc, P.p('decoder_h/kernel') if off else None,
                     self.gates_dec if off else None)
         if stage is not None:
-            self._label_forward(X, eps_W, w_true, pack=pack, stage=stage, proj=proj)
+            self._label_forward(pass_, X, eps_W, w_true, pack=pack, stage=stage, proj=proj)
         notes = None
         if proj is not None:
             pass
@@ -714,12 +767,12 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
             if off:        # history frames only: z_t . K_z is added inside the sequence kernel
                 g(self.XZ, P.p('decoder_h/kernel'), self.gates_dec, BT, G4, off, lda=self.xz_ld, ws=ws)
         if stage is None:
-            self._label_forward(X, eps_W, w_true, pack=pack if pack_in_label else None)
-        nz = getattr(self, '_noise', None)
+            self._label_forward(pass_, X, eps_W, w_true, pack=pack if self.label_walks_notes else None)
+        nz = pass_.noise
         ops.lstm_pair_fwd(B, T, L, self.gates_enc, self.wk_enc, self.gates_dec, off > 0, self.wk_dec, self.pair_pack,
                           P.p('Zargs/bias'), eps_Z, self.hs_enc, self.cs_enc, self.hs_dec, self.cs_dec, self.zargs, self.Z,
                           self.xz_ld, self.klterm, gate_act=self.gate_act, noise=nz[1] if nz else None, notes=notes)
-        self._output_head(f8[0] if f8 is not None else (X if target is None else target), nll)
+        self._output_head(pass_, f8[0] if f8 is not None else (X if target is None else target), nll)
 
     def xp_view(self):
         """[B,T,D] strided view of the history columns of the [Xp | Z] buffer (stage batches straight into it)."""
@@ -732,12 +785,13 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                  bias=P.p('X_decoded_mean/bias'), act=ACT_SIGMOID, ws=self.ws)
         return self.dlogits
 
-    def _wgrad_args(self, name, X_in, x_ld, x_rows, hs, dz, x8=None):
-        """The argument tuple of ops.lstm_wgrad (up to dKz) for one LSTM's kernel gradients on the bf16 matrix cores
-        (csrc/wgrad_bf16.hip: x rows, h rows and z rows at once), or None where that kernel does not apply.
-        x8: the frame rows as a uint8 [B*T, nx] batch instead of the first nx columns of X_in (the z rows stay in X_in)."""
+    def _wgrad_args(self, w):
+        """The argument tuple of ops.lstm_wgrad (up to dKz) for one LSTM's kernel gradients (a _Wgrad) on the bf16 matrix
+        cores (csrc/wgrad_bf16.hip: x rows, h rows and z rows at once), or None where that kernel does not apply.
+        w.x8: the frame rows as a uint8 [B*T, nx] batch instead of the first nx columns of w.X (the z rows stay in w.X)."""
         cfg, P = self.cfg, self.P
         H, T, L = cfg['H'], cfg['T'], cfg['L']
+        name, X_in, x_ld, x_rows, hs, dz, x8 = w
         nz = L if name == 'decoder_h' else 0          # the decoder's per-step inputs are [x_{t-1} | z_t]
         nx = x_rows - nz                              # 0: a decoder without history frames
         if not (self.bf16_wgrad and nx > 0 and ops.lstm_wgrad_supported(4 * H, nx, H, nz, self.frames_exact_bf16)):
@@ -749,8 +803,8 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                 dz, P.g(name + '/kernel'), P.g(name + '/recurrent_kernel'),
                 P.rows(P.grads, name + '/kernel', nx) if nz else None)
 
-    def _lstm_wgrads(self, name, X_in, x_ld, x_rows, hs, dz, dzsum, w_row, ws, products=True, x8=None):
-        """Every weight gradient of one LSTM in two grouped launches.
+    def _lstm_wgrads(self, w, dzsum, w_row, ws, products=True):
+        """Every weight gradient of one LSTM (w: its _Wgrad) in two grouped launches.
         Over dz [B*T,4H] (K = B*T): kernel rows of the per-step inputs (x_t, or [x_{t-1} | z_t] for the
         decoder) and the recurrent kernel (h_{t-1}: shift 1, zero at t == 0); products=False: already formed
         (grads_tail: both LSTMs in one launch).
@@ -760,25 +814,18 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         G4 = 4 * H
         rq = self._rq()
         if products:
-            args = self._wgrad_args(name, X_in, x_ld, x_rows, hs, dz, x8)
-            if args is None and x8 is not None:
-                raise RuntimeError("frames8: the %s kernel gradients have no byte-reading kernel at these shapes" % name)
+            args = self._wgrad_args(w)
+            if args is None and w.x8 is not None:
+                raise RuntimeError("frames8: the %s kernel gradients have no byte-reading kernel at these shapes" % w.name)
             if args is not None:
                 ops.lstm_wgrad(*args, ws, defer=rq, split_scale=2 if self.fine_grid else 1)
-            else:
-                self._lstm_wgrads_f32(name, X_in, x_ld, x_rows, hs, dz, ws, rq)
-        if not (Cn + 1 <= 16 and B <= 4096):      # else: both LSTMs' label rows + biases in one launch (grads_tail)
-            ops.gemm_grouped_tn([dict(A=self.W, lda=Cn, M=Cn, C=P.rows(P.grads, name + '/kernel', w_row)),
-                                 dict(A=None, M=1, C=P.g(name + '/bias'), ones=1)], G4, B, dzsum, ws, defer=rq)
-
-    def _lstm_wgrads_f32(self, name, X_in, x_ld, x_rows, hs, dz, ws, rq):
-        """The same products on the f32 MFMA (grouped GEMM over dz): any shape."""
-        cfg, P = self.cfg, self.P
-        H, T = cfg['H'], cfg['T']
-        BT, G4 = self.B * T, 4 * H
-        ops.gemm_grouped_tn([dict(A=X_in, lda=x_ld, M=x_rows, C=P.g(name + '/kernel')),
-                             dict(A=hs, lda=H, M=H, C=P.g(name + '/recurrent_kernel'), shift=1, zero_period=T)],
-                            G4, BT, dz, ws, defer=rq, split_scale=2 if self.fine_grid else 1)
+            else:       # the same products on the f32 MFMA (grouped GEMM over dz): any shape
+                ops.gemm_grouped_tn([dict(A=w.X, lda=w.ldx, M=w.rows, C=P.g(w.name + '/kernel')),
+                                     dict(A=w.hs, lda=H, M=H, C=P.g(w.name + '/recurrent_kernel'), shift=1, zero_period=cfg['T'])],
+                                    G4, B * cfg['T'], w.dz, ws, defer=rq, split_scale=2 if self.fine_grid else 1)
+        if not self.skinny_label_rows:      # else: both LSTMs' label rows + biases in one launch (grads_tail)
+            ops.gemm_grouped_tn([dict(A=self.W, lda=Cn, M=Cn, C=P.rows(P.grads, w.name + '/kernel', w_row)),
+                                 dict(A=None, M=1, C=P.g(w.name + '/bias'), ones=1)], G4, B, dzsum, ws, defer=rq)
 
     def _dense_wgrad(self, name, A, lda, rows, N, K, Bm, ws, rq):
         """Kernel and bias gradient of a Dense layer in one pass over Bm = dL/d(output) [K,N].  When the bias follows the
@@ -797,12 +844,12 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
 
     def tail_range(self):
         """(offset, numel) of the hW-kernel bucket inside the flat gradient buffer: complete after
-        loss_and_grads(do_tail=False), i.e. before grads_tail() has produced the rest (unless the caller set
-        halves_adjacent for the pass: then it may be complete only after grads_tail())."""
+        loss_and_grads(do_tail=False), i.e. before grads_tail() has produced the rest (unless the caller passed
+        adjacent=True: then it may be complete only after grads_tail())."""
         D, T = self.cfg['D'], self.cfg['T']
         return self.P.offsets['hW/kernel'], T * D * D
 
-    def _bptt_separate(self, eps_Z, ws):
+    def _bptt_separate(self, pass_, eps_Z, ws):
         """Backward through both LSTMs and the latent head as separate launches (any latent_dim); leaves dz in
         gates_*, dzsum_*, dzargs."""
         cfg, P, B = self.cfg, self.P, self.B
@@ -820,42 +867,38 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
             ops.lstm_seq_bwd(B, T, P.p('decoder_h/recurrent_kernel'), self.dhs, self.cs_dec, self.gates_dec,
                              self.dzsum_dec, gate_act=self.gate_act, H=H)
             g(self.gates_dec, P.rows(P.params, 'decoder_h/kernel', off), self.dZ, BT, L, G4, tb=True, ws=ws)
-        if self.fuse_latent:       # dzargs, dh_enc and the head's own kernel / bias gradient in one launch; dzargs stays on chip
-            ops.latent_head_bwd(BT, H, L, self.hs_enc, P.p('Zargs/kernel'), self.zargs, eps_Z, self.dZ, L,
-                                self.kl_weight / BT, self.dhs, P.g('Zargs/kernel'), P.g('Zargs/bias'), ws, defer=self._rq())
-            self._head_grad_done = True
-        else:
-            ops.gauss_bwd(BT, L, self.zargs, eps_Z, self.dZ, L, self.kl_weight / BT, self.dzargs)
-            g(self.dzargs, P.p('Zargs/kernel'), self.dhs, BT, H, 2 * L, tb=True, ws=ws)
+        self._latent_bwd(pass_, eps_Z, self.dZ, self._rq())
         if self.use_mx:
             ops.lstm_mx_bwd(B, T, P.p('encoder_h/recurrent_kernel'), self.dhs, self.cs_enc, self.gates_enc, self.dzsum_enc)
         else:
             ops.lstm_seq_bwd(B, T, P.p('encoder_h/recurrent_kernel'), self.dhs, self.cs_enc, self.gates_enc,
                              self.dzsum_enc, gate_act=self.gate_act, H=H)
 
-    def loss_and_grads(self, X, Xp, w_true, eps_W, eps_Z, need_grads=True, do_tail=True, target=None, noise=None, frames8=None):
+    def loss_and_grads(self, X, Xp, w_true, eps_W, eps_Z, need_grads=True, do_tail=True, target=None, noise=None, frames8=None,
+                       stage=None, adjacent=None, keep_logits=None):
         """target: the frames the decoder output is scored against (default X; the next frames under --predict_next).
-        noise, frames8: see forward() (with frames8 and do_tail=False, hand the same frames8 to grads_tail())."""
+        noise, frames8: see forward() (with frames8 and do_tail=False, hand the same frames8 to grads_tail()).
+        stage (ops.label_stage, where can_stage_in_label()): the label launch assembles the mini-batch itself.
+        adjacent (with do_tail=False): nothing reads the gradients before grads_tail(), see tail_range().
+        keep_logits: store the logits of this pass (default: the engine's switch)."""
         cfg, P, B = self.cfg, self.P, self.B
         D, H, L, T, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['T'], cfg['C']
         C1, BT, G4 = Cn - 1, B * T, 4 * H
         inv_bt, inv_b = 1.0 / BT, 1.0 / B
         g, ws, off = ops.gemm, self.ws, self.off
-        adjacent, self.halves_adjacent = bool(do_tail or self.halves_adjacent), False
-        self._hw_outer = None
-        self._train_pass = bool(need_grads)      # LSTM(dropout=p) applies in training passes only
-        try:
-            self.forward(X, Xp, eps_W, eps_Z, w_true, nll=(inv_bt, need_grads), target=target, noise=noise, frames8=frames8)
-        finally:
-            self._train_pass = False
-        if not self._nll_done:
+        self._pending = None
+        pass_ = _Pass(f8=frames8, stage=stage, adjacent=bool(do_tail or adjacent), train=bool(need_grads),
+                      keep_logits=self.keep_logits if keep_logits is None else bool(keep_logits))
+        self.forward(X, Xp, eps_W, eps_Z, w_true, nll=(inv_bt, need_grads), target=target, noise=noise, frames8=frames8,
+                     pass_=pass_)
+        if not pass_.nll_done:
             ops.bernoulli_nll(BT, D, self.logits, X if target is None else target, D, inv_bt, self.rownll,
                               self.dlogits if need_grads else None)
         kl = (self.klterm, BT * L, 1) if self.fuse_pair else (self.rowkl, BT, 1)
         terms = [(self.rownll, BT, 1), kl, (self.rowloss, B, 3), (self.rowloss[:, 1:], B, 3), (self.rowloss[:, 2:], B, 3)]
         # the loss means ride in the reduce launch that ends the backward pass (grads_tail) when there is one
-        self._loss_terms = terms if (need_grads and self._rq() is not None) else None
-        if self._loss_terms is None:
+        pass_.loss_terms = terms if (need_grads and self._rq() is not None) else None
+        if pass_.loss_terms is None:
             ops.loss_sums(terms, self.scal)
         if not need_grads:
             self._join()
@@ -863,10 +906,11 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         # Backward, early part: everything on the critical chain dlogits -> BPTT -> label path -> hW kernel gradient.
         # The hW kernel (T*D*D floats) is 87 % of the gradient bytes: with N > 1 GPUs its all-reduce bucket starts
         # here and runs under the weight-gradient products of grads_tail().
-        if not self._head_done:
+        if not pass_.head_done:
             g(self.dlogits, P.p('X_decoded_mean/kernel'), self.dhs, BT, H, D, tb=True, ws=ws)
-        if self.dropout:
-            self._backward_dropout(X, w_true, eps_W, eps_Z)
+        if self.dropout:       # every gradient at once: grads_tail() has nothing left to do
+            self._backward_dropout(pass_, X, w_true, eps_W, eps_Z)
+            self._pending = None if do_tail else pass_
             return
         if self.fuse_pair:
             # decoder BPTT, dZ, the latent head's backward, dh_enc and encoder BPTT: one persistent launch
@@ -885,9 +929,9 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                               self.zargs, eps_Z, self.dzargs, gate_act=self.gate_act,
                               head_grad=(self.hs_enc, P.g('Zargs/kernel'), P.g('Zargs/bias')), ws=ws, defer=self._rq(),
                               label=label)
-            self._head_grad_done = True
+            pass_.head_grad_done = True
         else:
-            self._bptt_separate(eps_Z, ws)
+            self._bptt_separate(pass_, eps_Z, ws)
         # label head: dW from both LSTMs, label backward, dWargs and dhW in one launch
         if not (self.fuse_pair and self.label_in_pair):
             ops.vrnn_label_bwd(B, D, Cn, G4, self.dzsum_enc, self.dzsum_dec, P.rows(P.params, 'encoder_h/kernel', D),
@@ -903,10 +947,10 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                                              ops.dense_outer_bf16_supported(B, T * D, D, T * D, D)) else ops.sparse_outer
             frames = X if frames8 is None else frames8[0]
             gdot = (self.hW, D, P.p('hW/bias'), self.gdot)
-            if (outer is ops.dense_outer_bf16 and self.tail_launch and adjacent and self._rq() is not None
+            if (outer is ops.dense_outer_bf16 and self.tail_launch and pass_.adjacent and self._rq() is not None
                     and ops.reduce_outer_supported(B, T * D, D, T * D, D)):
                 # nothing reads the product before the pass's last launch: it runs there, beside the reduction (grads_tail)
-                self._hw_outer = dict(Bn=B, nx=T * D, N=D, X=frames, ldx=T * D, G=self.dhW, ldg=D, out=P.g('hW/kernel'),
+                pass_.hw_outer = dict(Bn=B, nx=T * D, N=D, X=frames, ldx=T * D, G=self.dhW, ldg=D, out=P.g('hW/kernel'),
                                       colsum=P.g('hW/bias'), gdot=gdot)
             else:
                 outer(B, T * D, D, frames, T * D, self.dhW, D, P.g('hW/kernel'), colsum=P.g('hW/bias'), gdot=gdot)
@@ -914,6 +958,7 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         else:
             g(X, self.dhW, P.g('hW/kernel'), T * D, D, B, ta=True, ws=ws)
             ops.colsum(self.dhW, B, D, P.g('hW/bias'), ws)
+        self._pending = pass_
         if do_tail:
             self.grads_tail(X, frames8=frames8)
 
@@ -924,32 +969,34 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
         D, H, L, T, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['T'], cfg['C']
         C1, BT, off = Cn - 1, B * T, self.off
         ws, rq = self.ws, self._rq()
+        pass_, self._pending = self._pending, None
+        if pass_ is None:
+            raise RuntimeError("grads_tail() without a pending pass: it ends one loss_and_grads(need_grads=True, do_tail=False)")
         if self.dropout:           # _backward_dropout has formed every gradient
             return
         # output head: kernel and bias gradient in one pass over dlogits (bias = an implicit row of ones)
-        if not self._head_done:
+        if not pass_.head_done:
             self._dense_wgrad('X_decoded_mean', self.hs_dec, H, H, D, BT, self.dlogits, ws, rq)
         # both LSTMs' kernel gradients in ONE launch where they take the same form of the kernel (configuration 3: 256
         # workgroups of 16 stages instead of twice 256 of 8; half as many slabs to reduce)
-        dec = ('decoder_h', self.XZ, self.xz_ld, off + L, self.hs_dec, self.gates_dec)
-        enc = ('encoder_h', X, D, D, self.hs_enc, self.gates_enc)
-        if frames8 is not None:      # the frame rows of both products read the byte batch (the z rows stay in [Xp | Z])
-            dec, enc = dec + (frames8[1],), enc + (frames8[0],)
+        # (frames8: the frame rows of both products read the byte batch, the z rows stay in [Xp | Z])
+        x8, xp8 = (None, None) if frames8 is None else frames8
+        dec = _Wgrad('decoder_h', self.XZ, self.xz_ld, off + L, self.hs_dec, self.gates_dec, xp8)
+        enc = _Wgrad('encoder_h', X, D, D, self.hs_enc, self.gates_enc, x8)
         paired = False
         if self.wgrad_pair:
-            pd, pe = self._wgrad_args(*dec), self._wgrad_args(*enc)
+            pd, pe = self._wgrad_args(dec), self._wgrad_args(enc)
             if pd is not None and pe is not None and ops.lstm_wgrad_pair_supported(pd, pe):
                 if rq is None and self.ws_b is None:
                     self.ws_b = ops.Workspace(self.device)
                 ops.lstm_wgrad_pair(pd, pe, (ws, self.ws_b), defer=rq, split_scale=2 if self.fine_grid else 1)
                 paired = True
-        self._lstm_wgrads(*dec[:6], self.dzsum_dec, off + L, ws, products=not paired, x8=dec[6] if len(dec) > 6 else None)
-        if not getattr(self, '_head_grad_done', False):
+        self._lstm_wgrads(dec, self.dzsum_dec, off + L, ws, products=not paired)
+        if not pass_.head_grad_done:
             self._dense_wgrad('Zargs', self.hs_enc, H, H, 2 * L, BT, self.dzargs, ws, rq)
-        self._head_grad_done = False
-        self._lstm_wgrads(*enc[:6], self.dzsum_enc, D, ws, products=not paired, x8=enc[6] if len(enc) > 6 else None)
+        self._lstm_wgrads(enc, self.dzsum_enc, D, ws, products=not paired)
         skinny = None
-        if Cn + 1 <= 16 and B <= 4096:
+        if self.skinny_label_rows:
             # label rows + bias of both LSTMs' input-kernel gradients (K = batch rows of sum_t dz)
             if rq is not None:      # ... as rider blocks of the reduction launch
                 skinny = [dict(A=self.W, lda=Cn, rows=Cn, B=dzs, ldb=4 * H, N=4 * H, K=B,
@@ -962,6 +1009,4 @@ class VrnnEngine(VrnnDropout, VrnnGenerate, _EngineBase):
                                            self.dzsum_dec, 4 * H, B)
         # (the Wargs layer's gradient: per-row slabs of the label backward kernel, already among the pending reductions)
         if rq is not None:
-            rq.flush(means=getattr(self, '_loss_terms', None), out=self.scal, skinny=skinny, outer=self._hw_outer)
-            self._loss_terms = None
-            self._hw_outer = None
+            rq.flush(means=pass_.loss_terms, out=self.scal, skinny=skinny, outer=pass_.hw_outer)

@@ -22,12 +22,12 @@ class VrnnDropout:
         H = self.cfg['H']
         return t[gi * H:] if t.dim() == 1 else t[:, gi * H:]
 
-    def _forward_dropout(self, X, eps_W, eps_Z, w_true, nll, target):
+    def _forward_dropout(self, pass_, X, eps_W, eps_Z, w_true, nll, target):
         cfg, P, B = self.cfg, self.P, self.B
         D, H, L, T, Cn, off = cfg['D'], cfg['H'], cfg['L'], cfg['T'], cfg['C'], self.off
         BT, G4, rate = B * T, 4 * H, self.dropout
         g, ws, gc = ops.gemm, self.ws, self._gate_cols
-        self._label_forward(X, eps_W, w_true)              # hW, Wargs, W, the label losses (its unmasked row biases are replaced)
+        self._label_forward(pass_, X, eps_W, w_true)             # hW, Wargs, W, the label losses (its unmasked row biases are replaced)
         in_e, in_d = D + Cn, off + L + Cn
         ue, ud = self.u_enc.view(B, 4 * in_e), self.u_dec.view(B, 4 * in_d)
         X2 = X.reshape(BT, D)
@@ -39,12 +39,7 @@ class VrnnDropout:
               bias=gc(P.p('encoder_h/bias'), gi), ws=ws)
         ops.lstm_seq_fwd(B, T, self.gates_enc, self.wk_enc, P.p('encoder_h/recurrent_kernel'), self.hs_enc, self.cs_enc,
                          self.gates_enc, gate_act=self.gate_act, H=H)
-        if self.fuse_latent:
-            ops.latent_head_fwd(BT, H, L, self.hs_enc, P.p('Zargs/kernel'), P.p('Zargs/bias'), eps_Z, self.zargs, self.Z,
-                                self.xz_ld, self.rowkl)
-        else:
-            g(self.hs_enc, P.p('Zargs/kernel'), self.zargs, BT, 2 * L, H, bias=P.p('Zargs/bias'), ws=ws)
-            ops.gauss_fwd(BT, L, self.zargs, eps_Z, self.Z, self.xz_ld, self.rowkl)
+        self._latent_fwd(pass_, eps_Z)
         for gi in range(4):
             ops.dropout_rows(BT, T, off + L, self.XZ, self.xz_ld, ud[:, gi * in_d:], 4 * in_d, rate, self.xm_d[gi], self.xz_ld)
             g(self.xm_d[gi], gc(P.p('decoder_h/kernel'), gi), gc(self.gates_dec, gi), BT, H, off + L, lda=self.xz_ld, ldb=G4,
@@ -54,9 +49,9 @@ class VrnnDropout:
               ldc=G4, bias=gc(P.p('decoder_h/bias'), gi), ws=ws)
         ops.lstm_seq_fwd(B, T, self.gates_dec, self.wk_dec, P.p('decoder_h/recurrent_kernel'), self.hs_dec, self.cs_dec,
                          self.gates_dec, gate_act=self.gate_act, H=H)
-        self._output_head(target, nll)
+        self._output_head(pass_, target, nll)
 
-    def _backward_dropout(self, X, w_true, eps_W, eps_Z):
+    def _backward_dropout(self, pass_, X, w_true, eps_W, eps_Z):
         """Everything behind dL/dh_dec (self.dhs) of a training pass with input dropout: both BPTTs, dZ and dW through the
         gates' masks, the latent head, the label path from an explicit dL/dW, every weight gradient.  Plain launches (no
         deferred reductions): this chain is the rarely used one."""
@@ -78,12 +73,8 @@ class VrnnDropout:
               ldb=G4, ws=ws)
             ops.dropout_rows(B, 1, Cn, self.dwg, Cn, ud[:, gi * in_d + off + L:], 4 * in_d, rate, self.dW, Cn, beta=float(gi > 0))
         # latent head backward -> dL/dh_enc
-        if self.fuse_latent:
-            ops.latent_head_bwd(BT, H, L, self.hs_enc, P.p('Zargs/kernel'), self.zargs, eps_Z, self.dZ, L,
-                                self.kl_weight / BT, self.dhs, P.g('Zargs/kernel'), P.g('Zargs/bias'), ws, defer=None)
-        else:
-            ops.gauss_bwd(BT, L, self.zargs, eps_Z, self.dZ, L, self.kl_weight / BT, self.dzargs)
-            g(self.dzargs, P.p('Zargs/kernel'), self.dhs, BT, H, 2 * L, tb=True, ws=ws)
+        self._latent_bwd(pass_, eps_Z, self.dZ, defer=None)
+        if not pass_.head_grad_done:
             self._dense_wgrad('Zargs', self.hs_enc, H, H, 2 * L, BT, self.dzargs, ws, None)
         ops.lstm_seq_bwd(B, T, P.p('encoder_h/recurrent_kernel'), self.dhs, self.cs_enc, self.gates_enc, self.dzsum_enc,
                          gate_act=self.gate_act, H=H)
@@ -110,9 +101,8 @@ class VrnnDropout:
                 g(wm[gi], gc(dzsum, gi), gc(P.rows(P.grads, name + '/kernel', nin), gi), Cn, H, B, ta=True, ldb=G4, ldc=G4, ws=ws)
             ops.gemm_grouped_tn([dict(A=hs, lda=H, M=H, C=P.g(name + '/recurrent_kernel'), shift=1, zero_period=T)], G4, BT, dz, ws)
             ops.colsum(dzsum, B, G4, P.g(name + '/bias'), ws)
-        if not self._head_done:
+        if not pass_.head_done:
             self._dense_wgrad('X_decoded_mean', self.hs_dec, H, H, D, BT, self.dlogits, ws, None)
         rq = self._rq()
         if rq is not None:       # (the fused output head may have left its slabs pending; the loss means ride along)
-            rq.flush(means=getattr(self, '_loss_terms', None), out=self.scal, skinny=None)
-            self._loss_terms = None
+            rq.flush(means=pass_.loss_terms, out=self.scal, skinny=None)

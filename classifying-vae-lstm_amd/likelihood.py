@@ -45,16 +45,16 @@ def _iw_step(model):
 class _SharedEngineState:
     """What a forward pass writes into the engine that a training step may still read: saved on entry, put back on exit."""
 
-    FLAGS = ('frames_exact_bf16', 'notes_valid', 'stage_spec')
-    BUFFERS = ('scal', 'XZ', 'notes_enc', 'notes_dec')
+    FLAGS = ('frames_exact_bf16', 'notes_valid')
+    BUFFERS = ('scal', 'XZ', 'notes_enc', 'notes_dec')      # (cl_vae has no XZ; the note lists exist only with fuse_notes)
 
     def __init__(self, eng):
         self.eng = eng
 
     def __enter__(self):
         e = self.eng
-        self.flags = {f: getattr(e, f) for f in self.FLAGS if hasattr(e, f)}
-        self.bufs = {b: getattr(e, b).clone() for b in self.BUFFERS if getattr(e, b, None) is not None}
+        self.flags = {f: getattr(e, f) for f in self.FLAGS}
+        self.bufs = {b: t.clone() for b, t in ((b, getattr(e, b, None)) for b in self.BUFFERS) if t is not None}
         return self
 
     def __exit__(self, *exc):

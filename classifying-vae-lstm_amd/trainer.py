@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .engine import NoiseSpec
 from .parallel import GradAllReduce, eps_first_index, meta_device
 
 
@@ -56,13 +57,13 @@ class TrainStep:
         self.b2 = 0.9 if optimizer == 'rmsprop' else 0.999                       # rmsprop: rho
         self.lr = lr
         self.use_graph = use_graph
-        # nothing reads the logits of a replayed training step (VrnnEngine.keep_logits): the store is switched off AROUND this
-        # step's own passes (_main), never on the shared engine for good -- a direct loss_and_grads() call, a tool or a second
-        # TrainStep(use_graph=False) on the same engine keep finding fresh logits
-        self._drop_logits = bool(use_graph and hasattr(engine, 'keep_logits') and 'keep_logits' not in engine.cfg)
-        self.fast_adam = bool(fast_adam) and os.environ.get('CLV_FAST_ADAM', '1') != '0'      # see _update()
         cfg, B, d = engine.cfg, engine.B, engine.device
         self.is_vrnn = 'T' in cfg
+        # nothing reads the logits of a replayed training step (VrnnEngine.keep_logits): the store is switched off FOR this
+        # step's own passes (_main: keep_logits=False), never on the shared engine -- a direct loss_and_grads() call, a
+        # tool or a second TrainStep(use_graph=False) on the same engine keep finding fresh logits
+        self._drop_logits = bool(use_graph and self.is_vrnn and 'keep_logits' not in cfg)
+        self.fast_adam = bool(fast_adam) and os.environ.get('CLV_FAST_ADAM', '1') != '0'      # see _update()
         T = cfg['T'] if self.is_vrnn else 1
         D, L, C1 = cfg['D'], cfg['L'], cfg['C'] - 1
         f = dict(dtype=torch.float32, device=d)
@@ -84,14 +85,14 @@ class TrainStep:
         self.w_true = torch.zeros(B, cfg['C'], **f)
         self.eps_w = torch.zeros(B, C1, **f)
         self.eps_z = torch.zeros(B * T, L, **f)
-        tail = engine.tail_range() if self.is_vrnn else (0, 0)
+        tail = engine.tail_range()
         # CLV_FORCE_DP_GRAPHS=1: take the multi-GPU schedule (main graph, tail graph, update graph around the two
         # gradient buckets) on a single GPU too, with the collectives as no-ops -- lets one box test that path
         force = os.environ.get('CLV_FORCE_DP_GRAPHS') == '1'
         # the scratch in front of the gradients (cl_vrnn: the optimizer's sum g.V of the hW kernel) travels with the tail bucket
         P = engine.P
         self.pre_in_tail = bool(self.is_vrnn and tail[1] and tail[0] == 0 and P.grads_pre.numel() > 0
-                                and getattr(engine, 'gdot', None) is not None
+                                and engine.gdot is not None
                                 and engine.gdot.data_ptr() == P.grads_pre.data_ptr())
         # CLV_DP_REAL_COLLECTIVES=1 (with the forced schedule, inside a one-rank RCCL group): the collectives are issued
         # for real -- the only way a one-GPU box can run RCCL inside this schedule, and try to capture it
@@ -121,29 +122,31 @@ class TrainStep:
         self.capture_collectives = os.environ.get('CLV_CAPTURE_COLLECTIVES', '1') != '0'
         self.capture_note = None
         self._graphs = None
+        self._graph_fast = False    # the captured optimizer is the short form (valid while FlatParams.norms_valid)
+        self._main_leaves_gdot = False
         self._warm = False
         self._bound = None          # bind_batches(): the mini-batch assembly as the first node of the captured step
         self.loss_acc = None        # a [>= 5] float tensor: every step adds its five loss means to it (inside the graph)
 
     # -- pieces -----------------------------------------------------------
     def noise_spec(self, stream_offset=0, row0=None):
-        """(seed, stream_w, stream_z, first_w, first_z, step, step_dev) of this rank's eps_w / eps_z: the Philox streams
+        """The NoiseSpec of this rank's eps_w / eps_z: the Philox streams
         (2*stream_offset, 2*stream_offset+1) at its global rows (row0 = first global row of the batch held here; default
         rank * B), at step `iterations`."""
         eng, B = self.eng, self.eng.B
         C1, L = eng.cfg['C'] - 1, eng.cfg['L']
         T = eng.cfg['T'] if self.is_vrnn else 1
         row0 = self.rank * B if row0 is None else int(row0)      # global row of this rank's first sample
-        return (self.seed, 2 * stream_offset, 2 * stream_offset + 1, eps_first_index(row0, C1),
-                eps_first_index(row0, T * L), 0, eng.P.iterations)
+        return NoiseSpec(self.seed, 2 * stream_offset, 2 * stream_offset + 1, eps_first_index(row0, C1),
+                         eps_first_index(row0, T * L), 0, eng.P.iterations)
 
     def draw_noise(self, stream_offset=0, row0=None):
         """Fill eps_w / eps_z (noise_spec) with one launch."""
         eng, B = self.eng, self.eng.B
         T = eng.cfg['T'] if self.is_vrnn else 1
-        seed, sw, sz, fw, fz, step, it = self.noise_spec(stream_offset, row0)
-        ops.philox_normal2(self.eps_w, B * (eng.cfg['C'] - 1), sw, fw, self.eps_z, B * T * eng.cfg['L'], sz, fz, seed, step,
-                           step_dev=it)
+        n = self.noise_spec(stream_offset, row0)
+        ops.philox_normal2(self.eps_w, B * (eng.cfg['C'] - 1), n.stream_w, n.first_w, self.eps_z, B * T * eng.cfg['L'],
+                           n.stream_z, n.first_z, n.seed, n.step, step_dev=n.step_dev)
 
     def _folded(self):
         """cl_vae's fused step draws its own noise and advances `iterations` in the launches it already has (a step is
@@ -177,7 +180,7 @@ class TrainStep:
     def _bytes_batch(self, b):
         """(X8, Xp8) when the bound batches can stay uint8 for the whole step, else None (see __init__)."""
         eng = self.eng
-        if not (self.is_vrnn and b['target'] is None and getattr(eng, 'frames_u8_route', lambda: None)() == 'gather'):
+        if not (self.is_vrnn and b['target'] is None and eng.frames_u8_route() == 'gather'):
             return None
         need_hist = eng.off > 0
         if need_hist != (b['hist'] is not None):
@@ -186,10 +189,13 @@ class TrainStep:
             t = x.store if isinstance(x, DevWindows) else x
             if t.dtype != torch.uint8 or not t.is_contiguous():
                 return None
+        return self._byte_buffers(need_hist)
+
+    def _byte_buffers(self, need_hist):
+        """(X8, Xp8): the uint8 twins of X / Xp (Xp8 None without history frames), allocated at their first use"""
         if self.X8 is None:
-            shp = tuple(self.X.shape)
-            self.X8 = torch.zeros(*shp, dtype=torch.uint8, device=self.X.device)
-            self.Xp8 = torch.zeros(*shp, dtype=torch.uint8, device=self.X.device) if need_hist else None
+            self.X8 = torch.zeros_like(self.X, dtype=torch.uint8)
+            self.Xp8 = torch.zeros_like(self.X, dtype=torch.uint8) if need_hist else None
         return (self.X8, self.Xp8)
 
     def _stage_bound(self):
@@ -205,9 +211,7 @@ class TrainStep:
         launch of its own; else None.  Byte frames only, no separate target, no note lists; CLV_STAGE_IN_LABEL=0 keeps the
         gather launch."""
         b, eng = self._bound, self.eng
-        if os.environ.get('CLV_STAGE_IN_LABEL', '1') == '0' or b['target'] is not None:
-            return None
-        if not getattr(eng, 'can_stage_in_label', lambda: False)():
+        if os.environ.get('CLV_STAGE_IN_LABEL', '1') == '0' or b['target'] is not None or not eng.can_stage_in_label():
             return None
         if not self.is_vrnn and not (self._folded() and b['w'] is not None):
             return None
@@ -226,69 +230,48 @@ class TrainStep:
             return None
         if b['w'].dtype != torch.float32 or not b['w'].is_contiguous():
             return None
-        if hasattr(eng, 'frames_exact_bf16') and not eng.frames_exact_bf16:      # byte frames (what _segments() notes for the gather)
+        if not eng.frames_exact_bf16:      # byte frames (what _segments() notes for the gather)
             eng.frames_exact_bf16 = True
             self.recapture()
         hist_chunk, hist_ld = (D, self.xp_ld) if self.xp_ld else (row, row)
-        f8 = None
-        if self.is_vrnn and getattr(eng, 'frames_u8_route', lambda: None)() == 'label':
-            # the label launch leaves the batch as BYTES (a quarter of its stores) and every later launch of the step reads bytes
-            if self.X8 is None:
-                self.X8 = torch.zeros(tuple(self.X.shape), dtype=torch.uint8, device=self.X.device)
-                self.Xp8 = torch.zeros(tuple(self.X.shape), dtype=torch.uint8, device=self.X.device) if need_hist else None
-            f8 = (self.X8, self.Xp8)
-        self._f8 = f8
+        # the label launch leaves the batch as BYTES (a quarter of its stores) and every later launch of the step reads bytes
+        self._f8 = f8 = self._byte_buffers(need_hist) if eng.frames_u8_route() == 'label' else None
         return ops.label_stage(cur, hist, b['idx'], 0, (eng.P.iterations, b['step0'], b['period'], b['stride'], b['offset']),
                                self.X, self.Xp if need_hist else None, hist_chunk, hist_ld, b['w'], self.w_true, bytes_out=f8)
 
     def _main(self):
-        if not self._drop_logits:
-            return self._main_pass()
-        keep, self.eng.keep_logits = self.eng.keep_logits, False
-        try:
-            return self._main_pass()
-        finally:
-            self.eng.keep_logits = keep
-
-    def _main_pass(self):
-        self._f8 = None
+        self._f8 = st = None
         if self._bound is not None:
-            st = self._label_stage()
+            st = self._label_stage()         # the step's first launch assembles the mini-batch (stage=), else a launch of its own
             if st is None:
                 self._stage_bound()
-            elif hasattr(self.eng, 'stage_spec'):
-                self.eng.stage_spec = st
         if self._folded():
             self.eng.loss_and_grads(self.X, self.Xp, self.w_true, self.eps_w, self.eps_z, target=self.Y,
-                                    noise=self.noise_spec(), bump=True)
+                                    noise=self.noise_spec(), bump=True, stage=st)
             return
         if self.is_vrnn:     # eps is drawn inside the label / pair kernels where they run (else one Philox launch in forward())
-            # no all-reduce starts between this half and _tail(): the hW kernel gradient may wait for the pass's last launch
-            if hasattr(self.eng, 'halves_adjacent'):
-                self.eng.halves_adjacent = self.ar is None
+            # adjacent: no all-reduce starts between this half and _tail(), the hW kernel gradient may wait for the pass's last launch
             self.eng.loss_and_grads(self.X, self.Xp, self.w_true, self.eps_w, self.eps_z, do_tail=False, target=self.Y,
-                                    noise=self.noise_spec(), frames8=self._f8)
+                                    noise=self.noise_spec(), frames8=self._f8, stage=st, adjacent=self.ar is None,
+                                    keep_logits=False if self._drop_logits else None)
             return
         self.draw_noise()
         self.eng.loss_and_grads(self.X, self.Xp, self.w_true, self.eps_w, self.eps_z, target=self.Y)
 
     def _tail(self):
-        if self.is_vrnn:
-            self.eng.grads_tail(self.X, frames8=self._f8)
+        self.eng.grads_tail(self.X, frames8=self._f8)
 
     def _update(self):
         # single GPU, cl_vrnn: the backward pass left sum_j K dK of the hW kernel (VrnnEngine.gdot), so Adam-WN runs in two
         # launches instead of five (FlatParams.adam_step); not under data parallelism (the gradient is averaged afterwards)
-        eng = self.eng
-        eng.P.adam_step(lr=self.lr, b2=self.b2, weightnorm=self.weightnorm, advanced=self._folded(), gdot=self._gdot())
+        self.eng.P.adam_step(lr=self.lr, b2=self.b2, weightnorm=self.weightnorm, advanced=self._folded(), gdot=self._gdot())
 
     def _gdot(self):
         """The hW kernel's sum g.V when this step's backward pass left it AND it went through whatever averaged the
         gradient (single GPU: nothing; data parallel: the tail bucket, which then carries it)."""
         eng = self.eng
-        ok = self.fast_adam and getattr(eng, 'gdot_fresh', False) and (self.ar is None or self.pre_in_tail)
-        if hasattr(eng, 'gdot_fresh'):
-            eng.gdot_fresh = False
+        ok = self.fast_adam and eng.gdot_fresh and (self.ar is None or self.pre_in_tail)
+        eng.gdot_fresh = False
         return eng.gdot if ok else None
 
     # multi-GPU: the optimizer step in two pieces, the tail bucket's tensor first (its all-reduce has landed under
@@ -313,7 +296,7 @@ class TrainStep:
         # frames that arrive as bytes are exactly representable in bf16: the LSTM kernel-gradient products then need
         # one bf16 piece for the frame rows (VrnnEngine.frames_exact_bf16); the choice is baked into the captured step
         exact = all(src(x)[0].dtype == torch.uint8 for x in (cur, hist) if x is not None)
-        if hasattr(self.eng, 'frames_exact_bf16') and self.eng.frames_exact_bf16 != exact:
+        if self.eng.frames_exact_bf16 != exact:
             self.eng.frames_exact_bf16 = exact
             self.recapture()
         c, cx = src(cur)
@@ -342,7 +325,7 @@ class TrainStep:
         when both come from uint8 stores that hold only 0 / 1 (checked once per store: a list says which notes are on,
         not how loud).  Tells the engine whether its lists describe the staged batch (baked into the captured step)."""
         eng = self.eng
-        if not getattr(eng, 'fuse_notes', False):
+        if not eng.fuse_notes:
             return None
         need = [cur, hist] if eng.off else [cur]           # a decoder without history frames needs no list of them
         ok = all(x is not None and self._is_binary_u8(x.store if isinstance(x, DevWindows) else x) for x in need)
@@ -396,20 +379,17 @@ class TrainStep:
         if self.ar is None:
             return self._single()
         self._main()
-        if self.ar is not None:
-            self.ar.reduce_tail()       # the hW-kernel bucket (most of the bytes) is complete: reduce it under _tail()
+        self.ar.reduce_tail()       # the hW-kernel bucket (most of the bytes) is complete: reduce it under _tail()
         self._tail()
-        if self.ar is not None:
-            self.ar.reduce_main()
-            if self.split_update:
-                self.ar.wait_tail()
-                self._update_tail()
-                self.ar.wait()
-                self._update_rest()
-                self._accumulate()
-                return
+        self.ar.reduce_main()
+        if self.split_update:
+            self.ar.wait_tail()
+            self._update_tail()
             self.ar.wait()
-        self._update()
+            self._update_rest()
+        else:
+            self.ar.wait()
+            self._update()
         self._accumulate()
 
     def tune_dp_schedule(self, steps=20, warm=3):
@@ -419,11 +399,11 @@ class TrainStep:
         the same decision.  Returns (and keeps in `dp_trials`) {'coarse_ms', 'fine_ms', 'chosen'}."""
         import time
         eng = self.eng
-        if self.ar is None or not hasattr(eng, 'fine_grid') or 'fine_grid' in eng.cfg:
+        if self.ar is None or not self.is_vrnn or 'fine_grid' in eng.cfg:
             return None
         import torch.distributed as dist
         saved = [t.clone() for t in eng.P.state_tensors()]
-        flags = (eng.P.norms_valid, getattr(eng, 'gdot_fresh', False))
+        flags = (eng.P.norms_valid, eng.gdot_fresh)
         res = {}
         for name, fine in (('coarse_ms', False), ('fine_ms', True)):
             eng.fine_grid = fine
@@ -445,8 +425,7 @@ class TrainStep:
             for t, sv in zip(eng.P.state_tensors(), saved):
                 t.copy_(sv)
             eng.P.norms_valid = flags[0]
-            if hasattr(eng, 'gdot_fresh'):
-                eng.gdot_fresh = flags[1]
+            eng.gdot_fresh = flags[1]
         eng.fine_grid = res['fine_ms'] < res['coarse_ms']
         res['chosen'] = 'fine' if eng.fine_grid else 'coarse'
         self.recapture()
@@ -468,22 +447,21 @@ class TrainStep:
             self._warm = True
             return
         if self._graphs is None:
+            self._graph_fast = bool(self.eng.P.norms_valid)
             if self.ar is None:
                 # the captured optimizer takes its short form only while the column norms follow the parameters
                 # (FlatParams.norms_valid); a step after they were written from outside runs eagerly (and re-validates)
-                self._graph_fast = bool(getattr(self.eng.P, 'norms_valid', False))
                 with ops.Graph() as g:
                     self._single()
                 self._graphs = (g,)
             else:
-                self._graph_fast = bool(getattr(self.eng.P, 'norms_valid', False))
                 if self._capture_whole_dp_step():
                     return self._launch_dp()
                 with ops.Graph() as g1:
                     self._main()
                 # whether the captured backward pass writes the hW kernel's sum g.V (only its sparse form does): the
                 # replayed steps restore the flag from this, never assume it
-                self._main_leaves_gdot = bool(getattr(self.eng, 'gdot_fresh', False))
+                self._main_leaves_gdot = bool(self.eng.gdot_fresh)
                 with ops.Graph() as g2:
                     self._tail()
                 if self.split_update and os.environ.get('CLV_DP_EAGER_UPDATE', '1') != '0':
@@ -501,7 +479,7 @@ class TrainStep:
                         self._update()
                     self._graphs = (g1, g2, g3)
         if self.ar is None:
-            if getattr(self, '_graph_fast', False) and not self.eng.P.norms_valid:
+            if self._graph_fast and not self.eng.P.norms_valid:
                 self._eager()
                 return
             self._graphs[0].launch()
@@ -535,7 +513,7 @@ class TrainStep:
             return False
 
     def _launch_dp(self):
-        if getattr(self, '_graph_fast', False) and not self.eng.P.norms_valid:
+        if self._graph_fast and not self.eng.P.norms_valid:
             self._eager()
             return
         if self._graphs[0] == 'whole':
@@ -552,8 +530,7 @@ class TrainStep:
             if g3 is not None:
                 g3.launch()
             else:
-                if hasattr(self.eng, 'gdot_fresh'):
-                    self.eng.gdot_fresh = self._main_leaves_gdot      # what the replayed backward pass has left
+                self.eng.gdot_fresh = self._main_leaves_gdot      # what the replayed backward pass has left
                 self._update_tail()
             self.ar.wait()
             if self._graphs[3] is not None:
