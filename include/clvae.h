@@ -674,7 +674,10 @@ int clv_vrnn_label_fwd_x_proj_supported(int B, int D, int nx, int T, int N);
  * label path.  From a few hundred batch rows on this replaces the note-walking gather (every kernel row is then fetched
  * once per workgroup instead of once per batch row that has the note).  N <= 96; N, ldx, ldk multiples of 4, nx of 8;
  * 16-byte aligned X and K; arrays below 2 GiB.  x_u8 != 0: X holds the frames as BYTES (uint8, ldx in bytes, 4-byte
- * aligned) -- the frame store's own format, widened inside the kernel (clv_frames_u8 below).  cl_vrnn/model.py:174-176. */
+ * aligned) -- the frame store's own format, widened inside the kernel (clv_frames_u8 below).  cl_vrnn/model.py:174-176.
+ * The chunks: with rb = ceil(Bn / 64) row blocks, chunks = ceil(256 / rb), at most nx / 64 (integer division) and at least 1;
+ * a chunk is ceil(nx / chunks) inputs rounded up to a multiple of 32, splits = ceil(nx / chunk); chunk c holds the inputs
+ * [c chunk, min(nx, (c + 1) chunk)).  part is [splits][Bn][N], exactly workspace_bytes = splits * Bn * N * 4. */
 int clv_dense_window_fwd_bf16_supported(int Bn, int nx, int N, int ldx, int ldk);
 int clv_dense_window_fwd_bf16_splits(int Bn, int nx);
 size_t clv_dense_window_fwd_bf16_workspace_bytes(int Bn, int nx, int N);
@@ -777,9 +780,11 @@ int clv_axpy(int64_t n, float alpha, const float* x, float* y, void* stream);
 /* Input projection of sparse frames: out[r, 0:N] = sum_k X[r,k] * K[k,:] for r < R, X [R,ldx] (nx used
  * columns), K [nx,N] (16-byte aligned), out rows of stride ldo.  The LSTM input projections of cl_vrnn
  * (cl_vrnn/model.py:193-196, 218-226) multiply piano-roll frames that are ~4 % nonzero; this keeps K in LDS
- * and adds only the kernel rows of a frame's nonzero inputs.  Exact for any float input (cost grows with
- * the number of nonzeros); clv_sparse_proj_supported: nx <= 128, N <= 384, nx*N*4 <= 150 KB.  x_u8 != 0: X holds the frames
- * as bytes (uint8 rows, ldx in bytes). */
+ * and adds only the kernel rows of a frame's nonzero inputs.  Right for any float input (cost grows with
+ * the number of nonzeros): out = fma(X[r,k], K[k,:], out) over the nonzero inputs k in ascending order, from 0 -- for
+ * 0/1 frames bit for bit the sequential fp32 sum of the listed kernel rows, for other inputs within fp32 rounding of the
+ * product (tests/window_reference.py).  clv_sparse_proj_supported: nx <= 128, N <= 384, nx*N a multiple of 4,
+ * nx*N*4 <= 150 KB.  x_u8 != 0: X holds the frames as bytes (uint8 rows, ldx in bytes). */
 int clv_sparse_proj_supported(int nx, int N);
 size_t clv_sparse_proj_lds_bytes(int nx, int N);
 int clv_sparse_proj(int R, int nx, int N, const void* X, int x_u8, int ldx, const float* K, float* out, int ldo, void* stream);
