@@ -768,7 +768,7 @@ extern "C" int clv_gemm_f32(int transa, int transb, int M, int N, int K, float a
                                      const float* bias, int act, const float* aux,
                                      int split_k, void* ws, size_t ws_bytes, clv_reduce_job* job, void* stream) {
   using namespace clv;
-  if (job) memset(job, 0, sizeof(*job));
+  clear_job(job);
   if (M <= 0 || N <= 0 || K < 0 || !A || !B || !C) return CLV_EINVAL;
   if (act < CLV_ACT_NONE || act > CLV_ACT_MASKPOS) return CLV_EINVAL;
   if (act == CLV_ACT_MASKPOS && !aux) return CLV_EINVAL;
@@ -803,11 +803,7 @@ extern "C" int clv_gemm_f32(int transa, int transb, int M, int N, int K, float a
   }
   int st = launch_status();
   if (st) return st;
-  if (splits > 1) {
-    const ReduceJob j = make_job(g, splits);
-    if (job) memcpy(job, &j, sizeof(j));       // the caller reduces later (clv_splitk_reduce_multi)
-    else st = launch_reduce(j, s);
-  }
+  if (splits > 1) st = finish_or_defer(make_job(g, splits), splits, job, s);      // (an unsplit product needs no reduction)
   return st;
 }
 
@@ -880,7 +876,7 @@ extern "C" int clv_gemm_grouped_tn(const clv_gemm_prob* probs, int nprob, int N,
                                             const float* B, int ldb, float beta,
                                             int split_k, void* ws, size_t ws_bytes, clv_reduce_job* job, void* stream) {
   using namespace clv;
-  if (job) memset(job, 0, sizeof(*job));
+  clear_job(job);
   if (!probs || nprob < 1 || nprob > MAX_PROB || N <= 0 || K <= 0 || !B) return CLV_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   GemmArgs g;
@@ -957,11 +953,7 @@ extern "C" int clv_gemm_grouped_tn(const clv_gemm_prob* probs, int nprob, int N,
   }
   int st = launch_status();
   if (st) return st;
-  if (splits > 1) {
-    const ReduceJob j = make_job(g, splits);
-    if (job) memcpy(job, &j, sizeof(j));
-    else st = launch_reduce(j, s);
-  }
+  if (splits > 1) st = finish_or_defer(make_job(g, splits), splits, job, s);
   return st;
 }
 

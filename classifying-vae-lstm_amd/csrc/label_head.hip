@@ -610,7 +610,7 @@ extern "C" int clv_vrnn_label_bwd(int B, int D, int C, int G4, const float* dzsu
                                      float prior_logvar, float class_weight, float w_kl_weight, float inv_b,
                                      float* dwargs, float* dhW, float* dKa, float* dba, void* ws, size_t ws_bytes,
                                      clv_reduce_job* job, void* stream) {
-  if (job) memset(job, 0, sizeof(*job));
+  clear_job(job);
   if (B <= 0 || D <= 0 || D > 128 || C < 2 || C > LH_MAXC || G4 <= 0) return CLV_EINVAL;
   if (!dzsum_enc || !dzsum_dec || !Kenc_w || !Kdec_w || !wargs || !eps || !onehot || !W || !hW || !Ka || !dwargs || !dhW)
     return CLV_EINVAL;
@@ -625,17 +625,7 @@ extern "C" int clv_vrnn_label_bwd(int B, int D, int C, int G4, const float* dzsu
   }
   int st = launch_status();
   if (st || !wg) return st;
-  ReduceJob j;
-  memset(&j, 0, sizeof(j));
-  const int NA = 2 * (C - 1);
-  j.partial = (const float*)ws;
-  j.M = D + 1; j.N = NA; j.splits = B; j.nprob = 2;
-  j.alpha = 1.f; j.beta = 0.f; j.act = CLV_ACT_NONE;
-  j.prob[0] = ReduceProb{dKa, NA, 0};
-  j.prob[1] = ReduceProb{dba, NA, D};
-  if (job && B > 1) memcpy(job, &j, sizeof(j));
-  else st = launch_reduce(j, s);
-  return st;
+  return finish_or_defer(kernel_bias_job(ws, D + 1, 2 * (C - 1), B, dKa, dba, D), B, job, s);
 }
 
 extern "C" int clv_vrnn_label_fwd_x_proj_supported(int B, int D, int nx, int T, int N);

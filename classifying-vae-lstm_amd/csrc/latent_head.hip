@@ -461,6 +461,7 @@ extern "C" int clv_latent_head_bwd(int R, int H, int L, const float* hs, const f
                                    const float* eps, const float* dZ, int lddz, float kl_scale, float* dzargs, float* dhs,
                                    float* dWz, float* dbz, void* ws, size_t ws_bytes, clv_reduce_job* job, void* stream) {
   using namespace clv;
+  clear_job(job);
   if (!clv_latent_head_supported(H, L) || R <= 0 || lddz < L) return CLV_EINVAL;
   if (!hs || !Wz || !zargs || !eps || !dZ || !dhs || !dWz || !dbz || ((uintptr_t)hs) % 16 != 0) return CLV_EINVAL;
   if (!ws || ws_bytes < clv_latent_head_bwd_workspace_bytes(R, L)) return CLV_EWORKSPACE;
@@ -480,16 +481,5 @@ extern "C" int clv_latent_head_bwd(int R, int H, int L, const float* hs, const f
   }
   int st = launch_status();
   if (st) return st;
-  ReduceJob j;
-  memset(&j, 0, sizeof(j));
-  j.partial = (const float*)ws; j.M = ZH_SLAB_ROWS; j.N = 2 * L; j.splits = wgs; j.nprob = 2;
-  j.alpha = 1.f; j.beta = 0.f; j.act = CLV_ACT_NONE;
-  j.prob[0] = ReduceProb{dWz, 2 * L, 0};
-  j.prob[1] = ReduceProb{dbz, 2 * L, ZH};
-  if (job && wgs > 1) {
-    memcpy(job, &j, sizeof(j));   // the caller reduces later (clv_splitk_reduce_multi)
-    return CLV_OK;
-  }
-  if (job) memset(job, 0, sizeof(*job));      // a single slab is finished here (the multi-reduce skips empty jobs)
-  return launch_reduce(j, s);
+  return finish_or_defer(kernel_bias_job(ws, ZH_SLAB_ROWS, 2 * L, wgs, dWz, dbz, ZH), wgs, job, s);
 }

@@ -970,8 +970,8 @@ extern "C" int clv_lstm_pair_bwd(int B, int T, int H, int L, int gate_act, float
                                     const float* hs_enc, float* dWz, float* dbz, void* ws, size_t ws_bytes, clv_reduce_job* job,
                                     const clv_label_bwd_rider* label, void* stream) {
   using namespace clv;
-  if (job) memset(job, 0, sizeof(*job));
-  if (label && label->job) memset(label->job, 0, sizeof(*label->job));
+  clear_job(job);
+  if (label) clear_job(label->job);
   if (label) {
     const clv_label_bwd_rider& r = *label;
     if (r.D <= 0 || r.D > 128 || r.C < 2 || r.C > LH_MAXC) return CLV_EINVAL;
@@ -1010,30 +1010,13 @@ extern "C" int clv_lstm_pair_bwd(int B, int T, int H, int L, int gate_act, float
   int st = launch_status();
   if (st) return st;
   if (label && label->dKa) {       // the Wargs layer's per-row slabs, exactly as clv_vrnn_label_bwd leaves them
-    ReduceJob jl;
-    memset(&jl, 0, sizeof(jl));
-    const int NA = 2 * (label->C - 1);
-    jl.partial = (const float*)label->ws;
-    jl.M = label->D + 1; jl.N = NA; jl.splits = B; jl.nprob = 2;
-    jl.alpha = 1.f; jl.beta = 0.f; jl.act = CLV_ACT_NONE;
-    jl.prob[0] = ReduceProb{label->dKa, NA, 0};
-    jl.prob[1] = ReduceProb{label->dba, NA, label->D};
-    if (label->job && B > 1) memcpy(label->job, &jl, sizeof(jl));
-    else st = launch_reduce(jl, s);
+    const clv_label_bwd_rider& r = *label;
+    st = finish_or_defer(kernel_bias_job(r.ws, r.D + 1, 2 * (r.C - 1), B, r.dKa, r.dba, r.D), B, r.job, s);
     if (st) return st;
   }
   if (!wzg) return st;
   // the per-row slabs [B][89][2L] -> dWz [88,2L] and dbz [2L]: a pending reduction like a split-K product's
-  ReduceJob j;
-  memset(&j, 0, sizeof(j));
-  j.partial = (const float*)ws;
-  j.M = LH + 1; j.N = 2 * L; j.splits = B; j.nprob = 2;
-  j.alpha = 1.f; j.beta = 0.f; j.act = CLV_ACT_NONE;
-  j.prob[0] = ReduceProb{dWz, 2 * L, 0};
-  j.prob[1] = ReduceProb{dbz, 2 * L, LH};
-  if (job && B > 1) memcpy(job, &j, sizeof(j));
-  else st = launch_reduce(j, s);
-  return st;
+  return finish_or_defer(kernel_bias_job(ws, LH + 1, 2 * L, B, dWz, dbz, LH), B, job, s);
 }
 
 extern "C" size_t clv_lstm_pair_bwd_workspace_bytes(int B, int H, int L) {

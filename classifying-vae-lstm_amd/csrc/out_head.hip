@@ -306,6 +306,7 @@ extern "C" int clv_out_head_train(int R, int H, int D, const float* hs, const fl
                                   float* dhs, float* dWo, float* dbo, void* ws, size_t ws_bytes, clv_reduce_job* job,
                                   void* stream) {
   using namespace clv;
+  clear_job(job);
   if (!clv_out_head_train_supported(H, D) || R <= 0 || ldy < D) return CLV_EINVAL;
   if (!hs || !Wo || !bo || !Y || !rownll || !dhs || !dWo || !dbo) return CLV_EINVAL;
   if (((uintptr_t)hs) % 16 != 0 || ((uintptr_t)Wo) % 16 != 0) return CLV_EINVAL;
@@ -326,16 +327,5 @@ extern "C" int clv_out_head_train(int R, int H, int D, const float* hs, const fl
   }
   int st = launch_status();
   if (st) return st;
-  ReduceJob j;
-  memset(&j, 0, sizeof(j));
-  j.partial = (const float*)ws; j.M = OH_SLAB_ROWS; j.N = OH; j.splits = wgs; j.nprob = 2;
-  j.alpha = 1.f; j.beta = 0.f; j.act = CLV_ACT_NONE;
-  j.prob[0] = ReduceProb{dWo, OH, 0};
-  j.prob[1] = ReduceProb{dbo, OH, OH};
-  if (job && wgs > 1) {
-    memcpy(job, &j, sizeof(j));   // the caller reduces later (clv_splitk_reduce_multi)
-    return CLV_OK;
-  }
-  if (job) memset(job, 0, sizeof(*job));      // a single slab is finished here (the multi-reduce skips empty jobs)
-  return launch_reduce(j, s);
+  return finish_or_defer(kernel_bias_job(ws, OH_SLAB_ROWS, OH, wgs, dWo, dbo, OH), wgs, job, s);
 }

@@ -489,20 +489,38 @@ static int wgrad_splits(int K, int split_scale, int base_ranges = 128) {
 extern "C" size_t clv_lstm_wgrad_workspace_bytes(int K, int N, int nx, int nh, int nz, int split_scale) {
   return (size_t)wgrad_splits(K, split_scale) * (nx + nh + nz) * N * sizeof(float);
 }
+
+// The argument checks of one product, for the single and the pair entry (the workspace is each entry's own check).
+static bool wgrad_problem_ok(const clv_wgrad_problem& p) {
+  if (!clv_lstm_wgrad_supported(p.N, p.nx, p.nh, p.nz, p.x_exact_bf16) || p.K <= 0 || !p.X || !p.H || !p.dz || !p.dKx || !p.dU ||
+      (p.nz > 0 && (!p.Z || !p.dKz)))
+    return false;
+  if (!clv_lstm_wgrad_rows_supported(p.K, p.ldx, p.x_exact_bf16, p.ldh, p.ldz, p.nz, p.lddz)) return false;
+  // (the frames as bytes have ldx in bytes and 4-byte aligned rows)
+  return !(p.ldx % 4 || p.ldh % 4 || p.lddz % 4 || ((uintptr_t)p.H | (uintptr_t)p.dz) % 16 ||
+           ((uintptr_t)p.X) % (p.x_exact_bf16 == CLV_FRAMES_U8 ? 4 : 16));
+}
+
+// The slabs [splits][nx + nh + nz][N] of one product -> its two or three tensors (C = beta * C + sum).  A single slab
+// still goes through the reduction: it scatters the rows to the tensors.
+static clv::ReduceJob wgrad_job(const clv_wgrad_problem& w, int N, int splits) {
+  const clv::ReduceProb kx{w.dKx, w.ld_kx, 0}, u{w.dU, w.ld_u, w.nx}, kz{w.dKz, w.ld_kz, w.nx + w.nh};
+  const int M = w.nx + w.nh + w.nz;
+  return w.nz > 0 ? clv::slab_job(w.ws, M, N, splits, w.beta, {kx, u, kz}) : clv::slab_job(w.ws, M, N, splits, w.beta, {kx, u});
+}
+
 extern "C" int clv_lstm_wgrad(int K, int N, const void* X, int ldx, int nx, int x_exact_bf16,
                                  const float* H, int ldh, int nh, int h_shift, int h_zero_period,
                                  const float* Z, int ldz, int nz, const float* dz, int lddz,
                                  float* dKx, int ld_kx, float* dU, int ld_u, float* dKz, int ld_kz, float beta,
                                  int split_scale, void* ws, size_t ws_bytes, clv_reduce_job* job, void* stream) {
   using namespace clv;
-  if (split_scale < 1 || split_scale > 8) return CLV_EINVAL;
-  if (job) memset(job, 0, sizeof(*job));
-  if (!clv_lstm_wgrad_supported(N, nx, nh, nz, x_exact_bf16) || K <= 0 || !X || !H || !dz || !dKx || !dU || (nz > 0 && (!Z || !dKz)))
-    return CLV_EINVAL;
-  const bool xu8 = x_exact_bf16 == CLV_FRAMES_U8;           // the frames as bytes (ldx in bytes): 4-byte aligned rows
-  if (ldx % 4 || ldh % 4 || lddz % 4 || ((uintptr_t)H | (uintptr_t)dz) % 16 || ((uintptr_t)X) % (xu8 ? 4 : 16)) return CLV_EINVAL;
-  if (!clv_lstm_wgrad_rows_supported(K, ldx, x_exact_bf16, ldh, ldz, nz, lddz)) return CLV_EINVAL;
+  clear_job(job);
+  const clv_wgrad_problem w{K, N, X, ldx, nx, x_exact_bf16, H, ldh, nh, h_shift, h_zero_period, Z, ldz, nz, dz, lddz,
+                            dKx, ld_kx, dU, ld_u, dKz, ld_kz, beta, ws, ws_bytes};
+  if (split_scale < 1 || split_scale > 8 || !wgrad_problem_ok(w)) return CLV_EINVAL;
   if (clv_lstm_wgrad_workspace_bytes(K, N, nx, nh, nz, split_scale) > ws_bytes || !ws || ((uintptr_t)ws) % 16) return CLV_EWORKSPACE;
+  const bool xu8 = x_exact_bf16 == CLV_FRAMES_U8;
   hipStream_t s = (hipStream_t)stream;
   const int splits = wgrad_splits(K, split_scale);
   const int kc = wgrad_kc(K, split_scale);
@@ -524,31 +542,10 @@ extern "C" int clv_lstm_wgrad(int K, int N, const void* X, int ldx, int nx, int 
   }
   int st = launch_status();
   if (st) return st;
-  ReduceJob j;
-  memset(&j, 0, sizeof(j));
-  j.partial = (const float*)ws;
-  j.M = nx + nh + nz; j.N = N; j.splits = splits; j.nprob = nz > 0 ? 3 : 2;
-  j.alpha = 1.f; j.beta = beta; j.act = CLV_ACT_NONE;
-  j.prob[0] = ReduceProb{dKx, ld_kx, 0};
-  j.prob[1] = ReduceProb{dU, ld_u, nx};
-  if (nz > 0) j.prob[2] = ReduceProb{dKz, ld_kz, nx + nh};
-  // a single slab still goes through the reduction (it scatters the rows to the three tensors), but at once: the
-  // deferred queue skips jobs without a split
-  if (job && splits > 1) memcpy(job, &j, sizeof(j));
-  else st = launch_reduce(j, s);
-  return st;
+  return finish_or_defer(wgrad_job(w, N, splits), splits, job, s);
 }
 
 // ---- both LSTMs of a step in one launch -------------------------------------------------------------------------------
-static bool wgrad_problem_ok(const clv_wgrad_problem& p) {
-  if (!clv_lstm_wgrad_supported(p.N, p.nx, p.nh, p.nz, p.x_exact_bf16) || p.K <= 0 || !p.X || !p.H || !p.dz || !p.dKx || !p.dU ||
-      (p.nz > 0 && (!p.Z || !p.dKz)))
-    return false;
-  if (!clv_lstm_wgrad_rows_supported(p.K, p.ldx, p.x_exact_bf16, p.ldh, p.ldz, p.nz, p.lddz)) return false;
-  return !(p.ldx % 4 || p.ldh % 4 || p.lddz % 4 || ((uintptr_t)p.H | (uintptr_t)p.dz) % 16 ||
-           ((uintptr_t)p.X) % (p.x_exact_bf16 == CLV_FRAMES_U8 ? 4 : 16));
-}
-
 extern "C" int clv_lstm_wgrad_pair_supported(const clv_wgrad_problem* p, const clv_wgrad_problem* q) {
   if (!p || !q || !wgrad_problem_ok(*p) || !wgrad_problem_ok(*q)) return 0;
   // one kernel instance, one grid: the same row count, the same tile geometry, the same number of frame pieces
@@ -563,10 +560,9 @@ extern "C" size_t clv_lstm_wgrad_pair_workspace_bytes(int K, int N, int nx, int 
 extern "C" int clv_lstm_wgrad_pair(const clv_wgrad_problem* p, const clv_wgrad_problem* q, int split_scale,
                                    clv_reduce_job* job_p, clv_reduce_job* job_q, void* stream) {
   using namespace clv;
-  if (split_scale < 1 || split_scale > 8) return CLV_EINVAL;
-  if (job_p) memset(job_p, 0, sizeof(*job_p));
-  if (job_q) memset(job_q, 0, sizeof(*job_q));
-  if (!clv_lstm_wgrad_pair_supported(p, q)) return CLV_EINVAL;
+  clear_job(job_p);
+  clear_job(job_q);
+  if (split_scale < 1 || split_scale > 8 || !clv_lstm_wgrad_pair_supported(p, q)) return CLV_EINVAL;
   const clv_wgrad_problem* pr[2] = {p, q};
   for (int i = 0; i < 2; ++i)
     if (clv_lstm_wgrad_pair_workspace_bytes(pr[i]->K, pr[i]->N, pr[i]->nx, pr[i]->nh, pr[i]->nz, split_scale) > pr[i]->ws_bytes ||
@@ -598,18 +594,6 @@ extern "C" int clv_lstm_wgrad_pair(const clv_wgrad_problem* p, const clv_wgrad_p
   int st = launch_status();
   if (st) return st;
   clv_reduce_job* jobs[2] = {job_p, job_q};
-  for (int i = 0; i < 2 && !st; ++i) {
-    const clv_wgrad_problem& w = *pr[i];
-    ReduceJob j;
-    memset(&j, 0, sizeof(j));
-    j.partial = (const float*)w.ws;
-    j.M = w.nx + w.nh + w.nz; j.N = N; j.splits = splits; j.nprob = w.nz > 0 ? 3 : 2;
-    j.alpha = 1.f; j.beta = w.beta; j.act = CLV_ACT_NONE;
-    j.prob[0] = ReduceProb{w.dKx, w.ld_kx, 0};
-    j.prob[1] = ReduceProb{w.dU, w.ld_u, w.nx};
-    if (w.nz > 0) j.prob[2] = ReduceProb{w.dKz, w.ld_kz, w.nx + w.nh};
-    if (jobs[i] && splits > 1) memcpy(jobs[i], &j, sizeof(j));
-    else st = launch_reduce(j, s);
-  }
+  for (int i = 0; i < 2 && !st; ++i) st = finish_or_defer(wgrad_job(*pr[i], N, splits), splits, jobs[i], s);
   return st;
 }

@@ -55,15 +55,10 @@ class ReduceQueue:
         return buf
 
     def next_job(self):
-        j = C.byref(self.jobs, self.n * C.sizeof(_lib.ReduceJob))
+        """the next slot's job, as an address: an argument, or a job pointer that travels inside a struct"""
+        j = C.c_void_p(C.addressof(self.jobs) + self.n * C.sizeof(_lib.ReduceJob))
         self.n += 1
         return j
-
-    def next_job_addr(self):
-        """the next slot's address (for a job pointer that travels inside a struct)"""
-        a = C.addressof(self.jobs) + self.n * C.sizeof(_lib.ReduceJob)
-        self.n += 1
-        return a
 
     def flush(self, means=None, out=None, skinny=None, outer=None):
         """Run the pending reductions in one launch.  means: up to five (tensor, n, stride) terms whose means go to
@@ -97,6 +92,30 @@ class ReduceQueue:
         self.n = 0
 
 
+def _scratch(need, ws, defer):
+    """(buf, job) for a producer's slabs: the queue's next slot (its buffer first, then its job: the buffers are cached
+    per slot) under a ReduceQueue, else the Workspace and no job -- the reduction then runs inside the call."""
+    if defer is None:
+        return ws.ensure(need), None
+    return defer.scratch(need), defer.next_job()
+
+
+def _scratch_regions(needs, ws, defer):
+    """[(address, job)] for the slab regions of ONE call (need None: no such region, (None, None)): a queue slot each, in
+    order, under a ReduceQueue; else one Workspace buffer, every region behind the 256-byte-aligned end of the one before."""
+    if defer is not None:
+        slots = [_scratch(n, None, defer) if n is not None else (None, None) for n in needs]
+        return [(buf.data_ptr() if buf is not None else None, job) for buf, job in slots]
+    offs, end = [], 0
+    for n in needs:
+        offs.append((end + 255) // 256 * 256)
+        end = offs[-1] + (n or 0)
+    if all(n is None for n in needs):
+        return [(None, None)] * len(needs)
+    base = _scratch(end, ws, None)[0].data_ptr()
+    return [(base + o if n is not None else None, None) for n, o in zip(needs, offs)]
+
+
 def reduce_outer_supported(Bn, nx, N, ldx, ldg):
     """shapes ReduceQueue.flush(outer=...) takes"""
     return bool(_lib.lib().clv_splitk_reduce_multi_outer_supported(Bn, nx, N, ldx, ldg))
@@ -114,13 +133,21 @@ def gemm(A, B, C_out, M, N, K, ta=False, tb=False, lda=None, ldb=None, ldc=None,
         split_k = L.clv_gemm_auto_split(M, N, K)
     wsp, wsb, job = None, 0, None
     if split_k > 1:
-        need = L.clv_gemm_workspace_bytes(M, N, split_k)
-        buf = defer.scratch(need) if defer is not None else ws.ensure(need)
+        buf, job = _scratch(L.clv_gemm_workspace_bytes(M, N, split_k), ws, defer)
         wsp, wsb = _ptr(buf), buf.numel()
-        job = defer.next_job() if defer is not None else None
     check(L.clv_gemm_f32(int(ta), int(tb), M, N, K, float(alpha), _ptr(A), lda, _ptr(B), ldb, float(beta),
                                   _ptr(C_out), ldc, _ptr(bias), act, _ptr(aux), split_k, wsp, wsb, job, _stream()),
           "clv_gemm_f32")
+
+
+def _prob_array(probs, N):
+    arr = (_lib.GemmProb * len(probs))()
+    for i, p in enumerate(probs):
+        A = p.get('A')
+        arr[i] = _lib.GemmProb(A.data_ptr() if A is not None else None, p.get('lda', p['M']), p['M'],
+                               p['C'].data_ptr(), p.get('ldc', N), p.get('shift', 0), p.get('zero_period', 0),
+                               int(p.get('ones', 0)))
+    return arr
 
 
 def gemm_grouped_tn(probs, N, K, B, ws, ldb=None, beta=0.0, split_k=None, defer=None, split_scale=1):
@@ -128,23 +155,15 @@ def gemm_grouped_tn(probs, N, K, B, ws, ldb=None, beta=0.0, split_k=None, defer=
     ones=1: implicit row of ones (M == 1); ones=2: row M-1 is an implicit row of ones appended to A's M-1 columns;
     C_p[M_p,N] = A_p^T . B for every problem in one launch (all share B [K,N])."""
     L = _lib.lib()
-    arr = (_lib.GemmProb * len(probs))()
-    for i, p in enumerate(probs):
-        A = p.get('A')
-        arr[i] = _lib.GemmProb(A.data_ptr() if A is not None else None, p.get('lda', p['M']), p['M'],
-                               p['C'].data_ptr(), p.get('ldc', N), p.get('shift', 0), p.get('zero_period', 0),
-                               int(p.get('ones', 0)))
-    n = len(probs)
+    arr, n = _prob_array(probs, N), len(probs)
     if split_k is None:
         split_k = L.clv_gemm_grouped_auto_split(arr, n, N, K)
         if split_k > 1:
             split_k *= int(split_scale)      # finer grid: more, shorter workgroups (see VrnnEngine.fine_grid)
     wsp, wsb, job = None, 0, None
     if split_k > 1:
-        need = L.clv_gemm_grouped_workspace_bytes(arr, n, N, split_k)
-        buf = defer.scratch(need) if defer is not None else ws.ensure(need)
+        buf, job = _scratch(L.clv_gemm_grouped_workspace_bytes(arr, n, N, split_k), ws, defer)
         wsp, wsb = _ptr(buf), buf.numel()
-        job = defer.next_job() if defer is not None else None
     check(L.clv_gemm_grouped_tn(arr, n, N, K, _ptr(B), ldb if ldb is not None else N, float(beta), split_k,
                                          wsp, wsb, job, _stream()), "clv_gemm_grouped_tn")
 
@@ -165,9 +184,7 @@ def lstm_wgrad(K, N, X, ldx, nx, x_exact_bf16, H, ldh, nh, T, Z, ldz, nz, dz, dK
     dKx = X^T dz, dU = H'^T dz (H' = hs shifted by one step, zero at window starts: period T), dKz = Z^T dz.
     split_scale: that many times as many, shorter row ranges (2 under the data-parallel step: see include/clvae.h)."""
     L = _lib.lib()
-    need = L.clv_lstm_wgrad_workspace_bytes(K, N, nx, nh, nz, int(split_scale))
-    buf = defer.scratch(need) if defer is not None else ws.ensure(need)
-    job = defer.next_job() if defer is not None else None
+    buf, job = _scratch(L.clv_lstm_wgrad_workspace_bytes(K, N, nx, nh, nz, int(split_scale)), ws, defer)
     check(L.clv_lstm_wgrad(K, N, _ptr(X), ldx, nx, _frames_mode(X, x_exact_bf16), _ptr(H), ldh, nh, 1, T,
                               _ptr(Z), ldz, nz, _ptr(dz), N, _ptr(dKx), N, _ptr(dU), N, _ptr(dKz), N, float(beta),
                               int(split_scale), _ptr(buf), buf.numel(), job, _stream()), "clv_lstm_wgrad")
@@ -200,8 +217,8 @@ def lstm_wgrad_pair(p, q, ws, defer=None, split_scale=1):
     for i, t in enumerate((p, q)):
         w = _wgrad_problem(*t)
         need = L.clv_lstm_wgrad_pair_workspace_bytes(w.K, w.N, w.nx, w.nh, w.nz, int(split_scale))
-        buf = defer.scratch(need) if defer is not None else ws[i].ensure(need)
-        jobs.append(defer.next_job() if defer is not None else None)
+        buf, job = _scratch(need, ws[i] if defer is None else None, defer)
+        jobs.append(job)
         w.ws, w.ws_bytes = _ptr(buf), buf.numel()
         probs.append(w)
     check(L.clv_lstm_wgrad_pair(C.byref(probs[0]), C.byref(probs[1]), int(split_scale), jobs[0], jobs[1], _stream()),
@@ -226,9 +243,7 @@ def out_head_train(R, H, D, hs, Wo, bo, Y, scale, rownll, dhs, dWo, dbo, ws, log
     float32 or the bytes themselves (uint8).
     defer: a ReduceQueue that takes the pending reduction of the weight-gradient slabs."""
     L = _lib.lib()
-    need = L.clv_out_head_train_workspace_bytes(R)
-    buf = defer.scratch(need) if defer is not None else ws.ensure(need)
-    job = defer.next_job() if defer is not None else None
+    buf, job = _scratch(L.clv_out_head_train_workspace_bytes(R), ws, defer)
     check(L.clv_out_head_train(R, H, D, _ptr(hs), _ptr(Wo), _ptr(bo), _ptr(Y), _is_u8(Y), ldy if ldy is not None else D,
                                float(scale), _ptr(logits), _ptr(rownll), _ptr(dlogits), _ptr(dhs), _ptr(dWo), _ptr(dbo),
                                _ptr(buf), buf.numel(), job, _stream()), "clv_out_head_train")
@@ -249,22 +264,10 @@ def latent_head_bwd(R, H, L, hs, Wz, zargs, eps, dZ, lddz, kl_scale, dhs, dWz, d
     """The latent head's backward in one launch: dzargs (kept on chip unless a buffer is given), dhs = dzargs.Wz^T and the
     layer's kernel / bias gradient.  defer: a ReduceQueue that takes the pending reduction of the weight-gradient slabs."""
     Lb = _lib.lib()
-    need = Lb.clv_latent_head_bwd_workspace_bytes(R, L)
-    buf = defer.scratch(need) if defer is not None else ws.ensure(need)
-    job = defer.next_job() if defer is not None else None
+    buf, job = _scratch(Lb.clv_latent_head_bwd_workspace_bytes(R, L), ws, defer)
     check(Lb.clv_latent_head_bwd(R, H, L, _ptr(hs), _ptr(Wz), _ptr(zargs), _ptr(eps), _ptr(dZ), lddz, float(kl_scale),
                                  _ptr(dzargs), _ptr(dhs), _ptr(dWz), _ptr(dbz), _ptr(buf), buf.numel(), job, _stream()),
           "clv_latent_head_bwd")
-
-
-def _prob_array(probs, N):
-    arr = (_lib.GemmProb * len(probs))()
-    for i, p in enumerate(probs):
-        A = p.get('A')
-        arr[i] = _lib.GemmProb(A.data_ptr() if A is not None else None, p.get('lda', p['M']), p['M'],
-                               p['C'].data_ptr(), p.get('ldc', N), p.get('shift', 0), p.get('zero_period', 0),
-                               int(p.get('ones', 0)))
-    return arr
 
 
 def gemm_grouped_tn_small2(probs0, B0, probs1, B1, N, K, ldb=None):
@@ -539,38 +542,23 @@ def lstm_pair_bwd(B, T, L, kl_scale, pack, Wz, dhs_dec, aux_dec, aux_enc, gates_
     label = dict(D, C, Kenc_w, Kdec_w, wargs, eps, onehot, W, hW, Ka, prior, class_weight, w_kl_weight, inv_b, dwargs, dhW,
     layer_grad=(dKa, dba) | None): the label path's backward (vrnn_label_bwd) as the kernel's epilogue."""
     Lb = _lib.lib()
-    hs, dWz, dbz, buf, nbytes, job = None, None, None, None, 0, None
-    need_h = Lb.clv_lstm_pair_bwd_workspace_bytes(B, H, L) if head_grad is not None else 0
+    hs, dWz, dbz = head_grad if head_grad is not None else (None, None, None)
     lg = label.get('layer_grad') if label is not None else None
-    need_l = Lb.clv_vrnn_label_bwd_workspace_bytes(B, label['D'], label['C']) if lg is not None else 0
-    lbuf_ptr, ljob = None, None
-    if head_grad is not None:
-        hs, dWz, dbz = head_grad
-        if defer is not None:
-            buf = defer.scratch(need_h)
-            job = defer.next_job()
-        else:                              # one scratch buffer, two regions
-            buf = ws.ensure((need_h + 255) // 256 * 256 + need_l)
-        nbytes = need_h
+    need_h = Lb.clv_lstm_pair_bwd_workspace_bytes(B, H, L) if head_grad is not None else None
+    need_l = Lb.clv_vrnn_label_bwd_workspace_bytes(B, label['D'], label['C']) if lg is not None else None
+    (hptr, job), (lptr, ljob) = _scratch_regions((need_h, need_l), ws, defer)      # the head's slot first, then the label's
     rider = None
     if label is not None:
-        if lg is not None:
-            if defer is not None:
-                lbuf = defer.scratch(need_l)
-                lbuf_ptr, ljob = lbuf.data_ptr(), defer.next_job_addr()
-            else:
-                base = buf if buf is not None else ws.ensure(need_l)
-                lbuf_ptr = base.data_ptr() + ((need_h + 255) // 256 * 256 if buf is not None else 0)
         rider = _lib.LabelBwdRider(label['D'], label['C'], _ptr(label['Kenc_w']), _ptr(label['Kdec_w']), _ptr(label['wargs']),
                                    _ptr(label['eps']), _ptr(label['onehot']), _ptr(label['W']), _ptr(label['hW']),
                                    _ptr(label['Ka']), float(label['prior']), float(label['class_weight']),
                                    float(label['w_kl_weight']), float(label['inv_b']), _ptr(label['dwargs']),
                                    _ptr(label['dhW']), _ptr(lg[0]) if lg else None, _ptr(lg[1]) if lg else None,
-                                   lbuf_ptr, need_l, ljob)
+                                   lptr, need_l or 0, ljob)
     check(Lb.clv_lstm_pair_bwd(B, T, H, L, gate_act, float(kl_scale), _ptr(pack), _ptr(Wz),
                                   _ptr(dhs_dec), _ptr(aux_dec), _ptr(aux_enc), _ptr(gates_dec), _ptr(gates_enc),
                                   _ptr(dzsum_dec), _ptr(dzsum_enc), _ptr(zargs), _ptr(eps), _ptr(dzargs),
-                                  _ptr(hs), _ptr(dWz), _ptr(dbz), _ptr(buf), nbytes, job,
+                                  _ptr(hs), _ptr(dWz), _ptr(dbz), hptr, need_h or 0, job,
                                   C.byref(rider) if rider is not None else None, _stream()),
           "clv_lstm_pair_bwd")
 
@@ -692,10 +680,8 @@ def vrnn_label_bwd(B, D, Cn, G4, dzsum_enc, dzsum_dec, Kenc_w, Kdec_w, wargs, ep
     dKa, dba, buf, nbytes, job = None, None, None, 0, None
     if layer_grad is not None:
         dKa, dba = layer_grad
-        need = Lb.clv_vrnn_label_bwd_workspace_bytes(B, D, Cn)
-        buf = defer.scratch(need) if defer is not None else ws.ensure(need)
+        buf, job = _scratch(Lb.clv_vrnn_label_bwd_workspace_bytes(B, D, Cn), ws, defer)
         nbytes = buf.numel()
-        job = defer.next_job() if defer is not None else None
     check(Lb.clv_vrnn_label_bwd(B, D, Cn, G4, _ptr(dzsum_enc), _ptr(dzsum_dec), _ptr(Kenc_w), _ptr(Kdec_w),
                                    _ptr(wargs), _ptr(eps), _ptr(onehot), _ptr(W), _ptr(hW), _ptr(Ka),
                                    float(prior), float(class_weight), float(w_kl_weight), float(inv_b),

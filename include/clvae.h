@@ -170,7 +170,11 @@ int clv_gemm_grouped_tn_small2(const clv_gemm_prob* probs0, int nprob0, const fl
  * in `ws` and *job describes the pending reduction (+ epilogue) instead of launching it; `ws` must then stay untouched until
  * clv_splitk_reduce_multi has run.  A backward pass queues all of its weight-gradient products this way and finishes them
  * with ONE reduce launch (up to 16 pending jobs; jobs that needed no split are skipped).  Summation order per output is fixed,
- * so results are bit-identical either way. */
+ * so results are bit-identical either way.
+ * The deferred-reduction contract, for every entry point with a `clv_reduce_job* job` (the slab producers below leave one slab
+ * per workgroup or per batch row instead of one per K range): *job is pending only when the call returns CLV_OK and left
+ * more than one slab.  After every other return -- an error, from an argument check on; a product that was not split; a
+ * single slab, which is reduced at once -- *job is all zero: a queue slot never keeps the job of an earlier step. */
 typedef struct { unsigned char opaque[160]; } clv_reduce_job;
 int clv_gemm_f32(int transa, int transb, int M, int N, int K, float alpha,
                           const float* A, int lda, const float* B, int ldb,
@@ -367,8 +371,8 @@ int clv_lstm_mx_bwd(int B, int T, int H, const float* U, const float* dhs, const
  * dhs_dec [B,T,H] is the decoder's upstream gradient (from the output head).
  * hs_enc != NULL: the latent head's weight gradient rides along -- dWz [H,2L] = hs_enc^T . dzargs and dbz [2L] = column sums
  * of dzargs (cl_vrnn/model.py:201-210, the two TimeDistributed Dense heads as one [H,2L] kernel), accumulated per batch
- * row in the chains' spare lanes into ws (>= clv_lstm_pair_bwd_workspace_bytes) and summed over the rows by the pending
- * reduction `job` (NULL: summed at once), like a split-K product's slabs; no GEMM launch, no second read of hs_enc. */
+ * row in the chains' spare lanes into ws (>= clv_lstm_pair_bwd_workspace_bytes): one slab [H + 1, 2L] per batch row; no GEMM
+ * launch, no second read of hs_enc.  `job`: the deferred-reduction contract above clv_reduce_job. */
 int clv_lstm_pair_supported(int H, int L);
 /* Both passes read the recurrent kernels U_enc / U_dec [H,4H], Kz and (forward) Wz from `pack`: every workgroup needs
  * each weight exactly once, one value per lane, and clv_lstm_pair_pack lays them out in that order (one wave load = 1 KB
@@ -703,8 +707,8 @@ int clv_vae_fused_step(int B, int D, int H, int Hc, int C, int L, int use_x_prev
                        float* logits, float* w_out, float* wargs_out, float* zargs_out,
                        float* rownll, float* rowkl, float* rowloss, const clv_vae_step_opts* opts, void* stream);
 /* dKa != NULL -- the Wargs layer's own gradient rides along: dKa [D,2(C-1)] = hW^T . dwargs, dba = column sums of
- * dwargs, as per-row outer products in ws (>= clv_vrnn_label_bwd_workspace_bytes) summed by the pending reduction `job`
- * (NULL: at once), like a split-K product's slabs: no GEMM launch over K = batch. */
+ * dwargs, as per-row outer products in ws (>= clv_vrnn_label_bwd_workspace_bytes): one slab [D + 1, 2(C-1)] per batch row, no
+ * GEMM launch over K = batch.  `job`: the deferred-reduction contract above clv_reduce_job. */
 size_t clv_vrnn_label_bwd_workspace_bytes(int B, int D, int C);
 int clv_vrnn_label_bwd(int B, int D, int C, int G4, const float* dzsum_enc, const float* dzsum_dec,
                           const float* Kenc_w, const float* Kdec_w, const float* wargs, const float* eps,
@@ -741,8 +745,8 @@ int clv_gemm_bce_f32(int M, int N, int K, const float* A, int lda, const float* 
  * gradient exactly as clv_gemm_bce_f32, then dhs = dl.Wo^T (upstream gradient of the decoder BPTT) and
  * dWo = hs^T.dl, dbo = sum_r dl, with dl kept on chip (cl_vrnn/model.py:229-234, 241-242 and their K.gradients).
  * hs [R,88] and Wo 16-byte aligned; logits / dlogits may be NULL (not stored).  dWo/dbo leave as one partial slab per
- * workgroup in `ws`: with job == NULL they are reduced at once, otherwise *job receives the pending reduction for
- * clv_splitk_reduce_multi.  Replaces clv_gemm_bce_f32 + clv_gemm_f32 (NT) + clv_gemm_grouped_tn for this layer.
+ * workgroup in `ws`; `job`: the deferred-reduction contract above clv_reduce_job.
+ * Replaces clv_gemm_bce_f32 + clv_gemm_f32 (NT) + clv_gemm_grouped_tn for this layer.
  * y_u8 != 0: the targets are the frames as BYTES (uint8, ldy in bytes and a multiple of 4, Y 4-byte aligned). */
 int clv_out_head_train_supported(int H, int D);
 size_t clv_out_head_train_workspace_bytes(int R);
@@ -759,8 +763,8 @@ int clv_out_head_train(int R, int H, int D, const float* hs, const float* Wo, co
  *             -- replaces clv_gemm_f32 + clv_gauss_fwd;
  *   backward: dzargs = (dZ + kl_scale*mean | dZ*eps*sd/2 - kl_scale*(1 - sd^2)/2) (stored only when dzargs != NULL),
  *             dhs = dzargs.Wz^T [R,88], dWz = hs^T.dzargs, dbz = sum_r dzargs -- replaces clv_gauss_bwd + clv_gemm_f32 (NT)
- *             + clv_gemm_grouped_tn.  dWz/dbz leave as one partial slab per workgroup in `ws`: with job == NULL they are
- *             reduced at once, otherwise *job receives the pending reduction for clv_splitk_reduce_multi.
+ *             + clv_gemm_grouped_tn.  dWz/dbz leave as one partial slab per workgroup in `ws`; `job`: the deferred-reduction
+ *             contract above clv_reduce_job.
  * hs 16-byte aligned. */
 int clv_latent_head_supported(int H, int L);
 size_t clv_latent_head_bwd_workspace_bytes(int R, int L);

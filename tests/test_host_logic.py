@@ -126,6 +126,63 @@ def test_every_entry_point_survives_null_and_zero_arguments():
             assert rets[n] >= 0, n
 
 
+def test_a_rejected_call_leaves_its_reduce_job_all_zero():
+    """The deferred-reduction contract (include/clvae.h, above clv_reduce_job): after every return other than "deferred",
+    *job is all zero -- an entry point clears it before its first argument check, so a queue slot never keeps the job of
+    an earlier step.  Every entry point that takes a job (clv_lstm_wgrad_pair: two, clv_lstm_pair_bwd: its own and its
+    label rider's) gets jobs filled with 0xAB bytes and arguments it rejects before it touches the device: NULL operands
+    and zero sizes, and for the two heads also a valid shape whose workspace is missing.  In a process of its own."""
+    import sys
+    prog = (
+        "import sys, ctypes as C\n"
+        "sys.path.insert(0, %r)\n"
+        "import clvae_amd\n"
+        "from clvae_amd import _lib\n"
+        "L = _lib.lib()\n"
+        "def zeros(n):\n"
+        "    return [None if a is C.c_void_p else 0.0 if a is C.c_float else 0 for a in _lib.SIGNATURES[n][1]]\n"
+        "def job():\n"
+        "    j = _lib.ReduceJob()\n"
+        "    C.memset(C.byref(j), 0xAB, C.sizeof(j))\n"
+        "    return j\n"
+        "def call(tag, n, v, *jobs):\n"
+        "    print('CALL', tag, flush=True)\n"
+        "    r = getattr(L, n)(*v)\n"
+        "    print('RET', tag, r, *[int(any(bytes(j))) for j in jobs], flush=True)\n"
+        "for n in ('clv_gemm_f32', 'clv_gemm_grouped_tn', 'clv_lstm_wgrad', 'clv_out_head_train', 'clv_latent_head_bwd',\n"
+        "          'clv_vrnn_label_bwd'):\n"
+        "    v, j = zeros(n), job()\n"
+        "    v[-2] = C.byref(j)\n"                     # (..., job, stream)
+        "    call(n, n, v, j)\n"
+        "v, jp, jq = zeros('clv_lstm_wgrad_pair'), job(), job()\n"
+        "v[-3], v[-2] = C.byref(jp), C.byref(jq)\n"    # (p, q, split_scale, job_p, job_q, stream)
+        "call('clv_lstm_wgrad_pair', 'clv_lstm_wgrad_pair', v, jp, jq)\n"
+        "v, j, jl, rider = zeros('clv_lstm_pair_bwd'), job(), job(), _lib.LabelBwdRider()\n"
+        "rider.job = C.addressof(jl)\n"
+        "v[-3], v[-2] = C.byref(j), C.byref(rider)\n"  # (..., job, label, stream)
+        "call('clv_lstm_pair_bwd', 'clv_lstm_pair_bwd', v, j, jl)\n"
+        # a valid shape, operands that look like device memory (never dereferenced on the host), no workspace
+        "p, j = 1 << 20, job()\n"
+        "call('clv_out_head_train:ws', 'clv_out_head_train',\n"
+        "     [4, 88, 88, p, p, p, p, 0, 88, 1.0, None, p, None, p, p, p, None, 0, C.byref(j), None], j)\n"
+        "j = job()\n"
+        "call('clv_latent_head_bwd:ws', 'clv_latent_head_bwd',\n"
+        "     [4, 88, 2, p, p, p, p, p, 2, 1.0, None, p, p, p, None, 0, C.byref(j), None], j)\n" % ROOT)
+    r = subprocess.run([sys.executable, "-c", prog], capture_output=True, text=True, timeout=300)
+    calls = [l.split()[1] for l in r.stdout.splitlines() if l.startswith("CALL")]
+    rets = {l.split()[1]: [int(x) for x in l.split()[2:]] for l in r.stdout.splitlines() if l.startswith("RET")}
+    assert r.returncode == 0, "crashed in %s (exit code %d): %s" % (calls[-1] if calls else "?", r.returncode, r.stderr[-500:])
+    njobs = {"clv_lstm_wgrad_pair": 2, "clv_lstm_pair_bwd": 2}
+    want = ["clv_gemm_f32", "clv_gemm_grouped_tn", "clv_lstm_wgrad", "clv_out_head_train", "clv_latent_head_bwd",
+            "clv_vrnn_label_bwd", "clv_lstm_wgrad_pair", "clv_lstm_pair_bwd", "clv_out_head_train:ws",
+            "clv_latent_head_bwd:ws"]
+    assert sorted(rets) == sorted(want)
+    for tag in want:
+        status, dirty = rets[tag][0], rets[tag][1:]
+        assert status != 0, tag                                    # rejected
+        assert dirty == [0] * njobs.get(tag, 1), (tag, dirty)      # and every job byte is zero
+
+
 def test_adam_plan_layout_on_host():
     L = _lib.lib()
     tab = (_lib.ParamDesc * 3)(_lib.ParamDesc(0, 200, 88, 0, 1, 0), _lib.ParamDesc(17600, 1, 88, 0, 0, 0),
