@@ -17,6 +17,16 @@ def device_f32(a, device):
     return a.to(dtype=torch.float32, device=device).contiguous()
 
 
+def binary_frames(**frames):
+    """cl_vae reads every frame it is given as on / off: the persistent kernel (csrc/vae_generate.hip) forms a note mask and
+    adds kernel rows unweighted, the frame chain multiplies by the value, so the two routes are the same sampler only on
+    frames of 0 and 1.  ValueError for a frame tensor with any other entry (NaN included); None passes.  One device
+    reduction per tensor, before any launch.  cl_vrnn multiplies by the value on both routes and takes any float."""
+    for name, x in frames.items():
+        if x is not None and bool(((x != 0) & (x != 1)).any()):
+            raise ValueError("cl_vae reads frames as on/off: %s has an entry other than 0 and 1" % name)
+
+
 def clamp_roll(clamp, N, nsteps, D, device):
     """A constraint roll for generate(clamp=...): uint8 [N, nsteps, D], one row per returned frame; 0 forces the note off,
     1 forces it on, any other value (harmonize.FREE = 255) leaves it free.  numpy or torch in, contiguous device tensor out;
@@ -196,7 +206,10 @@ STEP_MAX = 2 ** 32 - 1                  # the Philox step is a uint32
 
 class GenState:
     """What a device sampler carries from one call to the next: float32 device tensors [N, width] and the
-    Philox step t of the next frame.  cl_vrnn: h_enc, c_enc, h_dec, c_dec [N, H] after the last frame's cells and x [N, D],
+    Philox step t of the next frame (binary: the frame rows are known to hold only 0 and 1, which the states that the
+    samplers return do by construction; cl_vae checks the others, binary_frames.  The mark describes the rows as the sampler
+    left them: writing into a marked state's tensors voids it, and is the writer's to keep binary).  cl_vrnn: h_enc, c_enc, h_dec, c_dec
+    [N, H] after the last frame's cells and x [N, D],
     the input of the next step (the last clamped sample; the bridge sample after priming with nsteps = 0).  cl_vae: x_in
     [N, D], the last frame, and hist [N, D], the frame before it.  Fields of equal width are views of one tensor `rows`
     [N, fields, width], the layout the persistent kernels read and write.  A state is never written by a call that takes
@@ -220,7 +233,7 @@ class GenState:
                 rows = torch.stack(ts, 1).contiguous()
         elif rows.dim() != 3 or rows.shape[1] != len(names) or rows.dtype != torch.float32 or not rows.is_contiguous():
             raise ValueError("rows must be a contiguous float32 tensor [N, %d, width]" % len(names))
-        self.kind, self.t, self.rows = kind, int(t), rows
+        self.kind, self.t, self.rows, self.binary = kind, int(t), rows, False
         self._d = {k: rows[:, i] for i, k in enumerate(names)} if rows is not None else \
             {k: tensors[k].contiguous() for k in names}
 
@@ -262,8 +275,16 @@ class GenState:
 
     def _like(self, f):
         if self.rows is not None:
-            return GenState(self.kind, None, self.t, rows=f(self.rows).contiguous())
-        return GenState(self.kind, {k: f(v) for k, v in self._d.items()}, self.t)
+            out = GenState(self.kind, None, self.t, rows=f(self.rows).contiguous())
+        else:
+            out = GenState(self.kind, {k: f(v) for k, v in self._d.items()}, self.t)
+        out.binary = self.binary              # copies and selections of rows hold what the rows held
+        return out
+
+    def _sampled(self):
+        """mark a state that a sampler built from its own frames"""
+        self.binary = True
+        return self
 
     def clone(self):
         return self._like(lambda v: v.clone())
@@ -812,7 +833,9 @@ class VaeGenerate:
         state, return_state: continue from a GenState (x_seed is then None: the state holds the last two
         frames) with the Philox steps counted on from state.t, and / or return (Xs, GenState after the last frame).  A
         piece generated in several such calls is bit for bit the piece of one call; the state is the same on both routes
-        and is not written.  Neither given (default): exactly the launches above."""
+        and is not written.  Neither given (default): exactly the launches above.
+        Frames are read as on / off: ValueError (binary_frames) for an x_seed, or a state not returned by a sampler, with
+        an entry other than 0 and 1, on both routes and before anything is launched."""
         cfg, d = self.cfg, self.device
         if state is not None or return_state:
             return self._generate_resume(x_seed, w, nsteps, seed, use_graph, z_prior, persistent, xhat_out, clamp,
@@ -820,6 +843,7 @@ class VaeGenerate:
         N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
         clamp = clamp_roll(clamp, N, nsteps, D, d)
         temper = temper_args(temperature, z_temperature)
+        binary_frames(x_seed=x_seed)
         f = dict(dtype=torch.float32, device=d)
         if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
             Xs = torch.zeros(N, nsteps, D, **f)
@@ -850,6 +874,8 @@ class VaeGenerate:
         if nsteps < 1:
             raise ValueError("nsteps must be >= 1, got %r" % (nsteps,))
         clamp = clamp_roll(clamp, N, nsteps, D, d)
+        if not state.binary:                   # a seed frame, from_numpy, built by hand: one reduction over both rows
+            binary_frames(**{'x_seed' if x_seed is not None else 'the state (x_in, hist)': state.rows})
         f = dict(dtype=torch.float32, device=d)
         Xs = torch.zeros(N, nsteps, D, **f)
         w = w.to(**f).contiguous()
@@ -857,13 +883,14 @@ class VaeGenerate:
             out = torch.empty(N, 2, D, **f) if return_state else None
             ops.vae_generate_resume(N, nsteps, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], z_prior, seed, w, *self._weights(),
                                     Xs, t0, state.rows, out, xhat=xhat_out, clamp=clamp, temper=temper)
-            return (Xs, GenState('cl_vae', None, t0 + nsteps, rows=out)) if return_state else Xs
+            return (Xs, GenState('cl_vae', None, t0 + nsteps, rows=out)._sampled()) if return_state else Xs
         chain = _Chain(_VaeRows(self, N), w, w, nsteps, seed, temper, 'enc_input', x_enc=state.x_in.clone(),
                        x_dec=state.hist.clone(), z_prior=z_prior, clamp=clamp, t0=t0)
         chain.run(nsteps, use_graph, lambda t: chain.store(t, Xs))
         if not return_state:
             return Xs
-        return Xs, GenState('cl_vae', None, t0 + nsteps, rows=torch.stack([chain.x_enc, chain.x_dec], 1).contiguous())
+        rows = torch.stack([chain.x_enc, chain.x_dec], 1).contiguous()
+        return Xs, GenState('cl_vae', None, t0 + nsteps, rows=rows)._sampled()
 
     def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
              z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
@@ -875,11 +902,14 @@ class VaeGenerate:
         ONE kernel, a workgroup per sequence (the VR instance of csrc/vae_generate.hip; any N); else the layer chain,
         captured once and replayed per frame (N <= batch size), reading its source frame through the device step counter.
         Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities; zout [3, N, T, L]
-         the latents (z_mean, z_log_var, z) of every frame."""
+         the latents (z_mean, z_log_var, z) of every frame.
+        Frames are read as on / off: ValueError (binary_frames) for sources or an x0 with an entry other than 0 and 1, on
+        both routes and before anything is launched."""
         cfg, d = self.cfg, self.device
         D, L = cfg['D'], cfg['L']
         temper = temper_args(temperature, z_temperature)
         sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, cfg['C'], d)
+        binary_frames(sources=sources, x0=x0)
         N, T = int(sources.shape[0]), int(sources.shape[1])
         Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
         if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
@@ -906,11 +936,14 @@ class VaeGenerate:
         (None: n), then the roll.  No eps is drawn.  persistent=True (default where the shapes allow): ONE kernel, a
         workgroup per sequence (the ZG instance of csrc/vae_generate.hip); else the layer chain, captured once and replayed
         per frame (N <= batch size), reading z[:, t] and history[:, t-1] through the device step counter.  Returns Xs
-        [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
+        [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities.
+        Frames are read as on / off: ValueError (binary_frames) for an x0 or a given history with an entry other than 0 and
+        1, on both routes and before anything is launched."""
         cfg, d = self.cfg, self.device
         D, L = cfg['D'], cfg['L']
         inv_T = decode_temper(temperature)
         z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, cfg['C'], d)
+        binary_frames(x0=x0, history=hist)
         N, T = int(z.shape[0]), int(z.shape[1])
         Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
         if max(N * T * L, N * T * D) >= 2 ** 32:

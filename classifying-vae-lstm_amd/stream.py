@@ -25,11 +25,16 @@ class Stream:
     """N pieces that go on where they stopped.  Stream(model, x_seeds, w, seed=0, z_prior=False) primes on the seed: cl_vrnn
     teacher-forces x_seeds [N, S, 88] (S = 0: a cold start) and keeps the bridge sample as the next input, cl_vae starts
     with x_seeds [N, 88] as the last frame and the one before it.  w [N, C] is the label until advance() replaces it.
+    temperature, z_temperature: those of the priming (cl_vrnn with seed frames: the latents of the seed steps and the bridge
+    sample are drawn under them, as one call draws them under its own).  A first advance() under other temperatures primes
+    again under its own, so that seed + first call is the one call whatever the constructor was given; a fork() taken before
+    it keeps the priming it was taken from.
     .t: the Philox step of the next frame; .state: the GenState (a call never writes it); .w: the current label."""
 
-    def __init__(self, model, x_seeds, w, seed=0, z_prior=False):
+    def __init__(self, model, x_seeds, w, seed=0, z_prior=False, temperature=1.0, z_temperature=1.0):
         self.kind, self._gen, zname = _family(model)
         self.model, self.seed, self._zkw = model, int(seed), {zname: bool(z_prior)}
+        self._pending = None            # cl_vrnn seed frames, their label and the priming's temperatures, until the first advance
         cfg, d = model.engine.cfg, model.engine.device
         self.w = np.asarray(w, np.float64)
         x = np.asarray(x_seeds)
@@ -40,9 +45,15 @@ class Stream:
         elif x.shape[1] == 0:
             self.state = GenState.fresh('cl_vrnn', cfg, d, N=x.shape[0])
         else:
-            _, self.state = self._gen(model, x, 0, self.w, seed=self.seed, return_state=True, **self._zkw)
+            self._pending = (x, self.w, (float(temperature), float(z_temperature)))
+            self._prime(temperature, z_temperature)
         if self.w.shape != (self.state.N, cfg['C']):
             raise ValueError("w must have shape %s, got %s" % ((self.state.N, cfg['C']), self.w.shape))
+
+    def _prime(self, temperature, z_temperature):
+        x, w0, _ = self._pending
+        _, self.state = self._gen(self.model, x, 0, w0, seed=self.seed, return_state=True, temperature=temperature,
+                                  z_temperature=z_temperature, **self._zkw)
 
     @property
     def t(self):
@@ -63,6 +74,10 @@ class Stream:
             if w.shape != self.w.shape:
                 raise ValueError("w must have shape %s, got %s" % (self.w.shape, w.shape))
             self.w = w
+        if self._pending is not None:
+            if self._pending[2] != (float(temperature), float(z_temperature)):
+                self._prime(temperature, z_temperature)
+            self._pending = None
         Xs, self.state = self._gen(self.model, None, int(nsteps), self.w, seed=self.seed, clamp=clamp,
                                    temperature=temperature, z_temperature=z_temperature, state=self.state,
                                    return_state=True, **self._zkw)
@@ -74,6 +89,7 @@ class Stream:
         an unchanged fork continues like the original."""
         other = object.__new__(Stream)
         other.__dict__.update(self.__dict__)
+        other._pending = None
         if index is None:
             other.state, other.w = self.state.clone(), self.w.copy()
         else:
@@ -111,7 +127,7 @@ def modulate(model, x_seeds, plan, seed=0, **temper):
     temper_args(temper.get('temperature', 1.0), temper.get('z_temperature', 1.0))
     N = np.asarray(x_seeds).shape[0]
     plan = check_plan(plan, N, model.engine.cfg['C'])
-    s = Stream(model, x_seeds, plan[0][0], seed=seed)
+    s = Stream(model, x_seeds, plan[0][0], seed=seed, **temper)
     return np.concatenate([s.advance(n, w=w, **temper) for w, n in plan], axis=1)
 
 
@@ -135,7 +151,7 @@ def generate_chunked(model, x_seeds, nsteps, w, chunk=None, changes=(), seed=0, 
     if any(not 0 < f < nsteps for f in frames) or any(b <= a for a, b in zip(frames, frames[1:])):
         raise ValueError("the frames of the changes must be strictly increasing, > 0 and < %d, got %s" % (nsteps, frames))
     new_w = dict((int(f), wv) for f, wv in changes)
-    s = Stream(model, x_seeds, w, seed=seed, z_prior=z_prior)
+    s = Stream(model, x_seeds, w, seed=seed, z_prior=z_prior, **temper)
     out = []
     for a, b in chunk_bounds(nsteps, chunk, frames):
         out.append(s.advance(b - a, w=new_w.get(a), clamp=None if clamp is None else clamp[:, a:b], **temper))

@@ -457,7 +457,12 @@ int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H, int L, int
  * index n*L+l), u = the clv_philox_uniform value for (seed, step t, stream 1, index n*D+j).  Kernels in Keras layout:
  * Kh = h/kernel [D+C,H] (frame rows, label rows), Kz = the fused head [H,2L], Kd = decoder_h/kernel [C+(D)+L,H]
  * (label rows, history rows, latent rows), Ko = x_decoded_mean/kernel [H,D].  Xs [N,nsteps,D]; xhat (optional) the
- * probabilities.  clv_vae_generate_supported: D == H == 88, L <= 32, C <= 32 (models with hidden layers). */
+ * probabilities.  clv_vae_generate_supported: D == H == 88, L <= 32, C <= 32 (models with hidden layers).
+ * FRAMES ARE READ AS ON / OFF by all seven clv_vae_* entry points below: a frame that comes in (x_seed, sources, x0, history,
+ * both rows of state_in) contributes the kernel row of every note whose entry is not 0, unweighted; an entry other than 0 or
+ * 1 is the caller's error (the host cannot see device memory: the Python layer refuses such frames, engine_generate.
+ * binary_frames, so that this kernel and the per-frame chain, which multiplies by the value, stay the same sampler).  The
+ * clv_vrnn_* entry points multiply by the value. */
 int clv_vae_generate_supported(int D, int H, int L, int C);
 int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
                      const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
@@ -465,7 +470,7 @@ int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_pr
                      float* Xs, float* xhat, void* stream);
 /* ... under a constraint roll clamp [N,nsteps,D] uint8 (encoding as clv_vrnn_generate_clamped): row t constrains frame t,
  * which is then the next input (and the decoder's history one frame later).  xhat keeps the model's own probabilities; an
- * all-free roll gives bit for bit the frames of clv_vae_generate.  clamp != NULL. */
+ * all-free roll gives bit for bit the frames of clv_vae_generate.  clamp != NULL.  Frames are read as on / off. */
 int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
                              const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
                              const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
@@ -486,6 +491,7 @@ int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H, int L, in
                                const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                                const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                                float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream);
+/* cl_vae: frames are read as on / off (x_seed; see clv_vae_generate). */
 int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
                               const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
                               const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
@@ -515,6 +521,7 @@ int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_act, int hi
                   const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                   const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                   float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream);
+/* cl_vae: frames are read as on / off (sources and x0; see clv_vae_generate). */
 int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
                  const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
                  const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
@@ -536,6 +543,7 @@ int clv_vrnn_vary_latents(int N, int T, int D, int H, int L, int C, int gate_act
                           const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                           const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                           float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout, void* stream);
+/* cl_vae: frames are read as on / off (sources and x0; see clv_vae_generate). */
 int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
                          const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
                          const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
@@ -555,6 +563,7 @@ int clv_vrnn_decode(int N, int T, int D, int H, int L, int C, int gate_act, uint
                     const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                     const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                     float inv_temperature, float* Xs, float* xhat, void* stream);
+/* cl_vae: frames are read as on / off (x0 and history; see clv_vae_generate). */
 int clv_vae_decode(int N, int T, int D, int H, int L, int C, int use_x_prev, uint64_t seed, const float* z_in,
                    const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
                    const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
@@ -581,6 +590,7 @@ int clv_vrnn_generate_resume(int N, int S, int nsteps, int D, int H, int L, int 
                              const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                              float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
                              float* state_out, float* Xs, float* xhat, void* stream);
+/* cl_vae: frames are read as on / off (both rows of state_in; see clv_vae_generate). */
 int clv_vae_generate_resume(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
                             const float* w, const float* Kh, const float* bh, const float* Kz, const float* bz,
                             const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,

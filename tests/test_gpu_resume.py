@@ -516,3 +516,31 @@ def test_sample_tools_in_chunks_and_modulated(dev, tmp_path, which):
     assert changed >= 3             # every pick changes under at least one of the two keys: one of them is not its own
     with pytest.raises(ValueError):
         run('mod_bad', ['--modulate', 'no such key@5'])
+
+
+# --------------------------------------------------------------------------- chunks under a temperature, seed frames
+@pytest.mark.parametrize("temper", [dict(temperature=0.5), dict(temperature=2.0, z_temperature=0.5)],
+                         ids=lambda t: ','.join('%s=%s' % kv for kv in t.items()))
+def test_chunks_and_modulation_prime_under_the_runs_temperatures(dev, temper):
+    """12. cl_vrnn with seed frames: one call draws the latents of the seed steps and the bridge sample under its own
+    temperatures, so a Stream has to prime under them too.  64 pieces: with the priming at temperature 1 some bridge draw of
+    the 64 x 88 falls between the two probabilities (the reference: 100 or more of them differ), and the pieces part."""
+    from clvae_amd.stream import Stream, generate_chunked, modulate
+    model, M, p = _case_model(dev, 'cl_vrnn')
+    c, N, nsteps, seed = TR.VRNN_CASE, 64, 7, 23
+    rng = np.random.default_rng(12)
+    seeds = (rng.random((N, c['S'], D)) < 0.06).astype(np.float64)
+    w = np.eye(c['C'])[rng.integers(0, c['C'], N)]
+    # the condition on the inputs: the bridge under the run's temperatures is not the bridge at temperature 1
+    bridge = lambda **t: TR.vrnn_generate(p, seeds, w, 1, seed, c['L'], **t)[1][:, c['S'] - 1]
+    u = TR._noise(N, c['L'], seed, c['S'] - 1, np.float64)[1]
+    cold, warm = bridge(), bridge(T=temper['temperature'], Tz=temper.get('z_temperature', 1.0))
+    assert ((u <= cold) != (u <= warm)).sum() >= 100
+    whole = M.generate_samples_device(model, seeds, nsteps, w, seed=seed, **temper)
+    assert np.array_equal(generate_chunked(model, seeds, nsteps, w, chunk=3, seed=seed, **temper), whole)
+    assert np.array_equal(modulate(model, seeds, [(w, 4), (w, 3)], seed=seed, **temper), whole)
+    # a Stream built without them primes again at its first advance; a fork taken before keeps the first priming
+    s = Stream(model, seeds, w, seed=seed)
+    f = s.fork()
+    assert np.array_equal(np.concatenate([s.advance(4, **temper), s.advance(3, **temper)], 1), whole)
+    assert not np.array_equal(f.advance(7, **temper), whole)

@@ -240,3 +240,23 @@ def test_flag_rules(which, capsys):
         assert S.on_device(parser.parse_args(['r', '--morph', '2'])) and not S.on_device(parser.parse_args(['r']))
     src = open(S.__file__).read()
     assert 'MORPH_FLAGS' in src.split("if __name__ == '__main__':")[1]
+
+
+# ------------------------------------------------------------------------------ cl_vae: frames are read as on / off
+class _VaeHost(VaeGenerate):
+    """the cl_vae sampling mixin without a device: its refusals come before its first launch"""
+    cfg = dict(D=D, C=4, L=2, H=88, T=8, use_x_prev=True)
+    device = 'cpu'
+
+
+def test_cl_vae_decode_refuses_frames_that_are_not_binary():
+    z, w = np.zeros((2, 3, 2)), np.eye(4)[[0, 1]]
+    for entry in (0.5, 2.0, float('nan')):
+        x0, hist = np.zeros((2, D)), np.zeros((2, 3, D))
+        x0[1, 0] = entry
+        hist[0, 2, 63] = entry
+        for persistent in (True, False):
+            with pytest.raises(ValueError, match='on/off'):
+                _VaeHost().decode_latents(z, w, x0=x0, persistent=persistent)
+            with pytest.raises(ValueError, match='on/off'):
+                _VaeHost().decode_latents(z, w, history=hist, persistent=persistent)

@@ -309,3 +309,35 @@ def test_plan_validation():
         ST.modulate(_Model('cl_vrnn'), np.zeros((2, 1, D)), [(w, 0)])
     with pytest.raises(ValueError):
         ST.Stream(type('M', (), {'engine': object()})(), np.zeros((2, 1, D)), w)              # neither family's model
+
+
+# ------------------------------------------------------------------------------ cl_vae: frames are read as on / off
+class _VaeHost(VaeGenerate):
+    """the cl_vae sampling mixin without a device: its refusals come before its first launch"""
+    cfg = dict(D=D, C=4, L=2, H=88, T=8, use_x_prev=True)
+    device = 'cpu'
+
+
+def test_cl_vae_generate_refuses_frames_that_are_not_binary():
+    w = torch.eye(4)[[0, 1]]
+    good = torch.zeros(2, D)
+    good[0, 5] = 1.0
+    for entry in (0.5, 2.0, float('nan')):
+        bad = good.clone()
+        bad[1, 64] = entry
+        by_hand = GenState('cl_vae', dict(x_in=good, hist=bad), 3)
+        loaded = GenState.from_numpy(dict(x_in=bad.numpy(), hist=good.numpy(), t=np.int64(3)), 'cpu')
+        for persistent in (True, False):
+            kw = dict(persistent=persistent)
+            with pytest.raises(ValueError, match='on/off'):
+                _VaeHost().generate(bad, w, 4, **kw)
+            with pytest.raises(ValueError, match='on/off'):
+                _VaeHost().generate(bad, w, 4, return_state=True, **kw)
+            for state in (by_hand, loaded, by_hand.clone(), loaded.select([1, 1]), GenState.fresh('cl_vae', _VaeHost.cfg, 'cpu', seed_frame=bad)):
+                assert not state.binary
+                with pytest.raises(ValueError, match='on/off'):
+                    _VaeHost().generate(None, w, 4, state=state, **kw)
+    # what a sampler returns is marked, and its copies and selections with it: those rows are not read again
+    st = GenState('cl_vae', dict(x_in=good, hist=good), 3)._sampled()
+    assert st.binary and st.clone().binary and st.select([0, 0]).binary
+    assert not GenState.from_numpy(st.to_numpy(), 'cpu').binary

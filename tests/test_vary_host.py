@@ -192,3 +192,26 @@ def test_flag_rules(which, capsys):
         assert S.on_device(parser.parse_args(['r', '--vary'])) and not S.on_device(parser.parse_args(['r']))
     src = open(S.__file__).read()
     assert 'VARY_FLAGS' in src.split("if __name__ == '__main__':")[1]
+
+
+# ------------------------------------------------------------------------------ cl_vae: frames are read as on / off
+class _VaeHost(VaeGenerate):
+    """the cl_vae sampling mixin without a device: its refusals come before its first launch"""
+    cfg = dict(D=D, C=4, L=2, H=88, T=8, use_x_prev=True)
+    device = 'cpu'
+
+
+def test_cl_vae_vary_refuses_frames_that_are_not_binary():
+    from clvae_amd.engine_generate import binary_frames
+    w = np.eye(4)[[0, 1]]
+    for entry in (0.5, 2.0, -1.0, float('nan')):
+        src, x0 = np.zeros((2, 3, D)), np.zeros((2, D))
+        src[1, 2, 64] = entry
+        with pytest.raises(ValueError, match='on/off'):
+            _VaeHost().vary(src, w)
+        with pytest.raises(ValueError, match='on/off'):
+            _VaeHost().vary(src, w, persistent=False)
+        x0[0, 87] = entry
+        with pytest.raises(ValueError, match='on/off'):
+            _VaeHost().vary(np.zeros((2, 3, D)), w, x0=x0, history='source')
+    binary_frames(sources=torch.tensor([[0.0, 1.0, 1.0]]), x0=None)              # 0 and 1 pass, an absent frame passes
