@@ -201,7 +201,17 @@ def vary_args(sources, w_enc, w_dec, x0, history, clamp, D, C, device):
 
 
 STATE_FIELDS = {'cl_vrnn': ('h_enc', 'c_enc', 'h_dec', 'c_dec', 'x'), 'cl_vae': ('x_in', 'hist')}
+# what else the host drivers know of a family.  Its seed: cl_vrnn steps through S >= 0 teacher-forced frames [N, S, D] from
+# zero LSTM states; cl_vae's one frame [N, D] IS its state (x_in = hist = the frame) and takes no step, S = 0.  Its state
+# fields that are H wide (the LSTM states); every other field is a frame, D wide.
+SEED_RANK = {'cl_vrnn': 3, 'cl_vae': 2}
+LSTM_FIELDS = {'cl_vrnn': ('h_enc', 'c_enc', 'h_dec', 'c_dec'), 'cl_vae': ()}
 STEP_MAX = 2 ** 32 - 1                  # the Philox step is a uint32
+
+
+def seed_steps(kind, x_seed):
+    """S, the steps a sampler spends on its seed frames"""
+    return int(x_seed.shape[1]) if SEED_RANK[kind] == 3 else 0
 
 
 class GenState:
@@ -242,12 +252,12 @@ class GenState:
         """the state a sampler starts from: cl_vrnn zero LSTM states and the zero frame for N sequences; cl_vae x_in = hist =
         seed_frame [N, D]; t = 0"""
         f = dict(dtype=torch.float32, device=device)
-        if kind == 'cl_vae':
+        if SEED_RANK[kind] == 2:
             x = device_f32(seed_frame, device)
             if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != cfg['D']:
                 raise ValueError("seed_frame must be [N, %d] with N >= 1, got shape %s" % (cfg['D'], tuple(x.shape)))
             return cls(kind, None, 0, rows=torch.stack([x, x], 1).contiguous())
-        return cls(kind, {k: torch.zeros(int(N), cfg['D'] if k == 'x' else cfg['H'], **f) for k in STATE_FIELDS[kind]}, 0)
+        return cls(kind, {k: torch.zeros(int(N), n, **f) for k, n in state_widths(kind, cfg).items()}, 0)
 
     @property
     def N(self):
@@ -341,7 +351,7 @@ def resume_args(state, kind, N, widths, nframes):
 
 
 def state_widths(kind, cfg):
-    return {k: cfg['H'] if k[0] in 'hc' and kind == 'cl_vrnn' else cfg['D'] for k in STATE_FIELDS[kind]}
+    return {k: cfg['H'] if k in LSTM_FIELDS[kind] else cfg['D'] for k in STATE_FIELDS[kind]}
 
 
 def generate_samples_numpy(engine, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
@@ -385,21 +395,21 @@ def _resume_samples_numpy(engine, kind, x_seeds, nsteps, w_vals, seed, z_prior, 
         raise ValueError("give w_vals")
     if state is not None and not isinstance(state, GenState):
         raise ValueError("state must be a GenState, got %r" % type(state).__name__)
-    if kind == 'cl_vae' and state is not None and x_seeds is not None:
+    rank = SEED_RANK[kind]
+    if rank == 2 and state is not None and x_seeds is not None:
         raise ValueError("a cl_vae state holds its last two frames: give no x_seeds with it")
     if x_seeds is None:
         if state is None:
             raise ValueError("give x_seeds or a state")
         N = state.N
-        xs = torch.zeros(N, 0, cfg['D'], dtype=torch.float32, device=d) if kind == 'cl_vrnn' else None
+        xs = torch.zeros(N, 0, cfg['D'], dtype=torch.float32, device=d) if rank == 3 else None
     else:
         xs = device_f32(x_seeds, d)
-        if xs.dim() != (3 if kind == 'cl_vrnn' else 2) or xs.shape[0] < 1 or xs.shape[-1] != cfg['D']:
-            raise ValueError("x_seeds must be %s, got shape %s" % ("[N, S, %d]" % cfg['D'] if kind == 'cl_vrnn'
-                                                                    else "[N, %d]" % cfg['D'], tuple(xs.shape)))
+        if xs.dim() != rank or xs.shape[0] < 1 or xs.shape[-1] != cfg['D']:
+            raise ValueError("x_seeds must be %s, got shape %s" % (("[N, S, %d]" if rank == 3 else "[N, %d]") % cfg['D'],
+                                                                    tuple(xs.shape)))
         N = int(xs.shape[0])
-    S = int(xs.shape[1]) if kind == 'cl_vrnn' else 0
-    resume_args(state, kind, N, state_widths(kind, cfg), S + int(nsteps))
+    resume_args(state, kind, N, state_widths(kind, cfg), seed_steps(kind, xs) + int(nsteps))
     w = device_f32(w_vals, d)
     if tuple(w.shape) != (N, cfg['C']):
         raise ValueError("w_vals must have shape %s, got %s" % ((N, cfg['C']), tuple(w.shape)))
@@ -624,31 +634,6 @@ def _smc_drive(chunks, run_chunk, N, nsteps, D, n_out, device, C=None):
     return out
 
 
-def _smc_run(eng, S, cap, chain_of, x_seed, w, nsteps, clamp, particles, resample_threshold, n_out, seed, use_graph, chunk,
-             w_prior):
-    """generate_smc of both families: S seed steps, at most cap rows per chunk; chain_of(xs, wr, r0, smc) is the family's
-    frame chain over the chunk's particle rows (seeds xs and labels wr per row, r0 the first global row)"""
-    cfg, d = eng.cfg, eng.device
-    N, D = int(x_seed.shape[0]), cfg['D']
-    clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
-    P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
-    x_seed = x_seed.to(dtype=torch.float32, device=d)
-    w, prior = smc_label_args(w, w_prior, N, cfg['C'], d)
-
-    def run_chunk(m0, m1):
-        if prior is None:
-            wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
-        else:
-            wr = torch.zeros((m1 - m0) * P, cfg['C'], dtype=torch.float32, device=d)
-            prior.init_rows(m0, m1, P, seed, wr)
-        smc = _Smc(m1 - m0, P, nsteps, S, D, tau, seed, m0, clamp[m0:m1], d, wr=None if prior is None else wr)
-        chain_of(x_seed[m0:m1].repeat_interleave(P, 0), wr, m0 * P, smc).run(S + nsteps, use_graph)
-        return smc
-
-    return _smc_drive(_smc_chunks(N, P, cap, chunk), run_chunk, N, nsteps, D, int(n_out), d,
-                      C=None if prior is None else cfg['C'])
-
-
 def _zout_ok(zout, N, T, L):
     """the latents' output of vary: a contiguous float32 device tensor [3, N, T, L]"""
     if tuple(zout.shape) != (3, N, T, L) or zout.dtype != torch.float32 or not zout.is_contiguous():
@@ -712,7 +697,7 @@ class _VrnnRows:
 
     def carried(self, x_enc, x_next):
         """what a particle hands to its descendants: both LSTM states and its sample"""
-        return [self.st[k] for k in ('h_enc', 'c_enc', 'h_dec', 'c_dec')] + [x_next]
+        return [self.st[k] for k in LSTM_FIELDS['cl_vrnn']] + [x_next]
 
 
 class _Chain:
@@ -808,8 +793,146 @@ class _Chain:
             zout[2, :, j].copy_(rows.z[:R])
 
 
-class VaeGenerate:
+class _Generate:
+    """vary, decode_latents and generate_smc of both families, each written once.  What differs a family states itself
+    (VaeGenerate, VrnnGenerate below) and the bodies here only ask for it:
+    STATE_KIND                  its key in STATE_FIELDS, SEED_RANK, LSTM_FIELDS
+    ROWS                        the rows of a frame chain: _VaeRows (at most the batch size) / _VrnnRows (any number)
+    _persistent_ok()            do the model's shapes have a persistent kernel (reads cfg only)
+    _family_flag()              the int after C in every persistent entry: use_x_prev / the gate activation
+    _check_frames(**frames)     cl_vae reads frames as on / off: binary_frames; cl_vrnn takes any float: nothing
+    _vary_fits(clamp, T, zout)  does a re-decoding fit the persistent kernel's 32-bit addressing
+    _smc_seed(xs), _smc_cap()   how the filter's chain holds its seed rows xs; the most rows of a chunk (None: any)
+    _vary_op, _decode_op        ops.vae_* / ops.vrnn_*: vary_latents (without a zout it IS the family's vary) and decode
+    _weights(encoder=True)      the weight arguments of those, in their order
+    Every refusal (ValueError) comes before the first launch and before anything of the engine but cfg and device is read."""
+
+    def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
+             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
+        """Re-decode sources [N, T, D] (DESIGN.md 14): per frame t the encoder on [sources[t], w_enc] (cl_vae: the z-encoder;
+        cl_vrnn: the encoder step, from zero LSTM states), z = mean + exp(lv / 2) * Tz * eps, the decoder on [w_dec, xp, z]
+        with xp the frame directly before t as in training: x0 (None: zeros) at t = 0, then the sample of frame t-1
+        (history='own') or sources[t-1] ('source': the training forward pass; no effect without use_x_prev);
+        x ~ Bernoulli(x_hat), then the roll clamp [N, T, D] (row t constrains frame t; no bridge).  w_dec=None: w_enc (a
+        variation); another label: key transfer.  Noise as generate's (step = frame; cl_vrnn: with S = 0).  persistent=True
+        (default where the shapes allow): ONE kernel, a workgroup per sequence (the VR instances of csrc/vae_generate.hip /
+        csrc/generate.hip; any N); else the frame chain, captured once and replayed per frame (cl_vae: N <= batch size),
+        reading its source frame through the device step counter.  cl_vrnn's kernel addresses in 32 bits: a roll of 2^32
+        bytes or more, T * D * 4 >= 2^32 or a zout of 3 * 2^32 entries or more takes the chain.  Returns Xs [N, T, D];
+        xhat_out [N, T, D] receives the unclamped (tempered) probabilities; zout [3, N, T, L] the latents
+        (z_mean, z_log_var, z) of every frame.
+        cl_vae reads frames as on / off: ValueError (binary_frames) for sources or an x0 with an entry other than 0 and 1,
+        on both routes and before anything is launched.  cl_vrnn takes any float."""
+        cfg, d = self.cfg, self.device
+        D, L = cfg['D'], cfg['L']
+        temper = temper_args(temperature, z_temperature)
+        sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, cfg['C'], d)
+        self._check_frames(sources=sources, x0=x0)
+        N, T = int(sources.shape[0]), int(sources.shape[1])
+        if zout is not None:
+            _zout_ok(zout, N, T, L)
+        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
+        if persistent and self._vary_fits(clamp, T, zout) and self._persistent_ok():
+            self._vary_op(N, T, D, cfg['H'], L, cfg['C'], self._family_flag(), hist_source, seed, sources, x0, w_enc, w_dec,
+                          *self._weights(), Xs, zout, xhat_out, clamp=clamp, temper=temper)
+            return Xs
+        chain = _Chain(self.ROWS(self, N), w_enc, w_dec, T, seed, temper, 'enc_input' if hist_source else 'sample',
+                       x_dec=None if x0 is None else x0.clone(), sources=sources, clamp=clamp)
+        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out, zout))
+        return Xs
+
+    def decode_latents(self, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
+               persistent=True, use_graph=True, xhat_out=None):
+        """Decode the latent path z [N, T, L]: vary's loop without its encoder.  Per frame t (cl_vrnn: from
+        zero LSTM state) the decoder on [w_dec, xp, z[:, t]] with xp = x0 (None: zeros) at t = 0, then the sample of frame
+        t-1 (history='own') or history[:, t-1] (an [N, T, D] array: teacher forcing; no effect without use_x_prev);
+        x ~ Bernoulli(x_hat) with the uniforms of row noise_rows[n] (None: n), then the roll clamp [N, T, D].  No eps is
+        drawn.  persistent=True (default where the shapes allow): ONE kernel, a workgroup per sequence (the ZG instances of
+        csrc/vae_generate.hip / csrc/generate.hip); else the frame chain, captured once and replayed per frame (cl_vae:
+        N <= batch size), reading z[:, t] and history[:, t-1] through the device step counter.  N*T*L or N*T*D of 2^32 or
+        more takes the chain.  Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities.
+        cl_vae reads frames as on / off: ValueError (binary_frames) for an x0 or a given history with an entry other than
+        0 and 1, on both routes and before anything is launched.  cl_vrnn takes any float."""
+        cfg, d = self.cfg, self.device
+        D, L = cfg['D'], cfg['L']
+        inv_T = decode_temper(temperature)
+        z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, cfg['C'], d)
+        self._check_frames(x0=x0, history=hist)
+        N, T = int(z.shape[0]), int(z.shape[1])
+        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
+        if persistent and max(N * T * L, N * T * D) < 2 ** 32 and self._persistent_ok():
+            self._decode_op(N, T, D, cfg['H'], L, cfg['C'], self._family_flag(), seed, z, x0, hist, w_dec, noise_rows,
+                            *self._weights(encoder=False), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
+            return Xs
+        chain = _Chain(self.ROWS(self, N), None, w_dec, T, seed, None if inv_T == 1.0 else (inv_T, 1.0),
+                       'sample' if hist is None else hist, x_dec=None if x0 is None else x0.clone(), z_path=z,
+                       noise_rows=noise_rows, clamp=clamp)
+        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out))
+        return Xs
+
+    def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
+                     z_prior=False, chunk=None, w_prior=None, temperature=1.0, z_temperature=1.0):
+        """Particle-filter sampling under the constraint roll clamp [N, nsteps, D] (DESIGN.md 11): melody m runs P =
+        `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
+        probability of each returned frame's clamped notes and resampled (systematic, below an ESS of
+        resample_threshold * P).  x_seed, w [N, C] device tensors.  cl_vae: x_seed [N, D], row t of the roll constrains
+        frame t, and a chunk holds at most batch-size rows.  cl_vrnn: x_seed [N, S, D], row j of the roll constrains the
+        sample of step S+j; the seed steps and the bridge carry no constraint and no weight; a chunk holds any number of
+        rows.  `chunk`: at most that many melodies per pass; the Philox keys follow the global row, so the result does not
+        depend on the chunking.  Returns SmcResult (Xs [N, n_out, nsteps, D]).
+        w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state (cl_vrnn's seed
+        steps run under it too, unweighted), so the filter targets p(w, free notes | seed, constraints) (DESIGN.md 12);
+        returns SmcKeyResult.
+        temperature, z_temperature (temper_args, DESIGN.md 13): the filter runs on the TEMPERED model; its weights are the
+        tempered probabilities of the clamped notes, so log_evidence estimates log p_T(constraints | seed, w), the evidence
+        under the tempered model -- the trained model's only where both are 1."""
+        cfg, d = self.cfg, self.device
+        temper = temper_args(temperature, z_temperature)
+        N, D = int(x_seed.shape[0]), cfg['D']
+        clamp = smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, d)
+        P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
+        x_seed = x_seed.to(dtype=torch.float32, device=d)
+        w, prior = smc_label_args(w, w_prior, N, cfg['C'], d)
+        S = seed_steps(self.STATE_KIND, x_seed)
+
+        def run_chunk(m0, m1):
+            if prior is None:
+                wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+            else:
+                wr = torch.zeros((m1 - m0) * P, cfg['C'], dtype=torch.float32, device=d)
+                prior.init_rows(m0, m1, P, seed, wr)
+            smc = _Smc(m1 - m0, P, nsteps, S, D, tau, seed, m0, clamp[m0:m1], d, wr=None if prior is None else wr)
+            xs = x_seed[m0:m1].repeat_interleave(P, 0)          # seeds and labels per particle row, m0 * P the first global row
+            _Chain(self.ROWS(self, smc.R), wr, wr, nsteps, seed, temper, z_prior=z_prior, r0=m0 * P, smc=smc,
+                   **self._smc_seed(xs)).run(S + nsteps, use_graph)
+            return smc
+
+        return _smc_drive(_smc_chunks(N, P, self._smc_cap(), chunk), run_chunk, N, nsteps, D, int(n_out), d,
+                          C=None if prior is None else cfg['C'])
+
+
+class VaeGenerate(_Generate):
     STATE_KIND = 'cl_vae'
+    ROWS = _VaeRows
+    _check_frames = staticmethod(binary_frames)
+    _vary_op, _decode_op = staticmethod(ops.vae_vary_latents), staticmethod(ops.vae_decode)
+
+    def _persistent_ok(self):
+        cfg = self.cfg
+        return cfg['H'] > 0 and ops.vae_generate_supported(cfg['D'], cfg['H'], cfg['L'], cfg['C'])
+
+    def _family_flag(self):
+        return self.cfg['use_x_prev']
+
+    def _vary_fits(self, clamp, T, zout):
+        return True
+
+    def _smc_seed(self, xs):
+        """the seed frame is both the encoder's input and the decoder's previous frame of step 0"""
+        return dict(dec_prev='enc_input', x_enc=xs, x_dec=xs.clone())
+
+    def _smc_cap(self):
+        return self.B
 
     def _weights(self, encoder=True):
         """the persistent kernels' weight arguments in the order ops.vae_* take them: the encoder half (vae_decode takes
@@ -833,156 +956,82 @@ class VaeGenerate:
         state, return_state: continue from a GenState (x_seed is then None: the state holds the last two
         frames) with the Philox steps counted on from state.t, and / or return (Xs, GenState after the last frame).  A
         piece generated in several such calls is bit for bit the piece of one call; the state is the same on both routes
-        and is not written.  Neither given (default): exactly the launches above.
+        and is not written.  Neither given (default): exactly the launches above -- the plain, clamped or tempered entry;
+        with either, the ST instance behind vae_generate_resume.
         Frames are read as on / off: ValueError (binary_frames) for an x_seed, or a state not returned by a sampler, with
         an entry other than 0 and 1, on both routes and before anything is launched."""
         cfg, d = self.cfg, self.device
-        if state is not None or return_state:
-            return self._generate_resume(x_seed, w, nsteps, seed, use_graph, z_prior, persistent, xhat_out, clamp,
-                                         temper_args(temperature, z_temperature), state, return_state)
-        N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
-        clamp = clamp_roll(clamp, N, nsteps, D, d)
-        temper = temper_args(temperature, z_temperature)
-        binary_frames(x_seed=x_seed)
-        f = dict(dtype=torch.float32, device=d)
-        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
-            Xs = torch.zeros(N, nsteps, D, **f)
-            ops.vae_generate(N, nsteps, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], z_prior, seed,
-                             x_seed.to(**f).contiguous(), w.to(**f).contiguous(), *self._weights(), Xs, xhat_out, clamp=clamp,
-                             temper=temper)
+        D, f = cfg['D'], dict(dtype=torch.float32, device=d)
+        resume = state is not None or return_state
+        if resume:
+            temper, nsteps = temper_args(temperature, z_temperature), int(nsteps)
+            if state is None:
+                state = GenState.fresh('cl_vae', cfg, d, seed_frame=x_seed)
+            elif x_seed is not None:
+                raise ValueError("a cl_vae state holds its last two frames: give no x_seed with it")
+            N = int(w.shape[0])
+            t0 = resume_args(state, 'cl_vae', N, state_widths('cl_vae', cfg), nsteps)
+            if nsteps < 1:
+                raise ValueError("nsteps must be >= 1, got %r" % (nsteps,))
+            clamp = clamp_roll(clamp, N, nsteps, D, d)
+            if not state.binary:                   # a seed frame, from_numpy, built by hand: one reduction over both rows
+                binary_frames(**{'x_seed' if x_seed is not None else 'the state (x_in, hist)': state.rows})
+            x_in, hist = state.x_in, state.hist
+        else:
+            N, t0 = int(x_seed.shape[0]), 0
+            clamp = clamp_roll(clamp, N, nsteps, D, d)
+            temper = temper_args(temperature, z_temperature)
+            binary_frames(x_seed=x_seed)
+            x_in = hist = x_seed.to(**f).contiguous()
+        w = w.to(**f).contiguous()
+        if not (persistent and self._persistent_ok()):
+            return self._generate_frames(x_in, hist, w, nsteps, seed, use_graph, z_prior, clamp, temper, t0, return_state)
+        Xs = torch.zeros(N, nsteps, D, **f)
+        head = (N, nsteps, D, cfg['H'], cfg['L'], cfg['C'], cfg['use_x_prev'], z_prior, seed)
+        if not resume:
+            ops.vae_generate(*head, x_in, w, *self._weights(), Xs, xhat_out, clamp=clamp, temper=temper)
             return Xs
-        rows = _VaeRows(self, N)
-        Xs = torch.zeros(N, nsteps, D, **f)
-        w = w.to(**f).contiguous()
-        chain = _Chain(rows, w, w, nsteps, seed, temper, 'enc_input', x_enc=x_seed.to(**f).clone(),
-                       x_dec=x_seed.to(**f).clone(), z_prior=z_prior, clamp=clamp)
-        chain.run(nsteps, use_graph, lambda t: chain.store(t, Xs))
-        return Xs
+        out = torch.empty(N, 2, D, **f) if return_state else None
+        ops.vae_generate_resume(*head, w, *self._weights(), Xs, t0, state.rows, out, xhat=xhat_out, clamp=clamp, temper=temper)
+        return (Xs, GenState('cl_vae', None, t0 + nsteps, rows=out)._sampled()) if return_state else Xs
 
-    def _generate_resume(self, x_seed, w, nsteps, seed, use_graph, z_prior, persistent, xhat_out, clamp, temper, state,
-                         return_state):
-        """generate from a state (None: x_in = hist = x_seed, t = 0) and / or to one: the ST instance of the persistent
-        kernel, or the frame chain started from the state's two frames"""
-        cfg, d = self.cfg, self.device
-        D, L, nsteps = cfg['D'], cfg['L'], int(nsteps)
-        if state is None:
-            state = GenState.fresh('cl_vae', cfg, d, seed_frame=x_seed)
-        elif x_seed is not None:
-            raise ValueError("a cl_vae state holds its last two frames: give no x_seed with it")
-        N = int(w.shape[0])
-        t0 = resume_args(state, 'cl_vae', N, state_widths('cl_vae', cfg), nsteps)
-        if nsteps < 1:
-            raise ValueError("nsteps must be >= 1, got %r" % (nsteps,))
-        clamp = clamp_roll(clamp, N, nsteps, D, d)
-        if not state.binary:                   # a seed frame, from_numpy, built by hand: one reduction over both rows
-            binary_frames(**{'x_seed' if x_seed is not None else 'the state (x_in, hist)': state.rows})
-        f = dict(dtype=torch.float32, device=d)
-        Xs = torch.zeros(N, nsteps, D, **f)
-        w = w.to(**f).contiguous()
-        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
-            out = torch.empty(N, 2, D, **f) if return_state else None
-            ops.vae_generate_resume(N, nsteps, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], z_prior, seed, w, *self._weights(),
-                                    Xs, t0, state.rows, out, xhat=xhat_out, clamp=clamp, temper=temper)
-            return (Xs, GenState('cl_vae', None, t0 + nsteps, rows=out)._sampled()) if return_state else Xs
-        chain = _Chain(_VaeRows(self, N), w, w, nsteps, seed, temper, 'enc_input', x_enc=state.x_in.clone(),
-                       x_dec=state.hist.clone(), z_prior=z_prior, clamp=clamp, t0=t0)
+    def _generate_frames(self, x_in, hist, w, nsteps, seed, use_graph, z_prior, clamp, temper, t0=0, return_state=False):
+        """generate on the frame chain, started from the last frame x_in and the one before it, hist (a fresh start: the seed
+        frame twice, t0 = 0); with return_state the two frames it ends on go back as a state"""
+        Xs = torch.zeros(w.shape[0], nsteps, self.cfg['D'], dtype=torch.float32, device=self.device)
+        chain = _Chain(_VaeRows(self, int(w.shape[0])), w, w, nsteps, seed, temper, 'enc_input', x_enc=x_in.clone(),
+                       x_dec=hist.clone(), z_prior=z_prior, clamp=clamp, t0=t0)
         chain.run(nsteps, use_graph, lambda t: chain.store(t, Xs))
         if not return_state:
             return Xs
         rows = torch.stack([chain.x_enc, chain.x_dec], 1).contiguous()
         return Xs, GenState('cl_vae', None, t0 + nsteps, rows=rows)._sampled()
 
-    def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
-             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
-        """Re-decode sources [N, T, D]: per frame t the z-encoder on [sources[t], w_enc], z = mean +
-        exp(lv / 2) * Tz * eps, the decoder on [w_dec, xp, z] with xp the frame directly before t as in training: x0 (None:
-        zeros) at t = 0, then the sample of frame t-1 (history='own') or sources[t-1] ('source': the training forward pass);
-        x ~ Bernoulli(x_hat), then the roll clamp [N, T, D] (row t constrains frame t).  w_dec=None: w_enc (a variation);
-        another label: key transfer.  Noise as generate's (step = frame).  persistent=True (default where the shapes allow):
-        ONE kernel, a workgroup per sequence (the VR instance of csrc/vae_generate.hip; any N); else the layer chain,
-        captured once and replayed per frame (N <= batch size), reading its source frame through the device step counter.
-        Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities; zout [3, N, T, L]
-         the latents (z_mean, z_log_var, z) of every frame.
-        Frames are read as on / off: ValueError (binary_frames) for sources or an x0 with an entry other than 0 and 1, on
-        both routes and before anything is launched."""
-        cfg, d = self.cfg, self.device
-        D, L = cfg['D'], cfg['L']
-        temper = temper_args(temperature, z_temperature)
-        sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, cfg['C'], d)
-        binary_frames(sources=sources, x0=x0)
-        N, T = int(sources.shape[0]), int(sources.shape[1])
-        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
-        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
-            args = (N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], hist_source, seed, sources, x0, w_enc, w_dec,
-                    *self._weights(), Xs)
-            if zout is None:
-                ops.vae_vary(*args, xhat_out, clamp=clamp, temper=temper)
-            else:
-                ops.vae_vary_latents(*args, _zout_ok(zout, N, T, L), xhat_out, clamp=clamp, temper=temper)
-            return Xs
-        rows = _VaeRows(self, N)
-        if zout is not None:
-            _zout_ok(zout, N, T, L)
-        chain = _Chain(rows, w_enc, w_dec, T, seed, temper, 'enc_input' if hist_source else 'sample',
-                       x_dec=None if x0 is None else x0.clone(), sources=sources, clamp=clamp)
-        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out, zout))
-        return Xs
 
-    def decode_latents(self, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
-               persistent=True, use_graph=True, xhat_out=None):
-        """Decode the latent path z [N, T, L]: vary's loop without its z-encoder.  Per frame t the decoder on
-        [w_dec, xp, z[:, t]] with xp = x0 (None: zeros) at t = 0, then the sample of frame t-1 (history='own') or
-        history[:, t-1] (an [N, T, D] array: teacher forcing); x ~ Bernoulli(x_hat) with the uniforms of row noise_rows[n]
-        (None: n), then the roll.  No eps is drawn.  persistent=True (default where the shapes allow): ONE kernel, a
-        workgroup per sequence (the ZG instance of csrc/vae_generate.hip); else the layer chain, captured once and replayed
-        per frame (N <= batch size), reading z[:, t] and history[:, t-1] through the device step counter.  Returns Xs
-        [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities.
-        Frames are read as on / off: ValueError (binary_frames) for an x0 or a given history with an entry other than 0 and
-        1, on both routes and before anything is launched."""
-        cfg, d = self.cfg, self.device
-        D, L = cfg['D'], cfg['L']
-        inv_T = decode_temper(temperature)
-        z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, cfg['C'], d)
-        binary_frames(x0=x0, history=hist)
-        N, T = int(z.shape[0]), int(z.shape[1])
-        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
-        if max(N * T * L, N * T * D) >= 2 ** 32:
-            persistent = False
-        if persistent and cfg['H'] > 0 and ops.vae_generate_supported(D, cfg['H'], L, cfg['C']):
-            ops.vae_decode(N, T, D, cfg['H'], L, cfg['C'], cfg['use_x_prev'], seed, z, x0, hist, w_dec, noise_rows,
-                           *self._weights(encoder=False), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
-            return Xs
-        chain = _Chain(_VaeRows(self, N), None, w_dec, T, seed, None if inv_T == 1.0 else (inv_T, 1.0),
-                       'sample' if hist is None else hist, x_dec=None if x0 is None else x0.clone(), z_path=z,
-                       noise_rows=noise_rows, clamp=clamp)
-        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out))
-        return Xs
-
-    def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
-                     z_prior=False, chunk=None, w_prior=None, temperature=1.0, z_temperature=1.0):
-        """Particle-filter sampling under the constraint roll clamp [N, nsteps, D] (DESIGN.md 11): melody m runs P =
-        `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
-        probability of each frame's clamped notes and resampled (systematic, below an ESS of resample_threshold * P).
-        Row t of the roll constrains frame t.  Melodies are processed in chunks of at most batch-size rows (and at most
-        `chunk` melodies); the Philox keys follow the global row, so the result does not depend on the chunking.
-        x_seed [N, D], w [N, C] device tensors.  Returns SmcResult (Xs [N, n_out, nsteps, D]).
-        w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state, so the filter
-        targets p(w, free notes | seed, constraints); returns SmcKeyResult.
-        temperature, z_temperature (temper_args, DESIGN.md 13): the filter runs on the TEMPERED model; its weights are the
-        tempered probabilities of the clamped notes, so log_evidence estimates log p_T(constraints | seed, w), the evidence
-        under the tempered model -- the trained model's only where both are 1."""
-        temper = temper_args(temperature, z_temperature)
-
-        def chain_of(xs, wr, r0, smc):
-            return _Chain(_VaeRows(self, smc.R), wr, wr, smc.nsteps, seed, temper, 'enc_input', x_enc=xs, x_dec=xs.clone(),
-                          z_prior=z_prior, r0=r0, smc=smc)
-
-        return _smc_run(self, 0, self.B, chain_of, x_seed, w, nsteps, clamp, particles, resample_threshold, n_out, seed,
-                        use_graph, chunk, w_prior)
-
-
-class VrnnGenerate:
+class VrnnGenerate(_Generate):
     STATE_KIND = 'cl_vrnn'
+    ROWS = _VrnnRows
+    _check_frames = staticmethod(lambda **frames: None)
+    _vary_op, _decode_op = staticmethod(ops.vrnn_vary_latents), staticmethod(ops.vrnn_decode)
+
+    def _persistent_ok(self):
+        cfg = self.cfg
+        return ops.vrnn_generate_supported(cfg['D'], cfg['H'], cfg['L'], cfg['C'])
+
+    def _family_flag(self):
+        return self.gate_act
+
+    def _vary_fits(self, clamp, T, zout):
+        """the persistent kernel addresses the roll, a sequence's frames and the latents in 32 bits"""
+        return not ((clamp is not None and clamp.numel() >= 2 ** 32) or T * self.cfg['D'] * 4 >= 2 ** 32
+                    or (zout is not None and zout.numel() >= 3 * 2 ** 32))
+
+    def _smc_seed(self, xs):
+        """S teacher-forced steps on one frame slot that the encoder and the decoder share"""
+        return dict(dec_prev='shared', seed_frames=xs)
+
+    def _smc_cap(self):
+        return None
 
     # -- stateful single-step inference (the reference's stateful batch-1 sub-models,
     #    cl_vrnn/model.py:116-162; here for any batch of independent sequences) -------------
@@ -1042,9 +1091,12 @@ class VrnnGenerate:
 
     def generate(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, persistent=True, xhat_out=None, clamp=None,
                  temperature=1.0, z_temperature=1.0, state=None, return_state=False):
-        """Autoregressive generation of N independent sequences on the device.  persistent=True (default where the
-        shapes allow): the whole frame loop is ONE kernel, a workgroup per sequence (csrc/generate.hip); otherwise the
-        per-frame chain below, captured once and replayed per frame.  Same Philox noise either way.
+        """Autoregressive generation of N independent sequences on the device (the hot loop of cl_vrnn/model.py:47-59,
+        noise from Philox instead of np.random): x_seed [N,S,D] device tensor (teacher-forced frames, S may be 0), w [N,C];
+        returns Xs [N,nsteps,D].  One frame = encoder step -> z ~ N(mean, exp(lv)) -> decoder step -> x ~ Bernoulli(x_hat).
+        persistent=True (default where the shapes allow): the whole frame loop is ONE kernel, a workgroup per sequence
+        (csrc/generate.hip); otherwise the frame chain, captured once and replayed per frame with no host synchronisation.
+        Same Philox noise either way.
         xhat_out [N,S+nsteps,D] (persistent path only) receives every frame's note probabilities.
         clamp: constraint roll [N,nsteps,D] (engine_generate.clamp_roll): row j constrains the returned frame Xs[:, j],
         drawn at step S+j; the bridge sample of step S-1 stays free (clamped ancestral sampling).  The
@@ -1058,7 +1110,8 @@ class VrnnGenerate:
         may be None or [N,0,D] (the free run goes on from the state's x) or hold more teacher-forced frames.  nsteps = 0
         with seed frames primes a state: its x is then the bridge sample.  A piece generated in several such calls is bit
         for bit the piece of one call; the state is the same on both routes and is not written.  Neither given (default):
-        exactly the launches above."""
+        exactly the launches above -- the plain, clamped or tempered entry; with either, the ST instances behind
+        vrnn_generate_resume (they need D = H: one row width)."""
         cfg = self.cfg
         temper = temper_args(temperature, z_temperature)
         resume = state is not None or return_state
@@ -1075,40 +1128,34 @@ class VrnnGenerate:
             clamp = None                # nothing is returned, so nothing is constrained
         if clamp is not None and clamp.numel() >= 2 ** 32:
             persistent = False
-        persistent = persistent and ops.vrnn_generate_supported(cfg['D'], cfg['H'], cfg['L'], cfg['C'])
         if resume:
-            run = self._resume_persistent if persistent else self._resume_frames
-            kw = {} if persistent else dict(use_graph=use_graph)
-            x_seed = x_seed.to(dtype=torch.float32, device=self.device).contiguous()
-            return run(x_seed, w.to(dtype=torch.float32, device=self.device).contiguous(), nsteps, seed, z_prior, xhat_out,
-                       clamp, temper, t0, state, return_state, **kw)
-        if persistent:
-            return self._generate_persistent(x_seed, w, nsteps, seed, z_prior, xhat_out, clamp, temper)
-        return self._generate_frames(x_seed, w, nsteps, seed, use_graph, z_prior, clamp, temper)
-
-    def _resume_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp, temper, t0, state, return_state):
-        """the ST instances of csrc/generate.hip (they need D = H: one row width)"""
-        cfg = self.cfg
-        N, S, D = int(x_seed.shape[0]), int(x_seed.shape[1]), cfg['D']
-        f = dict(dtype=torch.float32, device=self.device)
-        Xs = torch.zeros(N, nsteps, D, **f)
-        out = torch.empty(N, 5, D, **f) if return_state else None
-        ops.vrnn_generate_resume(N, S, nsteps, D, cfg['H'], cfg['L'], cfg['C'], self.gate_act, z_prior, seed,
-                                 x_seed if S else None, w, *self._weights(), Xs if nsteps else None, t0,
-                                 None if state is None else state.rows, out, xhat=xhat_out, clamp=clamp, temper=temper)
+            x_seed = x_seed.to(dtype=torch.float32, device=self.device)
+            w = w.to(dtype=torch.float32, device=self.device)
+        x_seed, w = x_seed.contiguous(), w.contiguous()
+        if not (persistent and self._persistent_ok()):
+            return self._generate_frames(x_seed, w, nsteps, seed, use_graph, z_prior, clamp, temper, t0, state, return_state)
+        Xs = torch.zeros(N, nsteps, cfg['D'], dtype=torch.float32, device=self.device)
+        head = (N, S, nsteps, cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.gate_act, z_prior, seed, x_seed if S else None, w,
+                *self._weights())
+        if not resume:
+            ops.vrnn_generate(*head, Xs, xhat_out, clamp=clamp, temper=temper)
+            return Xs
+        out = torch.empty(N, 5, cfg['D'], dtype=torch.float32, device=self.device) if return_state else None
+        ops.vrnn_generate_resume(*head, Xs if nsteps else None, t0, None if state is None else state.rows, out, xhat=xhat_out,
+                                 clamp=clamp, temper=temper)
         return (Xs, GenState('cl_vrnn', None, t0 + S + nsteps, rows=out)) if return_state else Xs
 
-    def _resume_frames(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp, temper, t0, state, return_state,
-                       use_graph=True):
-        """_generate_frames with the rows' LSTM states and the first input taken from the state and read back"""
+    def _generate_frames(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, clamp=None, temper=None, t0=0,
+                         state=None, return_state=False):
+        """generate on the frame chain: S seed steps, then nsteps returned frames.  With a state the rows' LSTM states and
+        the first input are taken from it (else zero, t0 = 0); with return_state they are read back after the last frame."""
         N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
         Xs = torch.zeros(N, nsteps, self.cfg['D'], dtype=torch.float32, device=self.device)
         rows = _VrnnRows(self, N)
         chain = _Chain(rows, w, w, nsteps, seed, temper, 'shared', z_prior=z_prior, seed_frames=x_seed, clamp=clamp, S=S,
                        t0=t0)
-        lstm = ('h_enc', 'c_enc', 'h_dec', 'c_dec')
         if state is not None:
-            for k in lstm:
+            for k in LSTM_FIELDS['cl_vrnn']:
                 rows.st[k].copy_(state[k])
             chain.x_enc.copy_(state.x)
 
@@ -1119,122 +1166,6 @@ class VrnnGenerate:
         chain.run(S + nsteps, use_graph, after)
         if not return_state:
             return Xs
-        tensors = {k: rows.st[k].clone() for k in lstm}
+        tensors = {k: rows.st[k].clone() for k in LSTM_FIELDS['cl_vrnn']}
         tensors['x'] = chain.x_enc.clone()
         return Xs, GenState('cl_vrnn', tensors, t0 + S + nsteps)
-
-    def _generate_persistent(self, x_seed, w, nsteps, seed, z_prior, xhat_out, clamp=None, temper=None):
-        cfg = self.cfg
-        N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
-        Xs = torch.zeros(N, nsteps, cfg['D'], dtype=torch.float32, device=self.device)
-        ops.vrnn_generate(N, S, nsteps, cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.gate_act, z_prior, seed,
-                          x_seed.contiguous() if S else None, w.contiguous(), *self._weights(), Xs, xhat_out, clamp=clamp,
-                          temper=temper)
-        return Xs
-
-    def _generate_frames(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, clamp=None, temper=None):
-        """Batched autoregressive generation on the device (the hot loop of cl_vrnn/model.py:47-59 for N
-        independent sequences at once, noise from Philox instead of np.random).
-        x_seed [N,S,D] device tensor (teacher-forced frames, S may be 0), w [N,C]; returns Xs [N,nsteps,D].
-        One frame = encoder step -> z ~ N(mean, exp(lv)) -> decoder step -> x ~ Bernoulli(x_hat); the chain
-        is captured once and replayed per frame with no host synchronisation."""
-        N, S = int(x_seed.shape[0]), int(x_seed.shape[1])
-        Xs = torch.zeros(N, nsteps, self.cfg['D'], dtype=torch.float32, device=self.device)
-        w = w.contiguous()
-        chain = _Chain(_VrnnRows(self, N), w, w, nsteps, seed, temper, 'shared', z_prior=z_prior, seed_frames=x_seed,
-                       clamp=clamp, S=S)
-
-        def after(t):
-            if t >= S:
-                chain.store(t - S, Xs)
-
-        chain.run(S + nsteps, use_graph, after)
-        return Xs
-
-    def vary(self, sources, w_enc, w_dec=None, x0=None, history='own', seed=0, clamp=None, temperature=1.0,
-             z_temperature=1.0, persistent=True, use_graph=True, xhat_out=None, zout=None):
-        """Re-decode sources [N, T, D]: from zero LSTM states, per frame t the encoder step on [sources[t],
-        w_enc], z = mean + exp(lv / 2) * Tz * eps, the decoder step on [xp, z, w_dec] with xp = x0 (None: zeros) at t = 0,
-        then the sample of frame t-1 (history='own') or sources[t-1] ('source': the training forward pass; no effect
-        without use_x_prev); x ~ Bernoulli(x_hat), then the roll clamp [N, T, D] (row t constrains frame t; no bridge).
-        w_dec=None: w_enc (a variation); another label: key transfer.  Noise as generate's with S = 0.  persistent=True
-        (default where the shapes allow): ONE kernel, a workgroup per sequence (the VR instances of csrc/generate.hip);
-        else the per-frame chain, captured once and replayed per frame, reading its source frame through the device step
-        counter.  A roll of 2^32 bytes or more takes the chain.  Returns Xs [N, T, D]; xhat_out [N, T, D] receives the
-        unclamped (tempered) probabilities; zout [3, N, T, L] the latents (z_mean, z_log_var, z) of every
-        frame."""
-        cfg, d = self.cfg, self.device
-        D, H, L, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['C']
-        temper = temper_args(temperature, z_temperature)
-        sources, w_enc, w_dec, x0, clamp, hist_source = vary_args(sources, w_enc, w_dec, x0, history, clamp, D, Cn, d)
-        N, T = int(sources.shape[0]), int(sources.shape[1])
-        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
-        if (clamp is not None and clamp.numel() >= 2 ** 32) or T * D * 4 >= 2 ** 32:
-            persistent = False
-        if zout is not None:
-            _zout_ok(zout, N, T, L)
-            if zout.numel() >= 3 * 2 ** 32:
-                persistent = False
-        if persistent and ops.vrnn_generate_supported(D, H, L, Cn):
-            args = (N, T, D, H, L, Cn, self.gate_act, hist_source, seed, sources, x0, w_enc, w_dec, *self._weights(), Xs)
-            if zout is None:
-                ops.vrnn_vary(*args, xhat_out, clamp=clamp, temper=temper)
-            else:
-                ops.vrnn_vary_latents(*args, zout, xhat_out, clamp=clamp, temper=temper)
-            return Xs
-        chain = _Chain(_VrnnRows(self, N), w_enc, w_dec, T, seed, temper, 'enc_input' if hist_source else 'sample',
-                       x_dec=None if x0 is None else x0.clone(), sources=sources, clamp=clamp)
-        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out, zout))
-        return Xs
-
-    def decode_latents(self, z, w_dec, x0=None, history='own', seed=0, clamp=None, temperature=1.0, noise_rows=None,
-               persistent=True, use_graph=True, xhat_out=None):
-        """Decode the latent path z [N, T, L]: vary's loop without its encoder.  From zero LSTM state, per
-        frame t the decoder step on [xp, z[:, t], w_dec] with xp = x0 (None: zeros) at t = 0, then the sample of frame t-1
-        (history='own') or history[:, t-1] (an [N, T, D] array: teacher forcing; no effect without use_x_prev);
-        x ~ Bernoulli(x_hat) with the uniforms of row noise_rows[n] (None: n), then the roll clamp [N, T, D].  No eps is
-        drawn.  persistent=True (default where the shapes allow): ONE kernel, a workgroup per sequence (the ZG instances of
-        csrc/generate.hip); else the per-frame chain, captured once and replayed per frame, reading z[:, t] and
-        history[:, t-1] through the device step counter.  N*T*L or N*T*D of 2^32 or more takes the chain.  Returns Xs
-        [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities."""
-        cfg, d = self.cfg, self.device
-        D, H, L, Cn = cfg['D'], cfg['H'], cfg['L'], cfg['C']
-        inv_T = decode_temper(temperature)
-        z, w_dec, x0, hist, clamp, noise_rows = decode_args(z, w_dec, x0, history, clamp, noise_rows, D, L, Cn, d)
-        N, T = int(z.shape[0]), int(z.shape[1])
-        Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
-        if max(N * T * L, N * T * D) >= 2 ** 32:
-            persistent = False
-        if persistent and ops.vrnn_generate_supported(D, H, L, Cn):
-            ops.vrnn_decode(N, T, D, H, L, Cn, self.gate_act, seed, z, x0, hist, w_dec, noise_rows,
-                            *self._weights(encoder=False), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
-            return Xs
-        chain = _Chain(_VrnnRows(self, N), None, w_dec, T, seed, None if inv_T == 1.0 else (inv_T, 1.0),
-                       'sample' if hist is None else hist, x_dec=None if x0 is None else x0.clone(), z_path=z,
-                       noise_rows=noise_rows, clamp=clamp)
-        chain.run(T, use_graph, lambda t: chain.store(t, Xs, xhat_out))
-        return Xs
-
-    def generate_smc(self, x_seed, w, nsteps, clamp, particles, resample_threshold=0.5, n_out=1, seed=0, use_graph=True,
-                     z_prior=False, chunk=None, w_prior=None, temperature=1.0, z_temperature=1.0):
-        """Particle-filter sampling under the constraint roll clamp [N, nsteps, D] (DESIGN.md 11): melody m runs P =
-        `particles` copies of the frame chain of generate(persistent=False) as global rows m*P + p, weighted by the
-        probability of each returned frame's clamped notes and resampled (systematic, below an ESS of
-        resample_threshold * P).  Row j of the roll constrains the sample of step S+j; the seed steps and the bridge carry
-        no constraint and no weight.  `chunk`: at most that many melodies per pass (the Philox keys follow the global row,
-        so the result does not depend on it).  x_seed [N, S, D], w [N, C] device tensors.  Returns SmcResult.
-        w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state (the seed steps
-        run under it too, unweighted), so the filter targets p(w, free notes | seed, constraints); returns
-        SmcKeyResult.
-        temperature, z_temperature (temper_args, DESIGN.md 13): the filter runs on the TEMPERED model; its weights are the
-        tempered probabilities of the clamped notes, so log_evidence estimates log p_T(constraints | seed, w), the evidence
-        under the tempered model -- the trained model's only where both are 1."""
-        S = int(x_seed.shape[1])
-        temper = temper_args(temperature, z_temperature)
-
-        def chain_of(xs, wr, r0, smc):
-            return _Chain(_VrnnRows(self, smc.R), wr, wr, smc.nsteps, seed, temper, 'shared', z_prior=z_prior, seed_frames=xs,
-                          r0=r0, smc=smc)
-
-        return _smc_run(self, S, None, chain_of, x_seed, w, nsteps, clamp, particles, resample_threshold, n_out, seed,
-                        use_graph, chunk, w_prior)
