@@ -65,6 +65,8 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_p
     frame, Philox noise instead of np.random: same distribution, different draws).  x_seeds [N,D], w_vals [N,C];
     returns [N,nsteps,D] float64 like generate_sample does per sequence.  clamp: numpy / torch uint8 [N,nsteps,D]
     constraint roll (0 off, 1 on, harmonize.FREE free): row t constrains frame t (clamped ancestral sampling).
+    clamp may also be an engine_generate.Constraints: a roll and / or voice counts (lo, hi) per returned frame,
+    every frame then drawn exactly given how many of its notes sound (on the frame chain, or in the filter with particles).
     particles=P: particle-filter sampling given every constraint (VaeEngine.generate_smc; resampling below an
     ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64.
     w_prior (an engine_generate.WPrior, with particles and instead of w_vals): a w per particle drawn from it, the evidence

@@ -9,8 +9,10 @@ if __package__ in (None, ''):
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
 from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
-                           VARY_FLAGS, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs)
-from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior, voice_constraints  # noqa: E402
+                           VARY_FLAGS, VOICES_FLAGS, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs,
+                           voices_kwargs)
+from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, voice_constraints,  # noqa: E402
+                                 voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
@@ -56,11 +58,12 @@ class Sampler:
         resume = resume_kwargs(self.args, self.data.key_map, len(names), self.margs['n_classes'])
         if resume:              # --chunk / --modulate: the same call a chunk at a time
             rolls = generate_chunked(self.model, np.stack(seeds), self.args.t, np.vstack(ws), seed=getattr(self.args, 'seed', 0),
-                                     z_prior=self.args.use_z_prior, **resume, **temperature_kwargs(self.args))
+                                     z_prior=self.args.use_z_prior, **resume, **temperature_kwargs(self.args),
+                                     **count_clamp(self.args))
         else:
             rolls = M.generate_samples_device(self.model, np.stack(seeds), self.args.t, np.vstack(ws),
                                               seed=getattr(self.args, 'seed', 0), use_z_prior=self.args.use_z_prior,
-                                              **temperature_kwargs(self.args))
+                                              **temperature_kwargs(self.args), **count_clamp(self.args))
         for roll, name in zip(rolls, names):
             write_sample(roll, self.args.sample_dir, name, True)
         return list(rolls)
@@ -83,13 +86,13 @@ class Sampler:
         resume = resume_kwargs(self.args, self.data.key_map, len(names), self.margs['n_classes'])
         if resume:              # --chunk / --modulate: harmonize()'s call a chunk at a time, the roll sliced per chunk
             out = generate_chunked(self.model, seeds, self.args.t, np.vstack(ws), seed=getattr(self.args, 'seed', 0),
-                                   z_prior=self.args.use_z_prior, clamp=voice_constraints(sources, voice_of(self.args)),
+                                   z_prior=self.args.use_z_prior, clamp=kept_voice(self.args, sources),
                                    **resume, **temperature_kwargs(self.args))
         else:
             out = harmonize(self.model, seeds, sources, None if ws is None else np.vstack(ws), voice=voice_of(self.args),
                             seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior, particles=particles,
                             return_evidence=particles is not None, **(dict(infer_key=infer_key) if infer_key else {}),
-                            **temperature_kwargs(self.args))
+                            **temperature_kwargs(self.args), voices=voices_kwargs(self.args))
         rolls = out[0] if particles is not None else out
         if particles is not None:
             print_evidence(names, out[1], self.args.t)
@@ -109,7 +112,7 @@ class Sampler:
                                                        for i in picks])
         rolls = vary(self.model, sources, ws, to_key=getattr(self.args, 'to_key', None), key_map=self.data.key_map,
                      history=getattr(self.args, 'vary_history', 'own'), seed=getattr(self.args, 'seed', 0),
-                     **temperature_kwargs(self.args))
+                     **temperature_kwargs(self.args), **count_clamp(self.args))
         for roll, src, name in zip(rolls, sources, names):
             write_sample(roll, self.args.sample_dir, name, True)
             write_sample(src, self.args.sample_dir, name + '_source', True)
@@ -133,7 +136,7 @@ class Sampler:
                                                        for i in picks])
         rolls = morph(self.model, sources[0::2], sources[1::2], steps=self.args.morph,
                       w_a=None if ws is None else ws[0::2], w_b=None if ws is None else ws[1::2],
-                      seed=getattr(self.args, 'seed', 0), **morph_kwargs(self.args))
+                      seed=getattr(self.args, 'seed', 0), **morph_kwargs(self.args), **count_clamp(self.args))
         for j, rows in enumerate(rolls):
             write_sample(sources[2 * j], self.args.sample_dir, '%s_%d_a' % (self.args.run_name, j), True)
             write_sample(sources[2 * j + 1], self.args.sample_dir, '%s_%d_b' % (self.args.run_name, j), True)
@@ -152,6 +155,18 @@ def make_sample(P, dec_model, w_enc_model, z_enc_model, args, margs):
     return roll
 
 
+def count_clamp(args):
+    """--voices as the clamp= of a call without a roll: {} without the flag (also for parsers without it)"""
+    v = voices_kwargs(args)
+    return {} if v is None else dict(clamp=voice_counts(v, None))
+
+
+def kept_voice(args, sources):
+    """--harmonize's roll over `sources`, under --voices with the frames' counts"""
+    roll, v = voice_constraints(sources, getattr(args, 'harmonize', None)), voices_kwargs(args)
+    return roll if v is None else voice_counts(v, sources, roll)
+
+
 def voice_of(args):
     """--harmonize's voice, or None (also for parsers without the flag)"""
     return getattr(args, 'harmonize', None)
@@ -161,8 +176,8 @@ def on_device(args):
     """Where the frame loop runs: like the reference (host loop, np.random) for every -n unless --device_loop asks for
     the device-side loop (Philox noise: other samples for the same np.random.seed, so it is opt-in); --harmonize
     --vary, --morph, --chunk and --modulate always run there, and so does a sampling temperature (the parser refuses them
-    next to --host_loop)."""
-    return bool(voice_of(args)) or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
+    next to --host_loop), and so does --voices."""
+    return bool(voice_of(args)) or getattr(args, 'voices', None) is not None or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
         temperature_kwargs(args)) or resuming(args) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
 
@@ -186,4 +201,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vae.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS).parse_args())

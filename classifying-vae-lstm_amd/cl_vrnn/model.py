@@ -244,6 +244,8 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     Returns the free-running part [N,nsteps,88] as a numpy array, like generate_sample does per seed.
     clamp: numpy / torch uint8 [N,nsteps,88] constraint roll (0 off, 1 on, harmonize.FREE free): row j constrains
     returned frame j (clamped ancestral sampling; the unreturned bridge sample of step S-1 stays free).
+    clamp may also be an engine_generate.Constraints: a roll and / or voice counts (lo, hi) per returned frame,
+    every frame then drawn exactly given how many of its notes sound (on the frame chain, or in the filter with particles).
     particles=P: particle-filter sampling given every constraint (VrnnEngine.generate_smc; resampling below
     an ESS of resample_threshold * P), one path per seed; return_evidence: also log p(constraints | seed, w) [N] float64.
     w_prior (an engine_generate.WPrior, with particles and instead of w_vals): a w per particle drawn from it, the evidence

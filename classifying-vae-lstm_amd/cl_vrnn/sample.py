@@ -9,8 +9,10 @@ if __package__ in (None, ''):
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
 from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
-                           VARY_FLAGS, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs)
-from clvae_amd.harmonize import harmonize, print_evidence, print_key_posterior, voice_constraints  # noqa: E402
+                           VARY_FLAGS, VOICES_FLAGS, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs,
+                           voices_kwargs)
+from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, voice_constraints,  # noqa: E402
+                                 voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
@@ -49,10 +51,12 @@ def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None)
         resume = resume_kwargs(args, P.key_map, len(picks), margs['n_classes'])
         if resume:              # --chunk / --modulate: the same call a chunk at a time
             rolls = list(generate_chunked(model, np.stack([P.x_test[i] for i in picks]), args.t, np.vstack(ws),
-                                          seed=getattr(args, 'seed', 0), **resume, **temperature_kwargs(args)))
+                                          seed=getattr(args, 'seed', 0), **resume, **temperature_kwargs(args),
+                                          **count_clamp(args)))
         else:
             rolls = list(M.generate_samples_device(model, np.stack([P.x_test[i] for i in picks]), args.t, np.vstack(ws),
-                                                   seed=getattr(args, 'seed', 0), **temperature_kwargs(args)))
+                                                   seed=getattr(args, 'seed', 0), **temperature_kwargs(args),
+                                                   **count_clamp(args)))
     else:
         rolls = [M.generate_sample(dec_model, w_enc_model, z_enc_model, P.x_test[i], args.t, margs['use_x_prev'],
                                    w_val=label_of(i), w_discrete=args.discrete_w, seq_length=margs['seq_length'])
@@ -76,7 +80,7 @@ def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice
     if infer_key:               # --infer_key: the filter weighs the keys by the voice, a key per particle
         model.engine.cfg['w_log_var_prior'] = float(margs.get('w_log_var_prior', 0.0))      # load_model rebuilds layers only
         out = harmonize(model, seeds, sources, None, voice=voice, seed=getattr(args, 'seed', 0), particles=particles,
-                        return_evidence=True, infer_key=infer_key, **temperature_kwargs(args))
+                        return_evidence=True, infer_key=infer_key, **temperature_kwargs(args), voices=voices_kwargs(args))
     else:
         ws = [label_of(i) for i in picks]
         if args.infer_w:
@@ -84,10 +88,11 @@ def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice
         resume = resume_kwargs(args, P.key_map, len(picks), margs['n_classes'])
         if resume:              # --chunk / --modulate: harmonize()'s call a chunk at a time, the roll sliced per chunk
             out = generate_chunked(model, seeds, t, np.vstack(ws), seed=getattr(args, 'seed', 0),
-                                   clamp=voice_constraints(sources, voice), **resume, **temperature_kwargs(args))
+                                   clamp=kept_voice(args, sources), **resume, **temperature_kwargs(args))
         else:
             out = harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0),
-                            particles=particles, return_evidence=particles is not None, **temperature_kwargs(args))
+                            particles=particles, return_evidence=particles is not None, **temperature_kwargs(args),
+                            voices=voices_kwargs(args))
     rolls = list(out[0] if particles is not None else out)
     if particles is not None:
         names = ['%s_%d' % (args.run_name, j) for j in range(len(rolls))]
@@ -111,7 +116,8 @@ def vary_samples(P, w_enc_model, args, margs, model, picks, label_of, half_speed
     if args.infer_w:
         ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in sources]
     rolls = list(vary(model, sources, np.vstack(ws), to_key=getattr(args, 'to_key', None), key_map=P.key_map,
-                      history=getattr(args, 'vary_history', 'own'), seed=getattr(args, 'seed', 0), **temperature_kwargs(args)))
+                      history=getattr(args, 'vary_history', 'own'), seed=getattr(args, 'seed', 0), **temperature_kwargs(args),
+                      **count_clamp(args)))
     for j, roll in enumerate(rolls):
         write_sample(roll, args.sample_dir, '%s_%d' % (args.run_name, j), half_speed)
         write_sample(sources[j], args.sample_dir, '%s_%d_source' % (args.run_name, j), half_speed)
@@ -130,13 +136,25 @@ def morph_samples(P, w_enc_model, args, margs, model, picks, label_of, half_spee
         ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in sources]
     ws = np.vstack(ws)
     rolls = morph(model, sources[0::2], sources[1::2], steps=args.morph, w_a=ws[0::2], w_b=ws[1::2],
-                  seed=getattr(args, 'seed', 0), **morph_kwargs(args))
+                  seed=getattr(args, 'seed', 0), **morph_kwargs(args), **count_clamp(args))
     for j, rows in enumerate(rolls):
         write_sample(sources[2 * j], args.sample_dir, '%s_%d_a' % (args.run_name, j), half_speed)
         write_sample(sources[2 * j + 1], args.sample_dir, '%s_%d_b' % (args.run_name, j), half_speed)
         for k, roll in enumerate(rows):
             write_sample(roll, args.sample_dir, '%s_%d_morph%d' % (args.run_name, j, k), half_speed)
     return list(rolls)
+
+
+def count_clamp(args):
+    """--voices as the clamp= of a call without a roll: {} without the flag (also for parsers without it)"""
+    v = voices_kwargs(args)
+    return {} if v is None else dict(clamp=voice_counts(v, None))
+
+
+def kept_voice(args, sources):
+    """--harmonize's roll over `sources`, under --voices with the frames' counts"""
+    roll, v = voice_constraints(sources, getattr(args, 'harmonize', None)), voices_kwargs(args)
+    return roll if v is None else voice_counts(v, sources, roll)
 
 
 def sample(args):
@@ -150,8 +168,9 @@ def sample(args):
     # --harmonize: windows of the seed's t frames and the t frames whose voice is kept
     P = PianoData(args.train_file, batch_size=1, seq_length=2 * args.t if voice else args.t, squeeze_x=False)
     # the reference's host loop (np.random) for every -n; --device_loop opts into the device-side loop (Philox noise), and
-    # a sampling temperature, --vary, --morph, --chunk and --modulate imply it (the parser refuses them next to --host_loop)
-    on_device = bool(voice) or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
+    # a sampling temperature, --vary, --morph, --chunk, --modulate and --voices imply it (the parser refuses them next to
+    # --host_loop)
+    on_device = bool(voice) or getattr(args, 'voices', None) is not None or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
         temperature_kwargs(args)) or resuming(args) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
     return gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
@@ -164,4 +183,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vrnn.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS).parse_args())

@@ -159,6 +159,33 @@ RESUME_FLAGS = [
 ]
 
 
+# voice counts (not in the reference): how many notes sound in every generated frame (implies --device_loop)
+VOICES_FLAGS = [
+    Flag(('--voices',), str, None, 'LO[:HI]: every generated frame holds LO (or LO to HI) sounding notes, 0 <= LO <= HI <= 15, '
+                                   'drawn exactly given that count; with --harmonize the kept voice counts too (on the '
+                                   'device loop only; implies --device_loop)'),
+]
+
+
+def parse_voices(text):
+    """--voices' LO[:HI] -> (lo, hi); ValueError unless both are integers with 0 <= lo <= hi <= 15"""
+    lo, sep, hi = str(text).partition(':')
+    try:
+        lo = int(lo)
+        hi = int(hi) if sep else lo
+    except ValueError:
+        raise ValueError("--voices takes LO[:HI], got %r" % (text,))
+    if not 0 <= lo <= hi <= 15:
+        raise ValueError("--voices: 0 <= LO <= HI <= 15, got %r" % (text,))
+    return lo, hi
+
+
+def voices_kwargs(args):
+    """--voices as a pair (lo, hi), None without the flag (also for parsers without it)"""
+    v = getattr(args, 'voices', None)
+    return None if v is None else parse_voices(v)
+
+
 def parse_modulate(text, t):
     """--modulate's NAME@FRAME[,NAME@FRAME...] -> [(name, frame), ...]; ValueError unless every item has a name and an
     integer frame and the frames are strictly increasing, > 0 and < t"""
@@ -216,7 +243,8 @@ class _Parser(argparse.ArgumentParser):
     """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles, a
     temperature other than 1 not with --host_loop (the host loop is the reference's and has none), --vary not with
     --harmonize or --host_loop, --to_key / --vary_history only with --vary, --morph >= 1 and not with --harmonize, --vary or
-    --host_loop, --chunk >= 1 and a well-formed --modulate, neither with --particles, --vary, --morph or --host_loop"""
+    --host_loop, --chunk >= 1 and a well-formed --modulate, neither with --particles, --vary, --morph or --host_loop, a
+    well-formed --voices LO[:HI] and not with --host_loop"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -259,6 +287,14 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--morph decodes mixed latent paths: not with --vary')
             if getattr(ns, 'host_loop', False):
                 self.error('--morph runs on the device loop: not with --host_loop')
+        voices = getattr(ns, 'voices', None)
+        if voices is not None:
+            try:
+                parse_voices(voices)
+            except ValueError as e:
+                self.error(str(e))
+            if getattr(ns, 'host_loop', False):
+                self.error('--voices runs on the device loop: not with --host_loop')
         temper = temperature_kwargs(ns)
         if temper:
             from .engine_generate import temper_args

@@ -30,9 +30,12 @@ def binary_frames(**frames):
 def clamp_roll(clamp, N, nsteps, D, device):
     """A constraint roll for generate(clamp=...): uint8 [N, nsteps, D], one row per returned frame; 0 forces the note off,
     1 forces it on, any other value (harmonize.FREE = 255) leaves it free.  numpy or torch in, contiguous device tensor out;
-    ValueError on a wrong shape or dtype."""
+    ValueError on a wrong shape or dtype.  A Constraints (roll and / or voice counts) in the same place: one
+    without voices comes back as its roll (or None), one with voices as itself, checked and on the device (resolve)."""
     if clamp is None:
         return None
+    if isinstance(clamp, Constraints):
+        return clamp.resolve(N, nsteps, D, device)
     if isinstance(clamp, torch.Tensor):
         if clamp.dtype != torch.uint8:
             raise ValueError("clamp must be uint8, got %s" % clamp.dtype)
@@ -44,6 +47,143 @@ def clamp_roll(clamp, N, nsteps, D, device):
     if tuple(clamp.shape) != (int(N), int(nsteps), int(D)):
         raise ValueError("clamp must have shape %s, got %s" % ((int(N), int(nsteps), int(D)), tuple(clamp.shape)))
     return clamp.to(device).contiguous()
+
+
+VOICES_FREE = (0, 255)          # the pair of a frame without a count
+VOICES_MAX = 15                 # the largest hi: the kernel's lanes hold the counts 0 .. 15
+VOICES_MAX_D = 128              # VOICES_MAX_D of csrc/voices.hip: two notes per lane
+
+
+def _count_pair(lo, hi):
+    for v in (lo, hi):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("a voice count is an integer, got %r" % (v,))
+    if not 0 <= lo <= hi <= VOICES_MAX:
+        raise ValueError("voice counts must satisfy 0 <= lo <= hi <= %d, got (%d, %d)" % (VOICES_MAX, lo, hi))
+    return int(lo), int(hi)
+
+
+class Constraints:
+    """What a device sampler's frames must satisfy, passed as the value of clamp=: a constraint roll (uint8
+    [N, nsteps, D], clamp_roll) and / or voice counts.  voices: uint8 [N, nsteps, 2] holding (lo, hi) per returned frame --
+    the frame then has lo <= sounding notes <= hi, 0 <= lo <= hi <= 15, drawn exactly from p(frame | roll row, count in
+    range); the pair (0, 255) leaves a frame free -- or an int k (exactly k in every frame) or a pair (lo, hi) for every
+    frame.  numpy or torch.  Row j of the counts applies where row j of the roll applies; seed steps and the bridge carry
+    none.  exactly(k), between(lo, hi) and as_in(source_rolls) (every frame as many notes as the source frame has) build
+    one; each takes roll= too.  Without voices a Constraints is its roll, launch for launch.  With voices the call runs on
+    the frame chain (persistent=True takes the chain too: the persistent kernels do not carry the count) or in the particle
+    filter, whose weight increment gains log P(count in range | forced notes).  A frame is infeasible when more notes are
+    forced on than hi, or forced-on plus free notes are fewer than lo: ValueError before any launch (resolve)."""
+
+    def __init__(self, roll=None, voices=None):
+        if isinstance(voices, (int, np.integer)) and not isinstance(voices, (bool, np.bool_)):
+            voices = _count_pair(voices, voices)
+        elif isinstance(voices, (tuple, list)):
+            if len(voices) != 2:
+                raise ValueError("voices must be an int, a pair (lo, hi) or a uint8 array [N, nsteps, 2], got %r" % (voices,))
+            voices = _count_pair(*voices)
+        elif voices is not None and not isinstance(voices, (np.ndarray, torch.Tensor)):
+            raise ValueError("voices must be an int, a pair (lo, hi) or a uint8 array [N, nsteps, 2], got %r" % (voices,))
+        if isinstance(roll, Constraints):
+            raise ValueError("roll must be a uint8 array, not a Constraints")
+        self.roll, self.voices, self._key = roll, voices, None
+
+    @classmethod
+    def exactly(cls, k, roll=None):
+        """every returned frame has exactly k sounding notes"""
+        return cls(roll, _count_pair(k, k))
+
+    @classmethod
+    def between(cls, lo, hi, roll=None):
+        """every returned frame has lo .. hi sounding notes"""
+        return cls(roll, _count_pair(lo, hi))
+
+    @classmethod
+    def as_in(cls, source_rolls, roll=None):
+        """frame (n, t) has as many sounding notes as source_rolls[n, t] ([N, nsteps, D], nonzero = sounding)"""
+        src = np.asarray(source_rolls.cpu() if isinstance(source_rolls, torch.Tensor) else source_rolls)
+        if src.ndim != 3:
+            raise ValueError("source_rolls must be [N, nsteps, D], got shape %s" % (src.shape,))
+        n = (src != 0).sum(axis=-1)
+        if n.size and n.max() > VOICES_MAX:
+            raise ValueError("a source frame has %d sounding notes: voice counts go up to %d" % (n.max(), VOICES_MAX))
+        return cls(roll, np.ascontiguousarray(np.stack([n, n], axis=-1).astype(np.uint8)))
+
+    def __getitem__(self, index):
+        """the constraints of some sequences and frames: c[m0:m1], c[:, a:b] (the index goes to the roll and to the counts)"""
+        take = lambda a: a if a is None or isinstance(a, tuple) else a[index]
+        out = Constraints(take(self.roll), take(self.voices))
+        if self._key is not None:           # a part of a checked whole is checked: only its shape is new
+            for name in ('roll', 'voices'):
+                if getattr(out, name) is not None:
+                    setattr(out, name, getattr(out, name).contiguous())
+            v = out.voices
+            out._key = (int(v.shape[0]), int(v.shape[1]), self._key[2], self._key[3])
+        return out
+
+    def repeat_rows(self, k):
+        """every sequence's constraints k times in a row (morph: the rows of a pair)"""
+        rep = lambda a: a if a is None or isinstance(a, tuple) else (
+            a.repeat_interleave(k, 0) if isinstance(a, torch.Tensor) else np.repeat(np.asarray(a), k, axis=0))
+        return Constraints(rep(self.roll), rep(self.voices))
+
+    def resolve(self, N, nsteps, D, device):
+        """Check against a call of N sequences x nsteps returned frames x D notes and move to the device.  Returns None
+        (nothing given), the roll as clamp_roll returns it (no voices), or a Constraints whose roll (or None) and voices are
+        contiguous uint8 device tensors.  ValueError for a wrong shape or dtype, D > 128, a pair that is neither (0, 255)
+        nor 0 <= lo <= hi <= 15, and an infeasible frame.  One device reduction, before any launch."""
+        key = (int(N), int(nsteps), int(D), str(device))
+        if self._key == key:
+            return self
+        roll = clamp_roll(self.roll, N, nsteps, D, device)
+        v = self.voices
+        if v is None:
+            return roll
+        if D > VOICES_MAX_D:
+            raise ValueError("voice counts need D <= %d notes, got %d" % (VOICES_MAX_D, D))
+        if isinstance(v, tuple):
+            v = torch.tensor(v, dtype=torch.uint8).expand(int(N), int(nsteps), 2)
+        else:
+            if not isinstance(v, torch.Tensor):
+                v = np.asarray(v)
+                if v.dtype != np.uint8:
+                    raise ValueError("voices must be uint8, got %s" % v.dtype)
+                v = torch.from_numpy(np.ascontiguousarray(v))
+            if v.dtype != torch.uint8:
+                raise ValueError("voices must be uint8, got %s" % v.dtype)
+            if tuple(v.shape) != (int(N), int(nsteps), 2):
+                raise ValueError("voices must have shape %s, got %s" % ((int(N), int(nsteps), 2), tuple(v.shape)))
+        v = v.to(device).contiguous()
+        lo, hi = v[..., 0].to(torch.int32), v[..., 1].to(torch.int32)
+        counted = ~((lo == VOICES_FREE[0]) & (hi == VOICES_FREE[1]))
+        bad = counted & ((lo > hi) | (hi > VOICES_MAX))
+        if roll is None:
+            on, open_ = torch.zeros_like(lo), torch.full_like(lo, int(D))
+        else:
+            on, open_ = (roll == 1).sum(-1).to(torch.int32), (roll > 1).sum(-1).to(torch.int32)
+        over, under = counted & ~bad & (on > hi), counted & ~bad & (on + open_ < lo)
+        wrong = bad | over | under
+        if wrong.numel() and bool(wrong.any()):
+            n, t = [int(i) for i in wrong.nonzero()[0]]
+            a, b, k, f = int(lo[n, t]), int(hi[n, t]), int(on[n, t]), int(open_[n, t])
+            if bool(bad[n, t]):
+                raise ValueError("voices[%d, %d] = (%d, %d): a pair is (0, 255) (free) or 0 <= lo <= hi <= %d"
+                                 % (n, t, a, b, VOICES_MAX))
+            if bool(over[n, t]):
+                raise ValueError("frame %d of sequence %d is infeasible: the roll forces %d notes on, more than hi = %d"
+                                 % (t, n, k, b))
+            raise ValueError("frame %d of sequence %d is infeasible: %d notes forced on and %d free are fewer than lo = %d"
+                             % (t, n, k, f, a))
+        out = Constraints(roll, v)
+        out._key = key
+        return out
+
+
+def clamp_parts(clamp):
+    """(roll, voices) of what clamp_roll returned: None, a roll, or a resolved Constraints"""
+    if isinstance(clamp, Constraints):
+        return clamp.roll, clamp.voices
+    return clamp, None
 
 
 SmcResult = namedtuple('SmcResult', 'Xs log_evidence ess resamples')
@@ -123,8 +263,9 @@ def smc_label_args(w, w_prior, N, C, device):
 
 
 def smc_args(clamp, particles, resample_threshold, n_out, N, nsteps, D, device):
-    """Validate generate_smc's arguments; returns the constraint roll as a device tensor (clamp_roll)."""
-    if clamp is None:
+    """Validate generate_smc's arguments; returns the constraints on the device (clamp_roll: a roll, or a Constraints with
+    voice counts)."""
+    if clamp is None or (isinstance(clamp, Constraints) and clamp.roll is None and clamp.voices is None):
         raise ValueError("particle sampling needs a constraint roll (clamp=...)")
     if isinstance(particles, bool) or int(particles) != particles or not 1 <= particles <= SMC_MAX_PARTICLES:
         raise ValueError("particles must be an integer in [1, %d], got %r" % (SMC_MAX_PARTICLES, particles))
@@ -575,7 +716,8 @@ class _Smc:
         self.wr = wr                # the particles' own label rows [R, C] under a key prior, else None
         if wr is not None:
             self.w_post = torch.zeros(G, nsteps, wr.shape[1], dtype=torch.float64, device=device)
-        self.tau, self.seed, self.m0, self.clamp = tau, seed, m0, clamp
+        self.tau, self.seed, self.m0 = tau, seed, m0
+        self.clamp, self.voices = clamp_parts(clamp)        # the roll (None under voice counts alone) and the counts
         f64 = dict(dtype=torch.float64, device=device)
         i32 = dict(dtype=torch.int32, device=device)
         self.ell, self.logW = torch.zeros(self.R, **f64), torch.zeros(self.R, **f64)
@@ -585,7 +727,12 @@ class _Smc:
         self.hist = torch.zeros(nsteps, self.R, D, dtype=torch.uint8, device=device)
 
     def step(self, xhat, u, counter, x_next, gather):
-        ops.smc_sample(self.R, self.D, self.P, self.nsteps, self.S, xhat, u, self.clamp, counter, x_next, self.ell, self.hist)
+        if self.voices is None:
+            ops.smc_sample(self.R, self.D, self.P, self.nsteps, self.S, xhat, u, self.clamp, counter, x_next, self.ell,
+                           self.hist)
+        else:
+            ops.smc_sample_voices(self.R, self.D, self.P, self.nsteps, self.S, xhat, u, self.clamp, self.voices, counter,
+                                  x_next, self.ell, self.hist)
         ops.smc_resample(self.G, self.P, self.nsteps, self.S, self.seed, self.m0, self.tau, self.ell, self.logW, self.logZ,
                          self.ess, self.nres, self.flag, self.anc, counter)
         gather(self.anc, self.flag, counter)
@@ -709,7 +856,8 @@ class _Chain:
     * z: z_path[:, t] of z_path [R, nsteps, L] and no encoder, else the encoder on [x_enc, w_enc] with eps of Philox stream 0
       from index r0 * L; under z_prior its zargs are zeroed.
     * the uniforms: the rows' own of stream 1 from index r0 * D, or those of rows noise_rows (_NoiseRows).
-    * the draw: free, under row t - S of the roll clamp [R, nsteps, D], or a particle filter's step (smc, an _Smc, which
+    * the draw: free, under row t - S of the roll clamp [R, nsteps, D] -- or of a Constraints with voice counts, whose
+      frames clv_bernoulli_sample_voices draws given their count --, or a particle filter's step (smc, an _Smc, which
       brings its own roll and S) followed by the ancestor gather of the rows' carried buffers.
     * dec_prev, what x_dec holds at the next step: 'sample'; 'enc_input', this step's x_enc (the decoder then lags the
       encoder by one frame: cl_vae's generator, and a re-decoding on its source's history); 'shared', x_dec IS x_enc
@@ -728,7 +876,7 @@ class _Chain:
         self.inv_T, self.Tz = (1.0, 1.0) if temper is None else temper
         self.sources, self.z_path, self.z_prior, self.seed_frames = sources, z_path, z_prior, seed_frames
         self.history, self.dec_prev = (None, dec_prev) if isinstance(dec_prev, str) else (dec_prev, 'history')
-        self.clamp, self.S, self.smc, self.t0 = clamp, S, smc, int(t0)
+        (self.clamp, self.voices), self.S, self.smc, self.t0 = clamp_parts(clamp), S, smc, int(t0)
         if z_path is None:
             self.x_enc, self.eps = new(D) if x_enc is None else x_enc, new(L)
         self.x_dec = self.x_enc if self.dec_prev == 'shared' else new(D) if x_dec is None else x_dec
@@ -761,6 +909,8 @@ class _Chain:
         self.noise.draw(self.u, self.seed, c, self.t0)
         if self.smc is not None:
             self.smc.step(rows.xhat, self.u, c, self.x_next, self.gather)
+        elif self.voices is not None:
+            ops.bernoulli_sample_voices(R * D, D, T, self.S, rows.xhat, self.u, self.clamp, self.voices, c, self.x_next)
         elif self.clamp is None:
             ops.bernoulli_sample(R * D, rows.xhat, self.u, self.x_next)
         else:                   # the row of step counter - S: none for the seed steps and the bridge
@@ -821,6 +971,9 @@ class _Generate:
         bytes or more, T * D * 4 >= 2^32 or a zout of 3 * 2^32 entries or more takes the chain.  Returns Xs [N, T, D];
         xhat_out [N, T, D] receives the unclamped (tempered) probabilities; zout [3, N, T, L] the latents
         (z_mean, z_log_var, z) of every frame.
+        clamp may be a Constraints: without voices it is its roll; with voice counts every returned frame is
+        drawn given its count on the frame chain -- persistent=True then takes the chain too: the persistent kernels do not
+        carry the count.
         cl_vae reads frames as on / off: ValueError (binary_frames) for sources or an x0 with an entry other than 0 and 1,
         on both routes and before anything is launched.  cl_vrnn takes any float."""
         cfg, d = self.cfg, self.device
@@ -832,7 +985,7 @@ class _Generate:
         if zout is not None:
             _zout_ok(zout, N, T, L)
         Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
-        if persistent and self._vary_fits(clamp, T, zout) and self._persistent_ok():
+        if persistent and not isinstance(clamp, Constraints) and self._vary_fits(clamp, T, zout) and self._persistent_ok():
             self._vary_op(N, T, D, cfg['H'], L, cfg['C'], self._family_flag(), hist_source, seed, sources, x0, w_enc, w_dec,
                           *self._weights(), Xs, zout, xhat_out, clamp=clamp, temper=temper)
             return Xs
@@ -851,6 +1004,9 @@ class _Generate:
         csrc/vae_generate.hip / csrc/generate.hip); else the frame chain, captured once and replayed per frame (cl_vae:
         N <= batch size), reading z[:, t] and history[:, t-1] through the device step counter.  N*T*L or N*T*D of 2^32 or
         more takes the chain.  Returns Xs [N, T, D]; xhat_out [N, T, D] receives the unclamped (tempered) probabilities.
+        clamp may be a Constraints: without voices it is its roll; with voice counts every returned frame is
+        drawn given its count on the frame chain -- persistent=True then takes the chain too: the persistent kernels do not
+        carry the count.
         cl_vae reads frames as on / off: ValueError (binary_frames) for an x0 or a given history with an entry other than
         0 and 1, on both routes and before anything is launched.  cl_vrnn takes any float."""
         cfg, d = self.cfg, self.device
@@ -860,7 +1016,8 @@ class _Generate:
         self._check_frames(x0=x0, history=hist)
         N, T = int(z.shape[0]), int(z.shape[1])
         Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
-        if persistent and max(N * T * L, N * T * D) < 2 ** 32 and self._persistent_ok():
+        if persistent and not isinstance(clamp, Constraints) and max(N * T * L, N * T * D) < 2 ** 32 \
+                and self._persistent_ok():
             self._decode_op(N, T, D, cfg['H'], L, cfg['C'], self._family_flag(), seed, z, x0, hist, w_dec, noise_rows,
                             *self._weights(encoder=False), Xs, xhat_out, clamp=clamp, inv_T=inv_T)
             return Xs
@@ -880,6 +1037,9 @@ class _Generate:
         sample of step S+j; the seed steps and the bridge carry no constraint and no weight; a chunk holds any number of
         rows.  `chunk`: at most that many melodies per pass; the Philox keys follow the global row, so the result does not
         depend on the chunking.  Returns SmcResult (Xs [N, n_out, nsteps, D]).
+        clamp may be a Constraints with voice counts, with or without a roll: a counted frame's weight
+        increment gains log P(count in range | forced notes), and log_evidence estimates log p(forced notes and every
+        frame's count in its range | seed, w).
         w=None, w_prior=WPrior: every particle draws its own w from the prior and carries it with its state (cl_vrnn's seed
         steps run under it too, unweighted), so the filter targets p(w, free notes | seed, constraints) (DESIGN.md 12);
         returns SmcKeyResult.
@@ -950,6 +1110,9 @@ class VaeGenerate(_Generate):
         sequence (csrc/vae_generate.hip; any N); otherwise the layer chain captured once as a hipGraph and replayed per
         frame (N <= batch size).  Same noise, same samples either way.  clamp: constraint roll [N,nsteps,D] (clamp_roll;
         row t constrains frame t, which is then fed back like a sampled one: clamped ancestral sampling).
+        clamp may be a Constraints: without voices it is its roll; with voice counts every returned frame is
+        drawn given its count on the frame chain -- persistent=True then takes the chain too: the persistent kernels do not
+        carry the count.
         temperature, z_temperature (temper_args): sample from the tempered model, x_hat = sigmoid(logit /
         temperature) and z = mean + exp(lv / 2) * z_temperature * eps, with the same Philox draws; xhat_out then holds the
         tempered probabilities.  Both 1.0 (default): exactly the untempered launches.
@@ -984,7 +1147,7 @@ class VaeGenerate(_Generate):
             binary_frames(x_seed=x_seed)
             x_in = hist = x_seed.to(**f).contiguous()
         w = w.to(**f).contiguous()
-        if not (persistent and self._persistent_ok()):
+        if not (persistent and not isinstance(clamp, Constraints) and self._persistent_ok()):
             return self._generate_frames(x_in, hist, w, nsteps, seed, use_graph, z_prior, clamp, temper, t0, return_state)
         Xs = torch.zeros(N, nsteps, D, **f)
         head = (N, nsteps, D, cfg['H'], cfg['L'], cfg['C'], cfg['use_x_prev'], z_prior, seed)
@@ -1101,6 +1264,9 @@ class VrnnGenerate(_Generate):
         clamp: constraint roll [N,nsteps,D] (engine_generate.clamp_roll): row j constrains the returned frame Xs[:, j],
         drawn at step S+j; the bridge sample of step S-1 stays free (clamped ancestral sampling).  The
         persistent kernel addresses the roll in 32 bits: a roll of 2^32 bytes or more takes the frame chain.
+        clamp may be a Constraints: without voices it is its roll; with voice counts every returned frame is
+        drawn given its count on the frame chain -- persistent=True then takes the chain too: the persistent kernels do not
+        carry the count.
         temperature, z_temperature (temper_args): sample from the tempered model, x_hat = sigmoid(logit /
         temperature) and z = mean + exp(lv / 2) * z_temperature * eps, with the same Philox draws (runs that differ only in
         the temperature share their uniforms); xhat_out then holds the tempered probabilities.  Both 1.0 (default):
@@ -1126,8 +1292,8 @@ class VrnnGenerate(_Generate):
         clamp = clamp_roll(clamp, N, nsteps, cfg['D'], self.device)
         if clamp is not None and nsteps == 0:
             clamp = None                # nothing is returned, so nothing is constrained
-        if clamp is not None and clamp.numel() >= 2 ** 32:
-            persistent = False
+        if clamp is not None and (isinstance(clamp, Constraints) or clamp.numel() >= 2 ** 32):
+            persistent = False          # voice counts run on the frame chain; so does a roll past 32-bit addressing
         if resume:
             x_seed = x_seed.to(dtype=torch.float32, device=self.device)
             w = w.to(dtype=torch.float32, device=self.device)

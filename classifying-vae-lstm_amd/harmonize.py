@@ -38,6 +38,21 @@ def voice_constraints(roll, voice='top', fence=True):
     return out
 
 
+def voice_counts(voices, source_rolls, roll=None):
+    """harmonize's voices argument as an engine_generate.Constraints over `roll`: an int k, a pair (lo, hi), or 'source'
+    (every frame as many sounding notes as the frame of source_rolls)"""
+    from .engine_generate import Constraints
+    if isinstance(voices, str):
+        if voices != 'source':
+            raise ValueError("voices must be an int, a pair (lo, hi) or 'source', got %r" % (voices,))
+        return Constraints.as_in(source_rolls, roll=roll)
+    if isinstance(voices, (tuple, list)):
+        if len(voices) != 2:
+            raise ValueError("voices must be an int, a pair (lo, hi) or 'source', got %r" % (voices,))
+        return Constraints.between(voices[0], voices[1], roll=roll)
+    return Constraints.exactly(voices, roll=roll)
+
+
 INFER_KEY = ('discrete', 'continuous')
 
 
@@ -53,7 +68,8 @@ def default_w_prior(model, N, infer_key):
 
 
 def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fence=True, z_prior=False, particles=None,
-              resample_threshold=0.5, return_evidence=False, infer_key=None, w_prior=None, temperature=1.0, z_temperature=1.0):
+              resample_threshold=0.5, return_evidence=False, infer_key=None, w_prior=None, temperature=1.0, z_temperature=1.0,
+              voices=None):
     """Generate len(seeds) sequences that keep the `voice` of source_rolls [N, nsteps, 88] and fill in the rest, with the
     frame loop on the device.  seeds: cl_vrnn [N, S, 88] teacher-forced frames (the first source frame follows them),
     cl_vae [N, 88] (frame 0 of the sequence; the first source frame is frame 1).  Returns [N, nsteps, 88] float64.
@@ -65,7 +81,12 @@ def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fenc
     w_posterior [N, nsteps, C] (after each frame) and the label w_out [N, C] of each returned sequence, float64.
     temperature, z_temperature: harmonize with the tempered model (note logits divided by temperature, latent
     noise scaled by z_temperature); evidence and key posterior are then that tempered model's, not the trained model's
-    unless both are 1."""
+    unless both are 1.
+    voices: how many notes sound in every returned frame, the kept voice included -- an int k (exactly k), a
+    pair (lo, hi), or 'source' (as many as the source frame has).  Each frame is then drawn exactly from p(frame | the kept
+    voice, count in range); with particles the evidence becomes log p(voice and texture | seed, w).  The call runs on the
+    frame chain or in the filter.  ValueError for a frame that cannot be had: the kept voice needs lo - 1 free notes on its
+    open side (with `fence`), and counts go up to 15."""
     from .engine import VaeEngine
     source_rolls = np.asarray(source_rolls)
     if source_rolls.ndim != 3:
@@ -85,6 +106,8 @@ def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fenc
     elif w_vals is None:
         raise ValueError("harmonize needs w_vals (or infer_key with particles)")
     clamp = voice_constraints(source_rolls, voice, fence)
+    if voices is not None:
+        clamp = voice_counts(voices, source_rolls, clamp)
     nsteps = source_rolls.shape[1]
     extra.update(temperature=temperature, z_temperature=z_temperature)
     if isinstance(model.engine, VaeEngine):

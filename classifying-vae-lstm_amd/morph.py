@@ -6,7 +6,7 @@ both pieces are encoded, their paths AND their labels mixed linearly on the devi
 import numpy as np
 import torch
 
-from .engine_generate import lerp_rows, temper_args
+from .engine_generate import Constraints, lerp_rows, temper_args
 from .vary import infer_labels
 
 
@@ -91,7 +91,8 @@ def morph(model, a, b, steps=8, w_a=None, w_b=None, z_temperature=0.0, common_no
     common_noise=True: every row of a pair draws the note uniforms of the pair's first row (noise_rows), so the rows differ
     through the path and the label only, not through the sampling noise.  Global row pair * (steps + 1) + k holds step k: with
     common_noise=False row 0 of a pair is vary(a) and row `steps` is vary(b) at those rows, bit for bit.
-    clamp: uint8 roll [pairs, T, 88] (or [T, 88]) applied to every row of its pair.  ValueError for pieces of unequal
+    clamp: uint8 roll [pairs, T, 88] (or [T, 88]) applied to every row of its pair, or a Constraints over the pairs (roll
+    [pairs, T, 88] and / or voice counts; the decoding then runs on the frame chain).  ValueError for pieces of unequal
     length or count, steps < 1, wrong shapes, a bool or out-of-range temperature."""
     if isinstance(steps, (bool, np.bool_)) or int(steps) != steps or steps < 1:
         raise ValueError("steps must be an integer >= 1, got %r" % (steps,))
@@ -105,7 +106,9 @@ def morph(model, a, b, steps=8, w_a=None, w_b=None, z_temperature=0.0, common_no
     cfg, d = eng.cfg, eng.device
     pairs, T, D = a.shape
     L, C, R = cfg['L'], cfg['C'], pairs * (K + 1)
-    if clamp is not None:
+    if isinstance(clamp, Constraints):      # roll and voice counts per pair, repeated for the pair's rows
+        clamp = clamp.repeat_rows(K + 1).resolve(R, T, D, d)
+    elif clamp is not None:
         clamp = np.asarray(clamp)
         if clamp.ndim == 2:
             clamp = clamp[None]

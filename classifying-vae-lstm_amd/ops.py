@@ -822,6 +822,20 @@ def smc_sample(R, D, P, nsteps, S, p, u, clamp, step_dev, x, ell, hist):
                                     _ptr(hist), _stream()), "clv_smc_sample")
 
 
+def bernoulli_sample_voices(n, D, nsteps, S, p, u, clamp, voices, step_dev, x, logb=None):
+    """bernoulli_sample_clamped given each frame's voice count: voices [n/D, nsteps, 2] uint8 holds (lo, hi)
+    per returned frame, (0, 255) = free; clamp (the roll) may be None; logb [n/D] fp64 (optional) = log P(count in range)."""
+    check(_lib.lib().clv_bernoulli_sample_voices(n, D, nsteps, S, _ptr(p), _ptr(u), _ptr(clamp), _ptr(voices), _ptr(step_dev),
+                                                 _ptr(x), _ptr(logb), _stream()), "clv_bernoulli_sample_voices")
+
+
+def smc_sample_voices(R, D, P, nsteps, S, p, u, clamp, voices, step_dev, x, ell, hist, logb=None):
+    """smc_sample given each frame's voice count: voices [R/P, nsteps, 2] uint8 per melody, as the roll (which
+    may be None); ell gains log P(count in range | forced notes), which logb [R] fp64 (optional) also receives."""
+    check(_lib.lib().clv_smc_sample_voices(R, D, P, nsteps, S, _ptr(p), _ptr(u), _ptr(clamp), _ptr(voices), _ptr(step_dev),
+                                           _ptr(x), _ptr(ell), _ptr(hist), _ptr(logb), _stream()), "clv_smc_sample_voices")
+
+
 def smc_resample(G, P, nsteps, S, seed, m0, tau, ell, logW, logZ, ess, nres, flag, anc, step_dev):
     """per melody m < G: log Z, normalized log weights, ESS [G, nsteps], systematic resampling below tau * P, ancestors
     anc [nsteps, G*P] of step *step_dev - S; m0 = global index of melody 0 (the resampling uniform's Philox index)."""

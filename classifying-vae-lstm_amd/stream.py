@@ -65,7 +65,8 @@ class Stream:
 
     def advance(self, nsteps, w=None, clamp=None, temperature=1.0, z_temperature=1.0):
         """the next nsteps frames [N, nsteps, 88] (float64).  w [N, C] replaces the label from this call on; clamp: a roll
-        uint8 [N, nsteps, 88] for these frames (row j constrains frame j of this call); temperature, z_temperature as in
+        uint8 [N, nsteps, 88] for these frames (row j constrains frame j of this call), or a Constraints with voice counts for
+        them; temperature, z_temperature as in
         generate_samples_device, for this call."""
         if isinstance(nsteps, (bool, np.bool_)) or int(nsteps) != nsteps or nsteps < 1:
             raise ValueError("nsteps must be an integer >= 1, got %r" % (nsteps,))

@@ -1029,6 +1029,29 @@ int clv_smc_w_posterior(int G, int P, int C, int nsteps, int S, const double* lo
                         double* out, void* stream);
 int clv_smc_take_w(int G, int P, int C, int n_out, const int32_t* picks, const float* wr, float* w_out, void* stream);
 
+/* --------------------------------------------------- voice-count constraints --
+ * Sampling a frame given how many of its notes sound: the voices twins of clv_bernoulli_sample_clamped and
+ * clv_smc_sample.  voices [rows of the roll, nsteps, 2] uint8 holds (lo, hi) per returned frame, addressed as the roll is
+ * (per sequence; per MELODY, row r / P, in the filter); clamp may be NULL (no roll).  With k = *step_dev - S and
+ * 0 <= k < nsteps, a frame whose pair has lo <= hi <= 15 is drawn from p(frame | roll row, lo <= count <= hi) exactly:
+ *   q_j = clip(p_j, 1e-7, 1 - 1e-7) in float32, widened; 0 / 1 where the roll forces the note; then in fp64
+ *   B[D][c] = [lo <= c <= hi], B[j][c] = (1 - q_j) B[j+1][c] + q_j B[j+1][c+1] for j = D-1 .. 0 (B[.][hi+1] = 0);
+ *   notes ascending, c = 0: a forced note takes its value, a free one a = q_j B[j+1][c+1], b = (1 - q_j) B[j+1][c],
+ *   x_j = 0 if a == 0, 1 if b == 0, else [(double)u_j <= a / B[j][c]]; c += x_j.
+ * Every other pair -- (0, 255) is the documented one -- leaves the frame free: the twin's own draw, bit for bit; so do the
+ * seed steps, the bridge and steps past the end (k outside [0, nsteps)).  The entries cannot read the device-side pairs:
+ * the caller keeps lo <= hi <= 15 or (0, 255), and every constrained frame feasible (forced-on notes <= hi, forced-on +
+ * free notes >= lo).  logb [rows] fp64 (optional) receives log B[0][0] = log P(lo <= count <= hi | roll row), 0 for a
+ * free frame.  clv_smc_sample_voices also writes hist as its twin and ell[r] = (the twin's sum over forced notes of
+ * log q) + log B[0][0].  One wave per row, lanes over the counts, no LDS, no atomics: bitwise reproducible.
+ * CLV_EINVAL unless D <= 128, the twin's conditions hold (n % D == 0; R % P == 0), n / D fits an int32 and no pointer
+ * other than clamp and logb is NULL. */
+int clv_bernoulli_sample_voices(int64_t n, int D, int nsteps, int S, const float* p, const float* u, const uint8_t* clamp,
+                                const uint8_t* voices, const int32_t* step_dev, float* x, double* logb, void* stream);
+int clv_smc_sample_voices(int R, int D, int P, int nsteps, int S, const float* p, const float* u, const uint8_t* clamp,
+                          const uint8_t* voices, const int32_t* step_dev, float* x, double* ell, uint8_t* hist, double* logb,
+                          void* stream);
+
 /* ------------------------------------------------------------- key tracking --
  * The label head at every offset of a piece, and its HMM smoothing.
  *

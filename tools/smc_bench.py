@@ -3,8 +3,10 @@ frames through VrnnEngine.generate_smc, against the clamped frame chain (generat
 G * P rows, which runs the same frame launches without the filter.  Runs alternate; medians are printed as one JSON line.
 --infer_key adds the filter with a label per particle on the same rows, in the same alternation: a uniform
 categorical prior over the keys and / or the model's own logistic-normal prior, each against the fixed-label filter.
+--voices LO[:HI] adds the filter and the clamped chain under that voice count per frame, the top-voice roll
+kept, in the same alternation: clv_smc_sample_voices / clv_bernoulli_sample_voices in place of their twins.
 
-    python tools/smc_bench.py [--melodies 64] [--particles 128] [--nsteps 64] [--reps 5] [--infer_key both]
+    python tools/smc_bench.py [--melodies 64] [--particles 128] [--nsteps 64] [--reps 5] [--infer_key both] [--voices 4]
 """
 import argparse
 import json
@@ -18,7 +20,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.engine import VrnnEngine  # noqa: E402
-from clvae_amd.engine_generate import WPrior  # noqa: E402
+from clvae_amd.cli import parse_voices  # noqa: E402
+from clvae_amd.engine_generate import Constraints, WPrior  # noqa: E402
 from clvae_amd.harmonize import FREE  # noqa: E402
 from clvae_amd.initializers import init_weights  # noqa: E402
 
@@ -30,6 +33,7 @@ ap.add_argument('--seed_frames', type=int, default=1)
 ap.add_argument('--tau', type=float, default=0.5)
 ap.add_argument('--reps', type=int, default=5)
 ap.add_argument('--infer_key', choices=('categorical', 'logistic_normal', 'both'), default=None)
+ap.add_argument('--voices', default=None, help='LO[:HI]: also run both samplers under this voice count per frame')
 args = ap.parse_args()
 dev = torch.device('cuda:0')
 G, P, T, S = args.melodies, args.particles, args.nsteps, args.seed_frames
@@ -68,8 +72,17 @@ def chain():
     return eng.generate(seeds_rows, wv_rows, T, seed=2, persistent=False, clamp=clamp_rows)
 
 
-names = ['smc', 'chain'] + key_modes
-run = {'smc': smc, 'chain': chain, 'categorical': lambda: smc('categorical'), 'logistic_normal': lambda: smc('logistic_normal')}
+voice_modes = []
+if args.voices is not None:
+    lo, hi = parse_voices(args.voices)
+    counted = Constraints.between(lo, hi, roll=clamp).resolve(G, T, 88, dev)
+    counted_rows = Constraints.between(lo, hi, roll=clamp_rows).resolve(G * P, T, 88, dev)
+    voice_modes = ['smc_voices', 'chain_voices']
+
+names = ['smc', 'chain'] + key_modes + voice_modes
+run = {'smc': smc, 'chain': chain,
+       'smc_voices': lambda: eng.generate_smc(seeds, wv, T, counted, P, resample_threshold=args.tau, seed=2),
+       'chain_voices': lambda: eng.generate(seeds_rows, wv_rows, T, seed=2, persistent=False, clamp=counted_rows), 'categorical': lambda: smc('categorical'), 'logistic_normal': lambda: smc('logistic_normal')}
 for name in names:
     run[name]()
 torch.cuda.synchronize()
@@ -99,6 +112,17 @@ for mode in key_modes:
         'mean_log_evidence_per_frame': float(k.log_evidence.mean()) / T,
         'mean_max_key_posterior': float(k.w_posterior[:, -1].max(dim=1).values.mean()),
     }
-if key_modes:
+if voice_modes:
+    k = last['smc_voices']
+    res['voices'] = {
+        'range': [lo, hi], 'smc_s': med['smc_voices'], 'chain_s': med['chain_voices'],
+        'smc_over_roll_only_pct': 100 * (med['smc_voices'] / med['smc'] - 1),
+        'chain_over_roll_only_pct': 100 * (med['chain_voices'] / med['chain'] - 1),
+        'smc_all_s': t['smc_voices'], 'chain_all_s': t['chain_voices'], 'roll_only_chain_all_s': t['chain'],
+        'resamples_per_melody': float(k.resamples.float().mean()),
+        'mean_log_evidence_per_frame': float(k.log_evidence.mean()) / T,
+        'counts_in_range': bool(((k.Xs.sum(-1) >= lo) & (k.Xs.sum(-1) <= hi)).all()),
+    }
+if key_modes or voice_modes:
     res['smc_all_s'] = t['smc']
 print(json.dumps(res))
