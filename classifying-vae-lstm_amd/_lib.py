@@ -252,6 +252,10 @@ SIGNATURES = {
     "clv_smc_init_w": (_i, [_i, _i, _i, _i, _u64, _i64, _p, _p, _p, _p, _p]),
     "clv_smc_w_posterior": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "clv_smc_take_w": (_i, [_i, _i, _i, _i, _p, _p, _p, _p]),
+    "clv_smc_pin_z": (_i, [_i, _i, _i, _i, _p, _p, _p, _p]),
+    "clv_smc_pin_frame": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "clv_smc_resample_conditional": (_i, [_i, _i, _i, _i, _u64, _i64, _d] + [_p] * 9),
+    "clv_smc_backtrack_path": (_i, [_i] * 6 + [_p] * 10),
     "clv_bernoulli_sample_voices": (_i, [_i64, _i, _i, _i] + [_p] * 8),
     "clv_smc_sample_voices": (_i, [_i] * 5 + [_p] * 10),
     "clv_key_track_windows": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _u64, _i64, _p, _p, _p]),

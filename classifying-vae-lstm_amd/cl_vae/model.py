@@ -60,7 +60,8 @@ def generate_sample(dec_model, w_enc_model, z_enc_model, x_seed, nsteps, w_val=N
 
 def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_prior=False, clamp=None, particles=None,
                             resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False,
-                            temperature=1.0, z_temperature=1.0, state=None, return_state=False):
+                            temperature=1.0, z_temperature=1.0, state=None, return_state=False, sweeps=None,
+                            return_renewed=False):
     """N sequences at once with the frame loop on the device (VaeEngine.generate: one captured hipGraph replayed per
     frame, Philox noise instead of np.random: same distribution, different draws).  x_seeds [N,D], w_vals [N,C];
     returns [N,nsteps,D] float64 like generate_sample does per sequence.  clamp: numpy / torch uint8 [N,nsteps,D]
@@ -82,9 +83,16 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, use_z_p
     change from call to call (row t of a call's roll constrains that call's frame t).  state.select(index) branches a
     prefix.  The state is not written.  ValueError for a state together with particles, a state of the other family, a
     state whose N or width is not the call's, x_seeds together with a state, and a state.t + nsteps that passes the last
-    Philox step 2^32 - 1."""
+    Philox step 2^32 - 1.
+    sweeps=K (with particles): K sweeps of particle Gibbs (the engine's generate_gibbs) -- sweep 0 is the filter
+    above, every later sweep reruns it with one particle pinned to the path of the sweep before -- and the LAST sweep's path
+    is returned; return_evidence then returns sweep 0's evidence (the only unbiased one), return_renewed also renewed
+    [N,K,nsteps] bool (frame k of sweep s did not come from the pinned particle).  ValueError for sweeps without particles,
+    with w_prior, return_key or a state, and for return_renewed without sweeps."""
     temper_args(temperature, z_temperature)         # refused before the model's engine is asked for
     resume = {} if state is None and not return_state else dict(state=state, return_state=return_state, kind='cl_vae')
+    if sweeps is not None or return_renewed:
+        resume = dict(resume, sweeps=sweeps, return_renewed=return_renewed)
     return generate_samples_numpy(model.engine, x_seeds, nsteps, w_vals, seed=seed, z_prior=use_z_prior, clamp=clamp,
                                   particles=particles, resample_threshold=resample_threshold, return_evidence=return_evidence,
                                   w_prior=w_prior, return_key=return_key, temperature=temperature, z_temperature=z_temperature,

@@ -8,10 +8,10 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
-                           VARY_FLAGS, VOICES_FLAGS, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs,
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
+                           VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs,
                            voices_kwargs)
-from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, voice_constraints,  # noqa: E402
+from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, print_renewed, voice_constraints,  # noqa: E402
                                  voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
@@ -92,10 +92,12 @@ class Sampler:
             out = harmonize(self.model, seeds, sources, None if ws is None else np.vstack(ws), voice=voice_of(self.args),
                             seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior, particles=particles,
                             return_evidence=particles is not None, **(dict(infer_key=infer_key) if infer_key else {}),
-                            **temperature_kwargs(self.args), voices=voices_kwargs(self.args))
+                            **temperature_kwargs(self.args), voices=voices_kwargs(self.args), **gibbs_kwargs(self.args))
         rolls = out[0] if particles is not None else out
         if particles is not None:
             print_evidence(names, out[1], self.args.t)
+            if gibbs_kwargs(self.args):     # --sweeps: out = (the last sweep's rolls, sweep 0's evidence, renewed)
+                print_renewed(names, out[2])
             if infer_key:
                 print_key_posterior(names, out[2], self.data.key_map)
         for roll, src, name in zip(rolls, sources, names):
@@ -201,4 +203,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vae.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS + VOICES_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS).parse_args())

@@ -237,7 +237,8 @@ class Encoder:
 
 def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
                             resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False,
-                            temperature=1.0, z_temperature=1.0, state=None, return_state=False):
+                            temperature=1.0, z_temperature=1.0, state=None, return_state=False, sweeps=None,
+                            return_renewed=False):
     """Batched, device-resident counterpart of generate_sample: N seeds at once, the whole frame loop as
     replays of one captured hipGraph, Philox noise instead of np.random (so the draws differ from the numpy
     path, the distribution does not).  x_seeds [N,S,88] (S >= 0 teacher-forced frames), w_vals [N,C].
@@ -263,9 +264,16 @@ def generate_samples_device(model, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     arrives in pieces: row j of a call's roll constrains that call's frame j).  state.select(index) branches a prefix.
     The state is not written.  ValueError for a state together with particles (the filter's per-particle state is not
     carried), a state of the other family, a state whose N or widths are not the call's, and a state.t + S + nsteps that
-    passes the last Philox step 2^32 - 1."""
+    passes the last Philox step 2^32 - 1.
+    sweeps=K (with particles): K sweeps of particle Gibbs (the engine's generate_gibbs) -- sweep 0 is the filter
+    above, every later sweep reruns it with one particle pinned to the path of the sweep before -- and the LAST sweep's path
+    is returned; return_evidence then returns sweep 0's evidence (the only unbiased one), return_renewed also renewed
+    [N,K,nsteps] bool (frame k of sweep s did not come from the pinned particle).  ValueError for sweeps without particles,
+    with w_prior, return_key or a state, and for return_renewed without sweeps."""
     temper_args(temperature, z_temperature)         # refused before the model's engine is asked for
     resume = {} if state is None and not return_state else dict(state=state, return_state=return_state, kind='cl_vrnn')
+    if sweeps is not None or return_renewed:
+        resume = dict(resume, sweeps=sweeps, return_renewed=return_renewed)
     return generate_samples_numpy(model.engine, x_seeds, nsteps, w_vals, seed=seed, z_prior=z_prior, clamp=clamp,
                                   particles=particles, resample_threshold=resample_threshold, return_evidence=return_evidence,
                                   w_prior=w_prior, return_key=return_key, temperature=temperature, z_temperature=z_temperature,

@@ -8,10 +8,10 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
-                           VARY_FLAGS, VOICES_FLAGS, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs,
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
+                           VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs,
                            voices_kwargs)
-from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, voice_constraints,  # noqa: E402
+from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, print_renewed, voice_constraints,  # noqa: E402
                                  voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
@@ -92,11 +92,13 @@ def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice
         else:
             out = harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0),
                             particles=particles, return_evidence=particles is not None, **temperature_kwargs(args),
-                            voices=voices_kwargs(args))
+                            voices=voices_kwargs(args), **gibbs_kwargs(args))
     rolls = list(out[0] if particles is not None else out)
     if particles is not None:
         names = ['%s_%d' % (args.run_name, j) for j in range(len(rolls))]
         print_evidence(names, out[1], t)
+        if gibbs_kwargs(args):      # --sweeps: out = (the last sweep's rolls, sweep 0's evidence, renewed)
+            print_renewed(names, out[2])
         if infer_key:
             print_key_posterior(names, out[2], P.key_map)
     for j, (i, roll) in enumerate(zip(picks, rolls)):
@@ -183,4 +185,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vrnn.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS + VOICES_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS).parse_args())

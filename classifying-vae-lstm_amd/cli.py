@@ -167,6 +167,21 @@ VOICES_FLAGS = [
 ]
 
 
+# particle Gibbs (not in the reference): sweeps of the particle filter on a retained path
+GIBBS_FLAGS = [
+    Flag(('--sweeps',), int, None, 'with --particles: this many sweeps of particle Gibbs; every sweep after the first reruns '
+                                   'the filter with one particle pinned to the path of the sweep before, so a few particles '
+                                   'and several sweeps reach what one pass of many particles would; prints how much of the '
+                                   'path each sweep renewed (not with --infer_key)'),
+]
+
+
+def gibbs_kwargs(args):
+    """--sweeps as keyword arguments of harmonize: empty without the flag (also for parsers without it)"""
+    k = getattr(args, 'sweeps', None)
+    return {} if k is None else dict(sweeps=k, return_renewed=True)
+
+
 def parse_voices(text):
     """--voices' LO[:HI] -> (lo, hi); ValueError unless both are integers with 0 <= lo <= hi <= 15"""
     lo, sep, hi = str(text).partition(':')
@@ -240,8 +255,8 @@ def morph_kwargs(args):
 
 
 class _Parser(argparse.ArgumentParser):
-    """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles, a
-    temperature other than 1 not with --host_loop (the host loop is the reference's and has none), --vary not with
+    """argparse with the rules between flags: --particles only with --harmonize, --infer_key only with --particles, --sweeps >= 1 only
+    with --particles and not with --infer_key, a temperature other than 1 not with --host_loop (the host loop is the reference's and has none), --vary not with
     --harmonize or --host_loop, --to_key / --vary_history only with --vary, --morph >= 1 and not with --harmonize, --vary or
     --host_loop, --chunk >= 1 and a well-formed --modulate, neither with --particles, --vary, --morph or --host_loop, a
     well-formed --voices LO[:HI] and not with --host_loop"""
@@ -270,6 +285,14 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--particles must be >= 1')
         elif getattr(ns, 'infer_key', None):
             self.error('--infer_key needs --particles')
+        sweeps = getattr(ns, 'sweeps', None)
+        if sweeps is not None:
+            if particles is None:
+                self.error('--sweeps needs --particles')
+            if sweeps < 1:
+                self.error('--sweeps must be >= 1')
+            if getattr(ns, 'infer_key', None):
+                self.error('--sweeps pins no key: not with --infer_key')
         if getattr(ns, 'vary', False):
             if getattr(ns, 'harmonize', None):
                 self.error('--vary re-decodes whole pieces: not with --harmonize')

@@ -10,6 +10,10 @@
 // With a key prior every particle carries its own label row: clv_smc_init_w draws the rows once per chunk,
 // the gather moves them with the state, clv_smc_w_posterior (in the frame, after the gather) writes the weighted mean of
 // the rows, and clv_smc_take_w copies the rows of the returned paths.
+// Particle Gibbs reruns the filter with row m * P pinned to the path retained from the sweep before:
+// clv_smc_pin_z and clv_smc_pin_frame put that path's latents, frames and bridge into the pinned row, in the frame;
+// clv_smc_resample_conditional is clv_smc_resample with conditional multinomial resampling (one kernel body, two instances);
+// clv_smc_backtrack_path writes the lineage clv_smc_backtrack drew as the next retained path, latents included.
 // Every output element has one owner and no kernel uses atomics, so every result is bitwise reproducible.
 #include "common.h"
 #include "philox.h"
@@ -18,6 +22,7 @@ namespace clv {
 
 constexpr uint32_t SMC_STREAM = 0xFFFFFFFDu;        // trainer.py's stream map, next to the IW pair
 constexpr uint32_t SMC_W_STREAM = 0xFFFFFFFCu;      // the particles' keys: step 0 the categorical u0, step 1 the eps
+constexpr uint32_t GIBBS_STREAM = 0xFFFFFFFAu;      // a conditional sweep's own uniform per particle (0xFFFFFFFB: key_track)
 constexpr int SMC_MAX_C = 32;                        // classes of a label row (MAXC of the label kernels)
 constexpr int SMC_MAX_P = 1024;                      // particles per melody: one workgroup holds them
 constexpr int SMC_MAX_BUFS = 8;
@@ -119,6 +124,10 @@ __global__ __launch_bounds__(64 * SMC_ROWS) void smc_sample_kernel(int R, int D,
   }
 }
 
+// CONDITIONAL (particle Gibbs): row m * P is the retained path and keeps itself as its ancestor; every other
+// particle draws its own uniform (GIBBS_STREAM, index = its GLOBAL row) and takes the first q with cum[q] > u, the last
+// one if none -- conditional multinomial resampling.  Weights, log Z, ESS and the rule are the filter's.
+template <bool CONDITIONAL>
 __global__ __launch_bounds__(SMC_MAX_P) void smc_resample_kernel(int P, int nsteps, int S, uint64_t seed, int64_t m0,
                                                                  double tau, const double* ell, double* logW, double* logZ,
                                                                  double* ess, int32_t* nres, int32_t* flag, int32_t* anc,
@@ -144,8 +153,14 @@ __global__ __launch_bounds__(SMC_MAX_P) void smc_resample_kernel(int P, int nste
   if (resample) {
     block_inclusive_scan(mine ? exp(wn) : 0.0, cum, red);
     if (mine) {
-      const double u0 = smc_uniform(seed, m0 + m, k + S);
-      anc[(int64_t)k * R + r] = m * P + systematic_pick(cum, P, (double)P, u0 + (double)p);
+      if (CONDITIONAL) {
+        const double up = (double)philox_uniform_at((uint64_t)((m0 + m) * P + p), (uint32_t)seed, (uint32_t)(seed >> 32),
+                                                    GIBBS_STREAM, (uint32_t)(k + S));
+        anc[(int64_t)k * R + r] = m * P + (p == 0 ? 0 : systematic_pick(cum, P, 1.0, up));
+      } else {
+        const double u0 = smc_uniform(seed, m0 + m, k + S);
+        anc[(int64_t)k * R + r] = m * P + systematic_pick(cum, P, (double)P, u0 + (double)p);
+      }
       logW[r] = -logP;
     }
   } else if (mine) {
@@ -292,6 +307,74 @@ __global__ void smc_take_w_kernel(int n, int P, int C, int n_out, const int32_t*
   w_out[i] = wr[((int64_t)m * P + pick) * C + c];
 }
 
+// ---- particle Gibbs: a conditional sweep pins row m * P of every melody to the retained path ----
+// z[m * P, :] = z_ref[m, c, :] at chain step c = *step_dev (seed steps included); a thread per element of the G pinned rows
+__global__ void smc_pin_z_kernel(int n, int P, int L, int T, const float* z_ref, const int32_t* step_dev, float* z) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int c = *step_dev;
+  if (c < 0 || c >= T) return;
+  const int m = i / L, j = i - m * L;
+  z[(int64_t)m * P * L + j] = z_ref[((int64_t)m * T + c) * L + j];
+}
+
+// after the draw: at returned step k the pinned row's sample and its history row become x_ref[m, k, :]; at step S - 1
+// (S > 0) the sample becomes the retained bridge.  A wave per melody; no other row and no other step is touched.
+__global__ __launch_bounds__(64 * SMC_ROWS) void smc_pin_frame_kernel(int G, int P, int D, int nsteps, int S,
+                                                                     const uint8_t* x_ref, const float* bridge,
+                                                                     const int32_t* step_dev, float* x, uint8_t* hist) {
+  const int m = blockIdx.x * SMC_ROWS + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (m >= G) return;
+  const int k = *step_dev - S;
+  float* xr = x + (int64_t)m * P * D;
+  if (k >= 0 && k < nsteps) {
+    const uint8_t* src = x_ref + ((int64_t)m * nsteps + k) * D;
+    uint8_t* hr = hist + ((int64_t)k * G * P + (int64_t)m * P) * D;
+    for (int j = lane; j < D; j += 64) {
+      const uint8_t b = src[j];
+      xr[j] = (float)b;
+      hr[j] = b;
+    }
+  } else if (k == -1 && S > 0 && bridge) {
+    const float* src = bridge + (int64_t)m * D;
+    for (int j = lane; j < D; j += 64) xr[j] = src[j];
+  }
+}
+
+// the path of pick picks[m] walked back as smc_backtrack_kernel walks it, written as the next retained path: frames
+// (uint8), the latents of every chain step, the bridge; renewed[m, k] = the row frame k came from is not the pinned one.
+// Seed steps and the bridge come from the lineage's root, the row at k = 0: nothing resamples before it.
+__global__ __launch_bounds__(64 * SMC_ROWS) void smc_backtrack_path_kernel(int G, int P, int nsteps, int S, int D, int L,
+                                                                          const int32_t* picks, const int32_t* anc,
+                                                                          const uint8_t* hist, const float* zhist,
+                                                                          const float* bridge_rows, uint8_t* x_ref,
+                                                                          float* z_ref, float* bridge_ref, uint8_t* renewed) {
+  const int m = blockIdx.x * SMC_ROWS + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (m >= G) return;
+  const int64_t R = (int64_t)G * P, first = (int64_t)m * P;
+  const int T = S + nsteps;
+  int64_t r = first + min(max(picks[m], 0), P - 1);
+  for (int k = nsteps - 1; k >= 0; --k) {
+    r = min(max((int64_t)anc[(int64_t)k * R + r], first), first + P - 1);     // a melody's lineage stays in its rows
+    const uint8_t* h = hist + ((int64_t)k * R + r) * D;
+    uint8_t* xo = x_ref + ((int64_t)m * nsteps + k) * D;
+    for (int j = lane; j < D; j += 64) xo[j] = h[j];
+    const float* zs = zhist + ((int64_t)(S + k) * R + r) * L;
+    float* zo = z_ref + ((int64_t)m * T + S + k) * L;
+    for (int j = lane; j < L; j += 64) zo[j] = zs[j];
+    if (lane == 0) renewed[(int64_t)m * nsteps + k] = r != first ? 1 : 0;
+  }
+  for (int t = 0; t < S; ++t) {
+    const float* zs = zhist + ((int64_t)t * R + r) * L;
+    float* zo = z_ref + ((int64_t)m * T + t) * L;
+    for (int j = lane; j < L; j += 64) zo[j] = zs[j];
+  }
+  if (S > 0 && bridge_rows && bridge_ref)
+    for (int j = lane; j < D; j += 64) bridge_ref[(int64_t)m * D + j] = bridge_rows[r * D + j];
+}
+
 static inline int smc_block(int P) { return (P + 63) / 64 * 64; }
 
 }  // namespace clv
@@ -319,8 +402,59 @@ extern "C" int clv_smc_resample(int G, int P, int nsteps, int S, uint64_t seed, 
   if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   ProfScope pr("smc_resample", s);
-  hipLaunchKernelGGL(smc_resample_kernel, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, S, seed, m0, tau, ell, logW, logZ,
-                     ess, nres, flag, anc, step_dev, G * P);
+  hipLaunchKernelGGL(smc_resample_kernel<false>, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, S, seed, m0, tau, ell, logW,
+                     logZ, ess, nres, flag, anc, step_dev, G * P);
+  return launch_status();
+}
+
+extern "C" int clv_smc_resample_conditional(int G, int P, int nsteps, int S, uint64_t seed, int64_t m0, double tau,
+                                            const double* ell, double* logW, double* logZ, double* ess, int32_t* nres,
+                                            int32_t* flag, int32_t* anc, const int32_t* step_dev, void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || nsteps <= 0 || S < 0 || m0 < 0 || !(tau >= 0.0 && tau <= 1.0) || !ell ||
+      !logW || !logZ || !ess || !nres || !flag || !anc || !step_dev)
+    return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_resample_conditional", s);
+  hipLaunchKernelGGL(smc_resample_kernel<true>, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, S, seed, m0, tau, ell, logW,
+                     logZ, ess, nres, flag, anc, step_dev, G * P);
+  return launch_status();
+}
+
+extern "C" int clv_smc_pin_z(int G, int P, int L, int T, const float* z_ref, const int32_t* step_dev, float* z,
+                             void* stream) {
+  if (G <= 0 || P <= 0 || L <= 0 || T <= 0 || !z_ref || !step_dev || !z) return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX || (int64_t)G * L > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_pin_z", s);
+  const int n = G * L;
+  hipLaunchKernelGGL(smc_pin_z_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, P, L, T, z_ref, step_dev, z);
+  return launch_status();
+}
+
+extern "C" int clv_smc_pin_frame(int G, int P, int D, int nsteps, int S, const uint8_t* x_ref, const float* bridge,
+                                 const int32_t* step_dev, float* x, uint8_t* hist, void* stream) {
+  if (G <= 0 || P <= 0 || D <= 0 || nsteps <= 0 || S < 0 || !x_ref || !step_dev || !x || !hist) return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_pin_frame", s);
+  hipLaunchKernelGGL(smc_pin_frame_kernel, dim3((G + SMC_ROWS - 1) / SMC_ROWS), dim3(64 * SMC_ROWS), 0, s, G, P, D, nsteps,
+                     S, x_ref, bridge, step_dev, x, hist);
+  return launch_status();
+}
+
+extern "C" int clv_smc_backtrack_path(int G, int P, int nsteps, int S, int D, int L, const int32_t* picks,
+                                      const int32_t* anc, const uint8_t* hist, const float* zhist, const float* bridge_rows,
+                                      uint8_t* x_ref, float* z_ref, float* bridge_ref, uint8_t* renewed, void* stream) {
+  if (G <= 0 || P <= 0 || nsteps <= 0 || S < 0 || D <= 0 || L <= 0 || !picks || !anc || !hist || !zhist || !x_ref ||
+      !z_ref || !renewed)
+    return CLV_EINVAL;
+  if (S > 0 && (!bridge_rows != !bridge_ref)) return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_backtrack_path", s);
+  hipLaunchKernelGGL(smc_backtrack_path_kernel, dim3((G + SMC_ROWS - 1) / SMC_ROWS), dim3(64 * SMC_ROWS), 0, s, G, P, nsteps,
+                     S, D, L, picks, anc, hist, zhist, bridge_rows, x_ref, z_ref, bridge_ref, renewed);
   return launch_status();
 }
 

@@ -196,6 +196,31 @@ of log p(constraints | seed) with the key marginalised out, then w_posterior [N,
 particles' label rows after each step: p(key | seed, constraints so far) for a categorical prior) and w_out [N, n_out, C]
 fp32 (the label row each returned path carried).  SmcResult itself keeps four fields: callers iterate over it."""
 
+GibbsResult = namedtuple('GibbsResult', 'Xs log_evidence renewed z')
+GibbsResult.__doc__ = """generate_gibbs's outputs (device tensors, DESIGN.md 19): Xs [N, K, nsteps, D] fp32, the retained path after
+every sweep; log_evidence [N, K] fp64, each sweep's log Z -- only column 0 (the unconditional filter) is an unbiased
+estimate of the evidence, a conditional sweep's log Z is conditioned on the retained path; renewed [N, K, nsteps] bool,
+frame k of sweep s was not taken from the pinned particle (sweep 0: all true); z [N, S + nsteps, L] fp32, the latents the
+decoder was fed along the last path."""
+
+GIBBS_SEED_STEP = 0x9E3779B97F4A7C15        # sweep s runs its whole chain under seed + s * this (mod 2^64)
+
+
+def gibbs_seed(seed, s):
+    """the Philox key of sweep s of a call with key `seed`"""
+    return (int(seed) + int(s) * GIBBS_SEED_STEP) % 2 ** 64
+
+
+def gibbs_args(sweeps, w_prior=None):
+    """Validate generate_gibbs's own arguments: sweeps an integer >= 1, and no key per particle"""
+    if isinstance(sweeps, (bool, np.bool_)) or not isinstance(sweeps, (int, np.integer)) or sweeps < 1:
+        raise ValueError("sweeps must be an integer >= 1, got %r" % (sweeps,))
+    if w_prior is not None:
+        raise ValueError("sweeps do not combine with w_prior: a conditional sweep pins no label row (a key per particle "
+                         "under particle Gibbs is not built)")
+    return int(sweeps)
+
+
 SMC_MAX_PARTICLES = 1024            # one workgroup of clv_smc_resample holds a melody's particles
 SMC_MAX_CLASSES = 32                # SMC_MAX_C of csrc/smc.hip
 
@@ -497,12 +522,23 @@ def state_widths(kind, cfg):
 
 def generate_samples_numpy(engine, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False, temperature=1.0,
-                           z_temperature=1.0, state=None, return_state=False, kind=None):
+                           z_temperature=1.0, state=None, return_state=False, kind=None, sweeps=None, return_renewed=False):
     """generate_samples_device of both families: engine.generate, or with particles engine.generate_smc, on host arrays ->
     [N, nsteps, D] float64 (and what smc_samples_numpy adds; with return_state (Xs, GenState)).  kind: the family
-    ('cl_vrnn' | 'cl_vae'; default: the engine's)."""
+    ('cl_vrnn' | 'cl_vae'; default: the engine's).  sweeps=K (with particles): engine.generate_gibbs, the last sweep's
+    path (gibbs_samples_numpy)."""
     temper = dict(temperature=temperature, z_temperature=z_temperature)
     temper_args(**temper)
+    if sweeps is None and return_renewed:
+        raise ValueError("return_renewed needs sweeps")
+    if sweeps is not None:
+        gibbs_args(sweeps, w_prior)
+        if particles is None:
+            raise ValueError("sweeps needs particles")
+        if return_key:
+            raise ValueError("sweeps do not combine with return_key: no key per particle under particle Gibbs")
+        if state is not None or return_state:
+            raise ValueError("a state does not combine with sweeps")
     d = engine.device
     if state is not None or return_state:
         return _resume_samples_numpy(engine, kind or engine.STATE_KIND, x_seeds, nsteps, w_vals, seed, z_prior, clamp,
@@ -518,6 +554,9 @@ def generate_samples_numpy(engine, x_seeds, nsteps, w_vals=None, seed=0, z_prior
     w = None if w_vals is None else device_f32(w_vals, d)
     if particles is not None:
         smc_args(clamp, particles, resample_threshold, 1, xs.shape[0], nsteps, engine.cfg['D'], d)
+        if sweeps is not None:
+            return gibbs_samples_numpy(engine, xs, w, nsteps, seed, z_prior, clamp, particles, sweeps, resample_threshold,
+                                       return_evidence, return_renewed, **temper)
         return smc_samples_numpy(engine, xs, w, nsteps, seed, z_prior, clamp, particles, resample_threshold, return_evidence,
                                  w_prior=w_prior, return_key=return_key, **temper)
     if return_evidence:
@@ -706,6 +745,21 @@ def smc_samples_numpy(engine, x_seed, w, nsteps, seed, z_prior, clamp, particles
     return out[0] if len(out) == 1 else tuple(out)
 
 
+def gibbs_samples_numpy(engine, x_seed, w, nsteps, seed, z_prior, clamp, particles, sweeps, resample_threshold,
+                        return_evidence, return_renewed=False, temperature=1.0, z_temperature=1.0):
+    """generate_samples_device(particles=P, sweeps=K): the last sweep's path per melody, [N, nsteps, D] float64 (then, with
+    return_evidence, sweep 0's log_evidence [N] float64 -- the only unbiased one -- and, with return_renewed, renewed
+    [N, K, nsteps] bool)"""
+    r = engine.generate_gibbs(x_seed, w, int(nsteps), clamp, particles, sweeps, resample_threshold, seed=int(seed),
+                              z_prior=z_prior, temperature=temperature, z_temperature=z_temperature)
+    out = [r.Xs[:, -1].cpu().numpy().astype(np.float64)]
+    if return_evidence:
+        out.append(r.log_evidence[:, 0].cpu().numpy())
+    if return_renewed:
+        out.append(r.renewed.cpu().numpy())
+    return out[0] if len(out) == 1 else tuple(out)
+
+
 class _Smc:
     """Device state of one chunk of G melodies x P particles: the weight increments, normalized log weights,
     log Z, ESS, resample counts, ancestors A_t [nsteps, R] and the uint8 frame history [nsteps, R, D].  step() is the SMC
@@ -726,13 +780,10 @@ class _Smc:
         self.anc = torch.zeros(nsteps, self.R, **i32)
         self.hist = torch.zeros(nsteps, self.R, D, dtype=torch.uint8, device=device)
 
+    ref = None                      # the path a conditional sweep pins (_GibbsSmc); the plain filter pins nothing
+
     def step(self, xhat, u, counter, x_next, gather):
-        if self.voices is None:
-            ops.smc_sample(self.R, self.D, self.P, self.nsteps, self.S, xhat, u, self.clamp, counter, x_next, self.ell,
-                           self.hist)
-        else:
-            ops.smc_sample_voices(self.R, self.D, self.P, self.nsteps, self.S, xhat, u, self.clamp, self.voices, counter,
-                                  x_next, self.ell, self.hist)
+        self.sample(xhat, u, counter, x_next)
         ops.smc_resample(self.G, self.P, self.nsteps, self.S, self.seed, self.m0, self.tau, self.ell, self.logW, self.logZ,
                          self.ess, self.nres, self.flag, self.anc, counter)
         gather(self.anc, self.flag, counter)
@@ -740,12 +791,68 @@ class _Smc:
             ops.smc_w_posterior(self.G, self.P, self.wr.shape[1], self.nsteps, self.S, self.logW, self.wr, counter,
                                 self.w_post)
 
+    def sample(self, xhat, u, counter, x_next):
+        if self.voices is None:
+            ops.smc_sample(self.R, self.D, self.P, self.nsteps, self.S, xhat, u, self.clamp, counter, x_next, self.ell,
+                           self.hist)
+        else:
+            ops.smc_sample_voices(self.R, self.D, self.P, self.nsteps, self.S, xhat, u, self.clamp, self.voices, counter,
+                                  x_next, self.ell, self.hist)
+
     def finish(self, n_out, Xs, w_out=None):
         picks = None if self.wr is None else torch.zeros(self.G, n_out, dtype=torch.int32, device=Xs.device)
         ops.smc_backtrack(self.G, self.P, self.nsteps, self.D, n_out, self.seed, self.m0, self.S + self.nsteps, self.logW,
                           self.anc, self.hist, Xs, picks)
         if self.wr is not None:     # the gather moved the rows with the state: the final particle holds its path's key
             ops.smc_take_w(self.G, self.P, self.wr.shape[1], n_out, picks, self.wr, w_out)
+
+
+class _Path:
+    """The path particle Gibbs retains for G melodies: frames x [G, nsteps, D] uint8, the latents of every
+    chain step z [G, S + nsteps, L], the bridge sample b [G, D] (None without seed steps)"""
+
+    def __init__(self, G, nsteps, S, D, L, device):
+        self.x = torch.zeros(G, nsteps, D, dtype=torch.uint8, device=device)
+        self.z = torch.zeros(G, S + nsteps, L, dtype=torch.float32, device=device)
+        self.b = torch.zeros(G, D, dtype=torch.float32, device=device) if S > 0 else None
+
+
+class _GibbsSmc(_Smc):
+    """One sweep of particle Gibbs over a chunk: the filter, which also keeps every row's latents of every chain step
+    (zhist [T, R, L]) and its sample of step S - 1 (bridge_rows [R, D]) so that the path it ends on can be retained; with
+    ref (a _Path) a conditional sweep: row m * P is pinned to ref and the resampling is the conditional one."""
+
+    def __init__(self, G, P, nsteps, S, D, L, tau, seed, m0, clamp, device, ref=None):
+        super().__init__(G, P, nsteps, S, D, tau, seed, m0, clamp, device)
+        self.L, self.ref = L, ref
+        self.zhist = torch.zeros(S + nsteps, self.R, L, dtype=torch.float32, device=device)
+        self.bridge_rows = torch.zeros(self.R, D, dtype=torch.float32, device=device) if S > 0 else None
+
+    def pin_z(self, z, counter):
+        ops.smc_pin_z(self.G, self.P, self.L, self.S + self.nsteps, self.ref.z, counter, z)
+
+    def step(self, xhat, u, counter, x_next, gather):
+        if self.ref is None:
+            return super().step(xhat, u, counter, x_next, gather)
+        self.sample(xhat, u, counter, x_next)
+        ops.smc_pin_frame(self.G, self.P, self.D, self.nsteps, self.S, self.ref.x, self.ref.b, counter, x_next, self.hist)
+        ops.smc_resample_conditional(self.G, self.P, self.nsteps, self.S, self.seed, self.m0, self.tau, self.ell, self.logW,
+                                     self.logZ, self.ess, self.nres, self.flag, self.anc, counter)
+        gather(self.anc, self.flag, counter)
+
+    def record(self, t, z, x_next):
+        """after chain step t (eagerly): every row's latents, and at step S - 1 its bridge sample"""
+        self.zhist[t].copy_(z[:self.R])
+        if t == self.S - 1:
+            self.bridge_rows.copy_(x_next)
+
+    def retain(self, path, Xs, renewed):
+        """draw the sweep's path (Xs [G, 1, nsteps, D]) and write it to path; renewed [G, nsteps] uint8"""
+        picks = torch.zeros(self.G, 1, dtype=torch.int32, device=Xs.device)
+        ops.smc_backtrack(self.G, self.P, self.nsteps, self.D, 1, self.seed, self.m0, self.S + self.nsteps, self.logW,
+                          self.anc, self.hist, Xs, picks)
+        ops.smc_backtrack_path(self.G, self.P, self.nsteps, self.S, self.D, self.L, picks, self.anc, self.hist, self.zhist,
+                               self.bridge_rows, path.x, path.z, path.b, renewed)
 
 
 def _smc_chunks(N, P, cap, chunk):
@@ -900,6 +1007,8 @@ class _Chain:
             if self.Tz != 1.0:
                 ops.scale_temper(R * L, self.eps, self.Tz)
             ops.gauss_fwd(R, L, rows.zargs, self.eps, rows.z, L, None)
+            if self.smc is not None and self.smc.ref is not None:      # a conditional sweep: the retained path's latents
+                self.smc.pin_z(rows.z, c)
         else:
             ops.take_frame(R, T, L, self.z_path, c, rows.z)
         rows.decode(self.w_dec, rows.z, self.x_dec if rows.eng.cfg['use_x_prev'] else None,
@@ -944,7 +1053,7 @@ class _Chain:
 
 
 class _Generate:
-    """vary, decode_latents and generate_smc of both families, each written once.  What differs a family states itself
+    """vary, decode_latents, generate_smc and generate_gibbs of both families, each written once.  What differs a family states itself
     (VaeGenerate, VrnnGenerate below) and the bodies here only ask for it:
     STATE_KIND                  its key in STATE_FIELDS, SEED_RANK, LSTM_FIELDS
     ROWS                        the rows of a frame chain: _VaeRows (at most the batch size) / _VrnnRows (any number)
@@ -1069,6 +1178,56 @@ class _Generate:
 
         return _smc_drive(_smc_chunks(N, P, self._smc_cap(), chunk), run_chunk, N, nsteps, D, int(n_out), d,
                           C=None if prior is None else cfg['C'])
+
+
+    def generate_gibbs(self, x_seed, w, nsteps, clamp, particles, sweeps, resample_threshold=0.5, seed=0, use_graph=True,
+                       z_prior=False, chunk=None, temperature=1.0, z_temperature=1.0):
+        """Particle Gibbs under the constraints clamp: K = `sweeps` sweeps of generate_smc's filter with P =
+        `particles` particles, x_seed, w [N, C], clamp (a roll or a Constraints), resample_threshold, chunk and the
+        temperatures as there.  Sweep 0 IS that filter with n_out = 1 under `seed`, bit for bit.  Sweep s >= 1 runs the
+        whole chain under the key gibbs_seed(seed, s) with particle 0 of every melody (row m * P) pinned to the path the
+        sweep before retained -- its latents at every chain step, its frames, and cl_vrnn's bridge sample -- and with
+        conditional multinomial resampling (the pinned particle always survives; every other particle draws its own
+        uniform of the stream trainer.GIBBS_STREAM); the sweep's path is then drawn from its final weights and retained.
+        A conditional sweep leaves p(free notes, z | seed, w, all constraints) invariant for any P >= 2, so the path after
+        K sweeps approaches the posterior as K grows, at a fixed small P; with P = 1 every sweep returns sweep 0's path.
+        There is no ancestor sampling: the early frames of a long piece renew slowly, and `renewed` shows it.
+        Returns GibbsResult: Xs [N, K, nsteps, D], the path after every sweep; log_evidence [N, K] -- ONLY column 0 is an
+        unbiased estimate of the evidence, the log Z of a conditional sweep is conditioned on the retained path --;
+        renewed [N, K, nsteps] bool; z [N, S + nsteps, L], the last path's latents.  The Philox streams follow the global
+        row and melody, so the result does not depend on `chunk`."""
+        cfg, d = self.cfg, self.device
+        temper = temper_args(temperature, z_temperature)
+        K = gibbs_args(sweeps)
+        N, D, L = int(x_seed.shape[0]), cfg['D'], cfg['L']
+        clamp = smc_args(clamp, particles, resample_threshold, 1, N, nsteps, D, d)
+        P, tau, nsteps = int(particles), float(resample_threshold), int(nsteps)
+        x_seed = x_seed.to(dtype=torch.float32, device=d)
+        w = w.to(dtype=torch.float32, device=d)
+        S = seed_steps(self.STATE_KIND, x_seed)
+        f = dict(device=d)
+        out = GibbsResult(torch.zeros(N, K, nsteps, D, dtype=torch.float32, **f), torch.zeros(N, K, dtype=torch.float64, **f),
+                          torch.ones(N, K, nsteps, dtype=torch.bool, **f), torch.zeros(N, S + nsteps, L, dtype=torch.float32, **f))
+        for m0, m1 in _smc_chunks(N, P, self._smc_cap(), chunk):
+            G = m1 - m0
+            wr = w[m0:m1].repeat_interleave(P, 0).contiguous()
+            path = _Path(G, nsteps, S, D, L, d)
+            Xs = torch.zeros(G, 1, nsteps, D, dtype=torch.float32, **f)
+            renewed = torch.zeros(G, nsteps, dtype=torch.uint8, **f)
+            for s in range(K):
+                key = gibbs_seed(seed, s)
+                smc = _GibbsSmc(G, P, nsteps, S, D, L, tau, key, m0, clamp[m0:m1], d, ref=path if s else None)
+                xs = x_seed[m0:m1].repeat_interleave(P, 0)      # anew per sweep: cl_vae's chain writes into its seed rows
+                rows = self.ROWS(self, smc.R)
+                chain = _Chain(rows, wr, wr, nsteps, key, temper, z_prior=z_prior, r0=m0 * P, smc=smc, **self._smc_seed(xs))
+                chain.run(S + nsteps, use_graph, lambda t: smc.record(t, rows.z, chain.x_next))
+                smc.retain(path, Xs, renewed)
+                out.Xs[m0:m1, s].copy_(Xs[:, 0])
+                out.log_evidence[m0:m1, s].copy_(smc.logZ)
+                if s:
+                    out.renewed[m0:m1, s].copy_(renewed != 0)
+            out.z[m0:m1].copy_(path.z)
+        return out
 
 
 class VaeGenerate(_Generate):

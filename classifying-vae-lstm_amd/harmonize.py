@@ -5,7 +5,8 @@ note off, 1 forces it on, FREE (any other value) leaves it to the model.  The ou
 the recurrent state, so inside a frame the free notes are drawn exactly from p(free notes | past, z_t, w); the clamped
 frame is then fed back as the next input.  This is clamped ancestral sampling: it does not condition on constraints that
 lie in the future.  harmonize(particles=P) samples given the whole voice instead, with a particle filter
-(DESIGN.md 11), and can return the model's log p(voice | seed, w).  harmonize(particles=P, infer_key=...) gives every
+(DESIGN.md 11), and can return the model's log p(voice | seed, w); with sweeps=K it runs K sweeps of particle Gibbs on
+that filter.  harmonize(particles=P, infer_key=...) gives every
 particle a key of its own, so that the key follows the voice: it also returns the posterior over the key."""
 import numpy as np
 
@@ -69,7 +70,7 @@ def default_w_prior(model, N, infer_key):
 
 def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fence=True, z_prior=False, particles=None,
               resample_threshold=0.5, return_evidence=False, infer_key=None, w_prior=None, temperature=1.0, z_temperature=1.0,
-              voices=None):
+              voices=None, sweeps=None, return_renewed=False):
     """Generate len(seeds) sequences that keep the `voice` of source_rolls [N, nsteps, 88] and fill in the rest, with the
     frame loop on the device.  seeds: cl_vrnn [N, S, 88] teacher-forced frames (the first source frame follows them),
     cl_vae [N, 88] (frame 0 of the sequence; the first source frame is frame 1).  Returns [N, nsteps, 88] float64.
@@ -86,12 +87,22 @@ def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fenc
     pair (lo, hi), or 'source' (as many as the source frame has).  Each frame is then drawn exactly from p(frame | the kept
     voice, count in range); with particles the evidence becomes log p(voice and texture | seed, w).  The call runs on the
     frame chain or in the filter.  ValueError for a frame that cannot be had: the kept voice needs lo - 1 free notes on its
-    open side (with `fence`), and counts go up to 15."""
+    open side (with `fence`), and counts go up to 15.
+    sweeps=K (with particles): K sweeps of particle Gibbs instead of one pass of the filter; the last sweep's
+    sequences are returned, the evidence is sweep 0's, and return_renewed adds renewed [N, K, nsteps] bool (which frames
+    each sweep took from a particle other than the pinned one).  ValueError for sweeps without particles or with
+    infer_key."""
     from .engine import VaeEngine
     source_rolls = np.asarray(source_rolls)
     if source_rolls.ndim != 3:
         raise ValueError("source_rolls must be [N, nsteps, 88], got shape %s" % (source_rolls.shape,))
     extra = {}
+    if sweeps is not None or return_renewed:
+        if sweeps is not None and particles is None:
+            raise ValueError("sweeps needs particles")
+        if sweeps is not None and (infer_key is not None or w_prior is not None):
+            raise ValueError("sweeps do not combine with infer_key: a conditional sweep pins no key")
+        extra = dict(sweeps=sweeps, return_renewed=return_renewed)
     if infer_key is not None:
         if infer_key not in INFER_KEY:
             raise ValueError("infer_key must be one of %s, got %r" % (INFER_KEY, infer_key))
@@ -99,7 +110,7 @@ def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fenc
             raise ValueError("give either w_vals or infer_key, not both")
         if particles is None:
             raise ValueError("infer_key needs particles: a single path cannot weigh keys")
-        extra = dict(w_prior=w_prior if w_prior is not None else default_w_prior(model, source_rolls.shape[0], infer_key),
+        extra.update(w_prior=w_prior if w_prior is not None else default_w_prior(model, source_rolls.shape[0], infer_key),
                      return_key=True)
     elif w_prior is not None:
         raise ValueError("w_prior needs infer_key")
@@ -124,6 +135,13 @@ def print_evidence(names, log_evidence, nsteps):
     """one line per harmonization: log p(voice | seed, w) per frame (the sample CLIs' --particles)"""
     for name, le in zip(names, np.asarray(log_evidence, dtype=np.float64)):
         print('%s: log p(voice) per frame %.4f (total %.4f over %d frames)' % (name, le / nsteps, le, nsteps))
+
+
+def print_renewed(names, renewed):
+    """one line per harmonization: the share of its frames that each sweep took from a particle other than the pinned one
+    (the sample CLIs' --sweeps; sweep 0, the plain filter, renews everything)"""
+    for name, r in zip(names, np.asarray(renewed, dtype=np.float64)):
+        print('%s: renewed per sweep %s' % (name, ' '.join('%.2f' % v for v in r.mean(axis=-1))))
 
 
 def print_key_posterior(names, w_posterior, key_map):

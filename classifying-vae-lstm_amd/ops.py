@@ -894,6 +894,35 @@ def smc_take_w(G, P, Cn, n_out, picks, wr, w_out):
     check(_lib.lib().clv_smc_take_w(G, P, Cn, n_out, _ptr(picks), _ptr(wr), _ptr(w_out), _stream()), "clv_smc_take_w")
 
 
+def smc_pin_z(G, P, L, T, z_ref, step_dev, z):
+    """a conditional sweep's latent pin: z[m*P] = z_ref[m, *step_dev] of z_ref [G, T, L]; z [G*P, L]"""
+    check(_lib.lib().clv_smc_pin_z(G, P, L, T, _ptr(z_ref), _ptr(step_dev), _ptr(z), _stream()), "clv_smc_pin_z")
+
+
+def smc_pin_frame(G, P, D, nsteps, S, x_ref, bridge, step_dev, x, hist):
+    """a conditional sweep's frame pin: at returned step k = *step_dev - S, x[m*P] and hist[k, m*P] = x_ref[m, k] (x_ref
+    [G, nsteps, D] uint8); at step S - 1 (S > 0) x[m*P] = bridge[m] (bridge [G, D] fp32 or None)"""
+    check(_lib.lib().clv_smc_pin_frame(G, P, D, nsteps, S, _ptr(x_ref), _ptr(bridge), _ptr(step_dev), _ptr(x), _ptr(hist),
+                                       _stream()), "clv_smc_pin_frame")
+
+
+def smc_resample_conditional(G, P, nsteps, S, seed, m0, tau, ell, logW, logZ, ess, nres, flag, anc, step_dev):
+    """smc_resample with conditional multinomial resampling: row m*P keeps itself, every other particle draws its own
+    uniform (stream GIBBS_STREAM, index = its global row)"""
+    check(_lib.lib().clv_smc_resample_conditional(G, P, nsteps, S, int(seed), int(m0), float(tau), _ptr(ell), _ptr(logW),
+                                                  _ptr(logZ), _ptr(ess), _ptr(nres), _ptr(flag), _ptr(anc), _ptr(step_dev),
+                                                  _stream()), "clv_smc_resample_conditional")
+
+
+def smc_backtrack_path(G, P, nsteps, S, D, L, picks, anc, hist, zhist, bridge_rows, x_ref, z_ref, bridge_ref, renewed):
+    """the lineage of particle picks [G] as the next retained path: x_ref [G, nsteps, D] uint8, z_ref [G, S+nsteps, L] from
+    zhist [S+nsteps, G*P, L], bridge_ref [G, D] from bridge_rows [G*P, D] (both None without seed steps), renewed
+    [G, nsteps] uint8 = frame k did not come from the pinned row"""
+    check(_lib.lib().clv_smc_backtrack_path(G, P, nsteps, S, D, L, _ptr(picks), _ptr(anc), _ptr(hist), _ptr(zhist),
+                                            _ptr(bridge_rows), _ptr(x_ref), _ptr(z_ref), _ptr(bridge_ref), _ptr(renewed),
+                                            _stream()), "clv_smc_backtrack_path")
+
+
 def key_track_windows(N, T, D, Hd, Cn, hop, K, frames, piece_off, win_off, Kh, bh, Ka, ba, seed, piece0, wargs, logp):
     """the label head on every window of N pieces of the uint8 roll frames [F, D] (clv_key_track_windows):
     window j of piece n starts at frame j * hop and goes to row win_off[n] + j of wargs [Wtot, 2(Cn-1)] and logp [Wtot, Cn];

@@ -35,6 +35,10 @@ SMC_W_STREAM = 0xFFFFFFFC
 # and, for the label noise of the key tracker (keytrack.py; step = sample k, index = (((GLOBAL piece) << 24) +
 # the window's first frame) * 32 + class; drawn inside csrc/key_track.hip), the one below that:
 KEY_STREAM = 0xFFFFFFFB
+# and, for the uniform every particle but the pinned one draws when a conditional sweep of particle Gibbs resamples
+# (engine_generate.generate_gibbs; step = generation step, index = GLOBAL row; drawn inside csrc/smc.hip), the
+# one below that:
+GIBBS_STREAM = 0xFFFFFFFA
 
 
 class DevWindows:

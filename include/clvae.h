@@ -1029,6 +1029,39 @@ int clv_smc_w_posterior(int G, int P, int C, int nsteps, int S, const double* lo
                         double* out, void* stream);
 int clv_smc_take_w(int G, int P, int C, int n_out, const int32_t* picks, const float* wr, float* w_out, void* stream);
 
+/* ------------------------------------------------- particle Gibbs (conditional SMC sweeps) --
+ * A conditional sweep is the filter above with row m * P of every melody pinned to the path retained from
+ * the sweep before: frames x_ref [G, nsteps, D] uint8, the latents the decoder was fed at every chain step z_ref [G, T, L]
+ * fp32 with T = S + nsteps, and (S > 0) the bridge sample bridge [G, D] fp32 drawn at step S - 1.  Every launch reads the
+ * chain step c = *step_dev, so one captured frame serves a whole sweep.
+ * clv_smc_pin_z: after the latents are formed and before the decoder, z[m*P, :] = z_ref[m, c, :] for 0 <= c < T (seed
+ *   steps included); z [R, L].  A thread per element; no other row is written.
+ * clv_smc_pin_frame: after the draw, with k = c - S: for 0 <= k < nsteps x[m*P, :] = x_ref[m, k, :] (as 0.0 / 1.0) and
+ *   hist[k, m*P, :] = x_ref[m, k, :]; for k = -1 and S > 0, x[m*P, :] = bridge[m, :] (bridge may be NULL: then nothing);
+ *   nothing at any other step.  A wave per melody.  ell is left alone: it depends on x_hat and the constraints only.
+ * clv_smc_resample_conditional: clv_smc_resample with conditional multinomial resampling (Andrieu, Doucet & Holenstein
+ *   2010).  Reweighting, logZ, ess, nres, flag and the rule ess < tau * P are the same code.  When melody m resamples,
+ *   row m*P keeps ancestor m*P, and row m*P + p, p >= 1, draws u = Philox uniform (stream 0xFFFFFFFA, step c, index
+ *   (m0 + m) * P + p: the GLOBAL row) and takes the first q with cum_q > u (cum the inclusive sums of the normalized
+ *   weights), the last one if none.  P = 1 never resamples.  One workgroup per melody, P <= 1024.
+ * clv_smc_backtrack_path: the lineage of particle picks[m] (picks [G] int32, as clv_smc_backtrack with n_out = 1 wrote
+ *   them) walked back, r_k = anc[k, r_{k+1}], and written as the next retained path: x_ref[m, k] = hist[k, r_k],
+ *   z_ref[m, S+k] = zhist[S+k, r_k] (zhist [T, R, L] fp32: every row's latents at every chain step),
+ *   renewed[m, k] = (r_k != m*P) as uint8 [G, nsteps]; z_ref[m, t] = zhist[t, r_0] for t < S and
+ *   bridge_ref[m] = bridge_rows[r_0] (bridge_rows [R, D]: every row's sample of step S - 1; both NULL or both given):
+ *   nothing resamples before k = 0, so the seed steps belong to the lineage's root.  A wave per melody.
+ * No atomics, one owner per output element: bitwise reproducible.  CLV_EINVAL for a G, P, D, L, T or nsteps of 0, S < 0
+ * and a NULL pointer other than the optional ones. */
+int clv_smc_pin_z(int G, int P, int L, int T, const float* z_ref, const int32_t* step_dev, float* z, void* stream);
+int clv_smc_pin_frame(int G, int P, int D, int nsteps, int S, const uint8_t* x_ref, const float* bridge,
+                      const int32_t* step_dev, float* x, uint8_t* hist, void* stream);
+int clv_smc_resample_conditional(int G, int P, int nsteps, int S, uint64_t seed, int64_t m0, double tau, const double* ell,
+                                 double* logW, double* logZ, double* ess, int32_t* nres, int32_t* flag, int32_t* anc,
+                                 const int32_t* step_dev, void* stream);
+int clv_smc_backtrack_path(int G, int P, int nsteps, int S, int D, int L, const int32_t* picks, const int32_t* anc,
+                           const uint8_t* hist, const float* zhist, const float* bridge_rows, uint8_t* x_ref, float* z_ref,
+                           float* bridge_ref, uint8_t* renewed, void* stream);
+
 /* --------------------------------------------------- voice-count constraints --
  * Sampling a frame given how many of its notes sound: the voices twins of clv_bernoulli_sample_clamped and
  * clv_smc_sample.  voices [rows of the roll, nsteps, 2] uint8 holds (lo, hi) per returned frame, addressed as the roll is

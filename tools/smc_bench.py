@@ -5,8 +5,10 @@ G * P rows, which runs the same frame launches without the filter.  Runs alterna
 categorical prior over the keys and / or the model's own logistic-normal prior, each against the fixed-label filter.
 --voices LO[:HI] adds the filter and the clamped chain under that voice count per frame, the top-voice roll
 kept, in the same alternation: clv_smc_sample_voices / clv_bernoulli_sample_voices in place of their twins.
+--sweeps K adds particle Gibbs on the same melodies and particles, in the same alternation: generate_gibbs with
+K sweeps and with one (the filter plus the bookkeeping of a retained path); a conditional sweep costs (t_K - t_1) / (K - 1).
 
-    python tools/smc_bench.py [--melodies 64] [--particles 128] [--nsteps 64] [--reps 5] [--infer_key both] [--voices 4]
+    python tools/smc_bench.py [--melodies 64] [--particles 128] [--nsteps 64] [--reps 5] [--infer_key both] [--voices 4] [--sweeps 4]
 """
 import argparse
 import json
@@ -34,7 +36,10 @@ ap.add_argument('--tau', type=float, default=0.5)
 ap.add_argument('--reps', type=int, default=5)
 ap.add_argument('--infer_key', choices=('categorical', 'logistic_normal', 'both'), default=None)
 ap.add_argument('--voices', default=None, help='LO[:HI]: also run both samplers under this voice count per frame')
+ap.add_argument('--sweeps', type=int, default=None, help='K >= 2: also run particle Gibbs with K sweeps and with one')
 args = ap.parse_args()
+if args.sweeps is not None and args.sweeps < 2:
+    ap.error('--sweeps must be >= 2')
 dev = torch.device('cuda:0')
 G, P, T, S = args.melodies, args.particles, args.nsteps, args.seed_frames
 cfg = dict(D=88, H=88, L=2, T=16, C=10, use_x_prev=True, class_weight=1.0, kl_weight=1.0, w_kl_weight=1.0,
@@ -79,8 +84,11 @@ if args.voices is not None:
     counted_rows = Constraints.between(lo, hi, roll=clamp_rows).resolve(G * P, T, 88, dev)
     voice_modes = ['smc_voices', 'chain_voices']
 
-names = ['smc', 'chain'] + key_modes + voice_modes
+gibbs_modes = [] if args.sweeps is None else ['gibbs', 'gibbs1']
+names = ['smc', 'chain'] + key_modes + voice_modes + gibbs_modes
 run = {'smc': smc, 'chain': chain,
+       'gibbs': lambda: eng.generate_gibbs(seeds, wv, T, clamp, P, args.sweeps, resample_threshold=args.tau, seed=2),
+       'gibbs1': lambda: eng.generate_gibbs(seeds, wv, T, clamp, P, 1, resample_threshold=args.tau, seed=2),
        'smc_voices': lambda: eng.generate_smc(seeds, wv, T, counted, P, resample_threshold=args.tau, seed=2),
        'chain_voices': lambda: eng.generate(seeds_rows, wv_rows, T, seed=2, persistent=False, clamp=counted_rows), 'categorical': lambda: smc('categorical'), 'logistic_normal': lambda: smc('logistic_normal')}
 for name in names:
@@ -123,6 +131,17 @@ if voice_modes:
         'mean_log_evidence_per_frame': float(k.log_evidence.mean()) / T,
         'counts_in_range': bool(((k.Xs.sum(-1) >= lo) & (k.Xs.sum(-1) <= hi)).all()),
     }
-if key_modes or voice_modes:
+if gibbs_modes:
+    k, K = last['gibbs'], args.sweeps
+    per = (med['gibbs'] - med['gibbs1']) / (K - 1)
+    res['gibbs'] = {
+        'sweeps': K, 's': med['gibbs'], 'one_sweep_s': med['gibbs1'], 'conditional_sweep_s': per,
+        'conditional_sweep_us_per_frame': 1e6 * per / frames, 'conditional_sweep_over_smc_pct': 100 * (per / med['smc'] - 1),
+        'one_sweep_over_smc_pct': 100 * (med['gibbs1'] / med['smc'] - 1), 'all_s': t['gibbs'], 'one_sweep_all_s': t['gibbs1'],
+        'sweep0_is_the_filter': bool(torch.equal(k.Xs[:, 0], r.Xs[:, 0]) and torch.equal(k.log_evidence[:, 0], r.log_evidence)),
+        'renewed_per_sweep': [float(v) for v in k.renewed.float().mean(dim=(0, 2))],
+        'mean_log_z_per_frame_per_sweep': [float(v) / T for v in k.log_evidence.mean(dim=0)],
+    }
+if key_modes or voice_modes or gibbs_modes:
     res['smc_all_s'] = t['smc']
 print(json.dumps(res))
