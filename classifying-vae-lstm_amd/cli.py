@@ -10,7 +10,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from .keras_like import Variable
+from .keras_like import OptimizerSpec, Variable
 from .parallel import init_from_env
 from .utils.model_utils import (AnnealLossWeight, best_epoch, get_callbacks, init_adam_wn, save_model_in_pieces,
                                 to_categorical)
@@ -98,6 +98,13 @@ SPLIT_CHOICES = ('test', 'valid', 'train')
 # cl_vae/train.py only, next to the reference's flags
 BF16_FLAGS = [
     Flag(('--bf16',), ON, False, 'Dense products of the fused training step on the bf16 matrix cores (fp32 accumulate)'),
+]
+
+# Keras' optimizer arguments that the reference's scripts leave at their defaults (both train.py, next to the reference's flags)
+OPTIMIZER_FLAGS = [
+    Flag(('--clipnorm',), float, 0.0, 'scale the gradient down to this global L2 norm when it is larger (0: off)'),
+    Flag(('--clipvalue',), float, 0.0, 'then clamp every gradient element to +- this value (0: off)'),
+    Flag(('--lr_decay',), float, 0.0, 'learning rate lr / (1 + lr_decay * iterations) (0: off)'),
 ]
 
 DEVICE_LOOP_FLAGS = [
@@ -387,8 +394,14 @@ class TrainPlan:
 
     def optimizer(self):
         """The optimizer object for get_model; `args.optimizer` keeps the flag's string for the run's JSON."""
-        opt, _ = init_adam_wn(self.args.optimizer)
-        return opt
+        a = self.args
+        clip = dict(decay=getattr(a, 'lr_decay', 0.0), clipnorm=getattr(a, 'clipnorm', 0.0), clipvalue=getattr(a, 'clipvalue', 0.0))
+        opt, _ = init_adam_wn(a.optimizer)
+        if not any(clip.values()):
+            return opt
+        if isinstance(opt, OptimizerSpec):          # 'adam-wn': the reference's hyper-parameters, with OPTIMIZER_FLAGS on top
+            return type(opt)(lr=opt.lr, beta_1=opt.beta_1, beta_2=opt.beta_2, epsilon=opt.epsilon, **clip)
+        return OptimizerSpec.resolve(opt, **clip)   # 'adam', 'rmsprop'
 
     def describe(self, model):
         if self.rank == 0:

@@ -12,6 +12,11 @@
 //   K5 rescale  : W <- s'.V'
 // The column kernels sum a tensor's per-unit partials with 64 columns x 4 unit-lanes per block and
 // several loads in flight (a serial loop over hW's 352 units would be latency-bound).
+//
+// Gradient clipping and learning-rate decay (clv_grad_norm_scale, clv_adam_wn_step_clipped): every kernel
+// that reads a gradient is a template over a trailing parameter pack `Clip`.  With the pack empty (clv_adam_wn_step) a
+// kernel has the arguments and the code it always had; with Clip = AdamClip every gradient read goes through
+// g_eff = clampv(fl32(g * scale)), gdot through fl32(gdot * scale), and the rate that enters lr_t is lr / (1 + decay it).
 #include "common.h"
 
 namespace clv {
@@ -48,16 +53,91 @@ struct AdamHyper {
   const int32_t* iterations;  // device counter (Keras `iterations`), t = *iterations + 1
 };
 
-__device__ __forceinline__ float adam_lr_t(const AdamHyper& h) {
+// the trailing kernel argument of the clipped instances
+struct AdamClip {
+  const float* scale;   // device: the factor of clv_grad_norm_scale (stats + 1); nullptr = 1
+  float clipvalue;      // > 0: clamp to [-clipvalue, clipvalue] after the scale; 0: off
+  float decay;          // > 0: lr / (1 + decay * iterations)
+};
+// what a gradient read goes through: the identity, or Keras' get_gradients (clipnorm's scale first, then clipvalue)
+struct GradAsIs {
+  __device__ __forceinline__ float operator()(float g) const { return g; }
+  __device__ __forceinline__ float dot(float x) const { return x; }
+  __device__ __forceinline__ float2 pair(float2 g) const { return g; }
+  // v' of the float2 body of the two-launch form, row group i (see GradClipped::second_moment)
+  __device__ __forceinline__ float second_moment(float b2, float v0, float gV, int) const { return b2 * v0 + (1.f - b2) * gV * gV; }
+};
+struct GradClipped {
+  float scale, cv;
+  // one rounded product, never contracted into the sum or difference that consumes it.  The result is pinned in its
+  // register: to the arithmetic that follows it is an opaque value, as a loaded gradient is.  What the compiler packs and
+  // fuses there then follows the unclipped instance (checked on the instruction mix of both: with the pins, and the pair
+  // below, the counts of packed and fused operations are equal), so that a scale of 1 gives that instance's bits; the
+  // one sum where that did not suffice is second_moment below
+  __device__ __forceinline__ float dot(float x) const {
+#pragma clang fp contract(off)
+    float r = x * scale;
+    asm("" : "+v"(r));
+    return r;
+  }
+  __device__ __forceinline__ float operator()(float g) const {
+#pragma clang fp contract(off)
+    const float x = g * scale;
+    float r = cv > 0.f ? (x < -cv ? -cv : (x > cv ? cv : x)) : x;      // a NaN stays a NaN
+    asm("" : "+v"(r));
+    return r;
+  }
+  // two neighbours read as one 8-byte load: pinned as the register pair such a load leaves
+  __device__ __forceinline__ float2 pair(float2 g) const {
+#pragma clang fp contract(off)
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const float x = g.x * scale, y = g.y * scale;
+    v2f r;
+    r.x = cv > 0.f ? (x < -cv ? -cv : (x > cv ? cv : x)) : x;
+    r.y = cv > 0.f ? (y < -cv ? -cv : (y > cv ? cv : y)) : y;
+    asm("" : "+v"(r));
+    return make_float2(r.x, r.y);
+  }
+  // b2 v + (1 - b2) gV^2 is a sum of two products, and either may be the one fused into it.  In the unclipped float2 body
+  // the compiler fuses b2 v in the first 16-row group and (1 - b2) gV . gV in the other three (its SLP pass commutes the sum
+  // there); left to itself it fuses b2 v in all four groups of this instance, and v' comes out one rounding apart.  The
+  // identity "a scale of 1 gives clv_adam_wn_step's bits" (tests/test_gpu_optim_clip.py::test_identities) needs the same
+  // choice, so it is written out here; that test fails if a compiler ever chooses otherwise for the unclipped instance.
+  __device__ __forceinline__ float second_moment(float b2, float v0, float gV, int i) const {
+#pragma clang fp contract(off)
+    const float t1 = (1.f - b2) * gV;
+    if (i == 0) { const float t2 = t1 * gV; return __builtin_fmaf(b2, v0, t2); }
+    const float bv = b2 * v0;
+    return __builtin_fmaf(t1, gV, bv);
+  }
+};
+__device__ __forceinline__ GradAsIs grad_of() { return {}; }
+__device__ __forceinline__ GradClipped grad_of(const AdamClip& c) { return {c.scale ? *c.scale : 1.f, c.clipvalue}; }
+
+__device__ __forceinline__ int adam_t(const AdamHyper& h) {
   // CLV_STEP_ADVANCED: the counter was advanced by the step that produced the gradients, it already holds t
-  const int t = h.iterations ? (*h.iterations + (h.step_t == CLV_STEP_ADVANCED ? 0 : 1)) : h.step_t;
-  return h.lr * sqrtf(1.f - powf(h.b2, (float)t)) / (1.f - powf(h.b1, (float)t));
+  return h.iterations ? (*h.iterations + (h.step_t == CLV_STEP_ADVANCED ? 0 : 1)) : h.step_t;
+}
+// the base rate: lr, or Keras' lr / (1 + decay * iterations) with iterations = t - 1, in fp64, rounded to fp32 once
+__device__ __forceinline__ float adam_lr(const AdamHyper& h) { return h.lr; }
+__device__ __forceinline__ float adam_lr(const AdamHyper& h, const AdamClip& c) {
+  float lr = h.lr;
+  if (c.decay > 0.f) lr = (float)((double)h.lr / (1.0 + (double)c.decay * (double)(adam_t(h) - 1)));
+  // the same in every lane: handed on as the scalar that h.lr is, so that what consumes it compiles as it does for h.lr
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lr)));
+}
+template <class... Clip>
+__device__ __forceinline__ float adam_lr_t(const AdamHyper& h, const Clip&... clip) {
+  const int t = adam_t(h);
+  return adam_lr(h, clip...) * sqrtf(1.f - powf(h.b2, (float)t)) / (1.f - powf(h.b1, (float)t));
 }
 
+template <class... Clip>
 __global__ __launch_bounds__(256) void wn_stats_kernel(const AdamUnit* units, const float* params, const float* grads,
-                                                       const float* s, float* partA, float* partB) {
+                                                       const float* s, float* partA, float* partB, Clip... clip) {
   const AdamUnit un = units[blockIdx.x];
   if (!un.is_matrix || un.small) return;
+  const auto ge = grad_of(clip...);
   __shared__ float ra[4][64], rbb[4][64];
   const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
   for (int c0 = 0; c0 < un.cols; c0 += 64) {
@@ -77,7 +157,7 @@ __global__ __launch_bounds__(256) void wn_stats_kernel(const AdamUnit* units, co
         if (ry + 4 * i < un.nrows) {
           const float V = pv[i] * inv_s;
           a += V * V;
-          b += gv[i] * V;
+          b += ge(gv[i]) * V;
         }
       }
     }
@@ -148,9 +228,10 @@ __device__ __forceinline__ float lanes16_sum(float (*red)[CPB], int zy, int cx, 
 }
 
 // colscal[4*j + {0,1,2,3}] = {1/s, grad_g/||V||, s, new_g}
+template <class... Clip>
 __global__ __launch_bounds__(256) void wn_cols_kernel(int n_cols, const AdamCol* cols, const float* partA,
                                                       const float* partB, const float* s, float* mg, float* vg,
-                                                      float* colscal, AdamHyper h) {
+                                                      float* colscal, AdamHyper h, Clip... clip) {
   __shared__ float red[CL][CPB];
   const int cx = threadIdx.x & (CPB - 1), zy = threadIdx.x / CPB;
   const int j = blockIdx.x * CPB + cx;
@@ -161,7 +242,7 @@ __global__ __launch_bounds__(256) void wn_cols_kernel(int n_cols, const AdamCol*
   a = lanes16_sum(red, zy, cx, a);
   b = lanes16_sum(red, zy, cx, b);
   if (zy != 0 || j >= n_cols || skip) return;
-  const float lr_t = adam_lr_t(h);
+  const float lr_t = adam_lr_t(h, clip...);
   const float sc = s[c.col_global];
   const float Vn = sqrtf(a);
   const float gparam = sc * Vn;
@@ -195,19 +276,23 @@ __global__ __launch_bounds__(256) void wn_cols2_kernel(int n_cols, const AdamCol
   if (vn2) vn2[c.col_global] = a;          // ||V'||^2: after the rescale V = W / s' = V', so this is the next step's sum V^2
 }
 
+template <class... Clip>
 __device__ __forceinline__ void wn_update_body(const AdamUnit& un, int unit_idx, float* params, const float* grads,
                                                float* m, float* v, const float* colscal,
-                                               const int32_t* colidx0, float* partC, const AdamHyper& h) {
+                                               const int32_t* colidx0, float* partC, const AdamHyper& h,
+                                               const Clip&... clip) {
   if (un.small && h.weightnorm == CLV_OPT_ADAM_WN) return;   // done by the small-tensor blocks
-  const float lr_t = adam_lr_t(h);
+  const float lr_t = adam_lr_t(h, clip...);
+  const auto ge = grad_of(clip...);
   if (h.weightnorm == CLV_OPT_RMSPROP) {  // Keras RMSprop: a = rho a + (1 - rho) g^2 ; p -= lr g / (sqrt(a) + eps)
     const int n = un.nrows * un.cols;
     const size_t base = un.offset + (size_t)un.row0 * un.cols;
+    const float lr0 = adam_lr(h, clip...);      // (read before the loop's stores: the decayed rate reads the counter)
     for (int i = threadIdx.x; i < n; i += 256) {
-      const float g = grads[base + i];
+      const float g = ge(grads[base + i]);
       const float an = h.b2 * v[base + i] + (1.f - h.b2) * g * g;
       v[base + i] = an;
-      params[base + i] -= h.lr * g / (sqrtf(an) + h.eps);
+      params[base + i] -= lr0 * g / (sqrtf(an) + h.eps);
     }
     return;
   }
@@ -215,7 +300,7 @@ __device__ __forceinline__ void wn_update_body(const AdamUnit& un, int unit_idx,
     const int n = un.nrows * un.cols;
     const size_t base = un.offset + (size_t)un.row0 * un.cols;
     for (int i = threadIdx.x; i < n; i += 256) {
-      const float g = grads[base + i];
+      const float g = ge(grads[base + i]);
       const float mn = h.b1 * m[base + i] + (1.f - h.b1) * g;
       const float vn = h.b2 * v[base + i] + (1.f - h.b2) * g * g;
       m[base + i] = mn; v[base + i] = vn;
@@ -245,7 +330,7 @@ __device__ __forceinline__ void wn_update_body(const AdamUnit& un, int unit_idx,
         if (r < un.nrows) {
           const size_t o = un.offset + (size_t)(un.row0 + r) * un.cols + col;
           const float V = pv[i] * inv_s;
-          const float gV = sc * (gv[i] - gov * V);
+          const float gV = sc * (ge(gv[i]) - gov * V);
           const float mn = h.b1 * mv[i] + (1.f - h.b1) * gV;
           const float vn = h.b2 * vv[i] + (1.f - h.b2) * gV * gV;
           m[o] = mn; v[o] = vn;
@@ -289,14 +374,17 @@ struct SmallItem {
   int64_t col_offset;   // tensor's offset into s/mg/vg
   int32_t rows, cols, col0, is_matrix;
 };
+template <class... Clip>
 __device__ __forceinline__ void wn_small_body(const SmallItem& it, float* params, const float* grads, float* m,
-                                              float* v, float* mg, float* vg, float* s, const AdamHyper& h) {
-  const float lr_t = adam_lr_t(h);
+                                              float* v, float* mg, float* vg, float* s, const AdamHyper& h,
+                                              const Clip&... clip) {
+  const float lr_t = adam_lr_t(h, clip...);
+  const auto ge = grad_of(clip...);
   if (!it.is_matrix) {                                  // bias: plain Adam over its elements
     const int n = it.rows * it.cols;
     for (int i = threadIdx.x; i < n; i += 256) {
       const size_t o = it.offset + i;
-      const float g = grads[o];
+      const float g = ge(grads[o]);
       const float mn = h.b1 * m[o] + (1.f - h.b1) * g;
       const float vn = h.b2 * v[o] + (1.f - h.b2) * g * g;
       m[o] = mn; v[o] = vn;
@@ -324,7 +412,7 @@ __device__ __forceinline__ void wn_small_body(const SmallItem& it, float* params
       const float V = pv[i] * inv_s;
       pv[i] = V;
       a += V * V;
-      b += gv[i] * V;
+      b += ge(gv[i]) * V;
     }
   auto colsum = [&](float x, int slot) {               // sum over the 16 row lanes, result to every lane of the column
     red[ry][cx] = x;
@@ -352,7 +440,7 @@ __device__ __forceinline__ void wn_small_body(const SmallItem& it, float* params
 #pragma unroll
   for (int i = 0; i < SM_RMAX; ++i)
     if (ry + SM_RL * i < it.rows) {
-      const float gV = sc * (gv[i] - gov * pv[i]);
+      const float gV = sc * (ge(gv[i]) - gov * pv[i]);
       const float mn = h.b1 * mv[i] + (1.f - h.b1) * gV;
       const float vn = h.b2 * vv[i] + (1.f - h.b2) * gV * gV;
       mv[i] = mn; vv[i] = vn;
@@ -377,15 +465,16 @@ __device__ __forceinline__ void wn_small_body(const SmallItem& it, float* params
 // K3 and the small tensors in one launch: blocks [0, n_units) update a unit of a tall matrix (or plain Adam), blocks
 // [n_units, n_units + n_small) do the whole Adam-WN of one small tensor.  The small-tensor blocks are a latency chain
 // of their own (~7 us); next to the update blocks they cost nothing.
+template <class... Clip>
 __global__ __launch_bounds__(256) void wn_update_kernel(int n_units, const AdamUnit* units, const SmallItem* items,
                                                         float* params, const float* grads, float* m, float* v,
                                                         float* mg, float* vg, float* s, const float* colscal,
-                                                        const int32_t* colidx0, float* partC, AdamHyper h) {
+                                                        const int32_t* colidx0, float* partC, AdamHyper h, Clip... clip) {
   if ((int)blockIdx.x >= n_units) {
-    wn_small_body(items[blockIdx.x - n_units], params, grads, m, v, mg, vg, s, h);
+    wn_small_body(items[blockIdx.x - n_units], params, grads, m, v, mg, vg, s, h, clip...);
     return;
   }
-  wn_update_body(units[blockIdx.x], (int)blockIdx.x, params, grads, m, v, colscal, colidx0, partC, h);
+  wn_update_body(units[blockIdx.x], (int)blockIdx.x, params, grads, m, v, colscal, colidx0, partC, h, clip...);
 }
 
 __global__ void adam_bump_kernel(int32_t* iterations) { *iterations += 1; }
@@ -420,17 +509,20 @@ struct AdamFast {
   float* partC;           // [nunits][cols]
 };
 
+template <class... Clip>
 __device__ __forceinline__ void wn_fast_update_body(const AdamFast& f, int unit, float* params, const float* grads, float* m,
-                                                    float* v, float* mg, float* vg, const float* s, const AdamHyper& h) {
+                                                    float* v, float* mg, float* vg, const float* s, const AdamHyper& h,
+                                                    const Clip&... clip) {
   __shared__ float cs[3][128];
   __shared__ float2 red[16][64];
   const int tid = threadIdx.x, cx = tid & 63, ry = tid >> 6;
-  const float lr_t = adam_lr_t(h);
+  const float lr_t = adam_lr_t(h, clip...);
+  const auto ge = grad_of(clip...);
   for (int c = tid; c < f.cols; c += FAST_NT) {             // this block's copy of the column scalars
     const size_t cg = f.col_offset + c;
     const float sc = s[cg], a = f.vn2[cg];
     const float Vn = sqrtf(a), inv_s = 1.f / sc;
-    const float grad_g = f.gdot[c] * inv_s / Vn;           // sum g.V / ||V||
+    const float grad_g = ge.dot(f.gdot[c]) * inv_s / Vn;   // sum g.V / ||V||
     cs[0][c] = inv_s; cs[1][c] = grad_g / Vn; cs[2][c] = sc;
     if (unit == 0) {                                        // Adam on the gain (utils/weightnorm.py:109-121), once per column
       const float mgn = h.b1 * mg[cg] + (1.f - h.b1) * grad_g;
@@ -450,14 +542,16 @@ __device__ __forceinline__ void wn_fast_update_body(const AdamFast& f, int unit,
 #pragma unroll
     for (int i = 0; i < FAST_ROWS / 16; ++i) {
       const size_t o = f.offset + (size_t)(row0 + min(ry + 16 * i, nrows - 1)) * f.cols + 2 * cx;
-      pv[i] = *reinterpret_cast<const float2*>(params + o); gv[i] = *reinterpret_cast<const float2*>(grads + o);
+      // (the gradient's transform here, with the loads and outside the row's conditional block below: that block then
+      // holds the same arithmetic on values from outside it in both instances, and compiles to the same fused operations)
+      pv[i] = *reinterpret_cast<const float2*>(params + o); gv[i] = ge.pair(*reinterpret_cast<const float2*>(grads + o));
       mv[i] = *reinterpret_cast<const float2*>(m + o); vv[i] = *reinterpret_cast<const float2*>(v + o);
     }
-    auto one = [&](float p, float g, float m0, float v0, float is, float go, float s0, float& mo, float& vo, float& a2) {
+    auto one = [&](int i, float p, float g, float m0, float v0, float is, float go, float s0, float& mo, float& vo, float& a2) {
       const float V = p * is;
       const float gV = s0 * (g - go * V);
       mo = h.b1 * m0 + (1.f - h.b1) * gV;
-      vo = h.b2 * v0 + (1.f - h.b2) * gV * gV;
+      vo = ge.second_moment(h.b2, v0, gV, i);
       const float Vp = V - lr_t * mo / (sqrtf(vo) + h.eps);
       a2 += Vp * Vp;
       return Vp;
@@ -468,8 +562,8 @@ __device__ __forceinline__ void wn_fast_update_body(const AdamFast& f, int unit,
       if (r < nrows) {
         const size_t o = f.offset + (size_t)(row0 + r) * f.cols + 2 * cx;
         float2 mo, vo, po;
-        po.x = one(pv[i].x, gv[i].x, mv[i].x, vv[i].x, inv_s.x, gov.x, sc.x, mo.x, vo.x, acc.x);
-        po.y = one(pv[i].y, gv[i].y, mv[i].y, vv[i].y, inv_s.y, gov.y, sc.y, mo.y, vo.y, acc.y);
+        po.x = one(i, pv[i].x, gv[i].x, mv[i].x, vv[i].x, inv_s.x, gov.x, sc.x, mo.x, vo.x, acc.x);
+        po.y = one(i, pv[i].y, gv[i].y, mv[i].y, vv[i].y, inv_s.y, gov.y, sc.y, mo.y, vo.y, acc.y);
         *reinterpret_cast<float2*>(m + o) = mo;
         *reinterpret_cast<float2*>(v + o) = vo;
         *reinterpret_cast<float2*>(params + o) = po;
@@ -492,17 +586,20 @@ __device__ __forceinline__ void wn_fast_update_body(const AdamFast& f, int unit,
 // The same pass with the tile taken as what it is in memory -- 64 rows x cols floats, CONTIGUOUS in each of the four arrays --
 // and walked 16 bytes per lane (round 4: 12.6 -> 11.0 us at configuration 3; 3 / 4 float4 per thread on fewer threads: 11.8 / 12.6): thread t owns the float4s t and t + 1024 of the tile (cols % 4 == 0: a float4 never crosses a
 // row, its columns are (4 t) % cols ..+3).  The per-column sums of V'^2 go through an LDS copy of the tile's squares.
+template <class... Clip>
 __device__ __forceinline__ void wn_fast_update_body_flat(const AdamFast& f, int unit, float* params, const float* grads, float* m,
-                                                         float* v, float* mg, float* vg, const float* s, const AdamHyper& h) {
+                                                         float* v, float* mg, float* vg, const float* s, const AdamHyper& h,
+                                                         const Clip&... clip) {
   __shared__ __attribute__((aligned(16))) float cs[3][128];
   __shared__ __attribute__((aligned(16))) float sq[FAST_ROWS * 128];          // V'^2 of the tile, [row][col]; then [8][cols] partial column sums at its front
   const int tid = threadIdx.x;
-  const float lr_t = adam_lr_t(h);
+  const float lr_t = adam_lr_t(h, clip...);
+  const auto ge = grad_of(clip...);
   for (int c = tid; c < f.cols; c += FAST_NT) {
     const size_t cg = f.col_offset + c;
     const float sc = s[cg], a = f.vn2[cg];
     const float Vn = sqrtf(a), inv_s = 1.f / sc;
-    const float grad_g = f.gdot[c] * inv_s / Vn;
+    const float grad_g = ge.dot(f.gdot[c]) * inv_s / Vn;
     cs[0][c] = inv_s; cs[1][c] = grad_g / Vn; cs[2][c] = sc;
     if (unit == 0) {
       const float mgn = h.b1 * mg[cg] + (1.f - h.b1) * grad_g;
@@ -532,7 +629,7 @@ __device__ __forceinline__ void wn_fast_update_body_flat(const AdamFast& f, int 
     const int i = tid + NTA * k;
     if (tid < NTA && i < n4) {
       const int c0 = (4 * i) % f.cols;
-      const float pin[4] = {pv[k].x, pv[k].y, pv[k].z, pv[k].w}, gin[4] = {gv[k].x, gv[k].y, gv[k].z, gv[k].w};
+      const float pin[4] = {pv[k].x, pv[k].y, pv[k].z, pv[k].w}, gin[4] = {ge(gv[k].x), ge(gv[k].y), ge(gv[k].z), ge(gv[k].w)};
       const float min_[4] = {mv[k].x, mv[k].y, mv[k].z, mv[k].w}, vin[4] = {vv[k].x, vv[k].y, vv[k].z, vv[k].w};
       // the four columns' scalars as three 16-byte LDS reads (c0 is a multiple of 4): twelve 4-byte reads at a lane stride of
       // 4 floats put lanes l and l + 16 on one bank (SQ counters, round 4: half of this kernel's LDS cycles were conflicts)
@@ -572,21 +669,22 @@ __device__ __forceinline__ void wn_fast_update_body_flat(const AdamFast& f, int 
   }
 }
 
+template <class... Clip>
 __global__ __launch_bounds__(FAST_NT) void wn_fast_update_kernel(AdamFast f, const SmallItem* items, float* params,
                                                                  const float* grads, float* m, float* v, float* mg, float* vg,
-                                                                 float* s, AdamHyper h) {
+                                                                 float* s, AdamHyper h, Clip... clip) {
   if ((int)blockIdx.x >= f.nunits) {
     if (threadIdx.x >= 256) return;           // the small-tensor blocks are 256-thread work: the other waves leave at once
-    wn_small_body(items[blockIdx.x - f.nunits], params, grads, m, v, mg, vg, s, h);
+    wn_small_body(items[blockIdx.x - f.nunits], params, grads, m, v, mg, vg, s, h, clip...);
     return;
   }
 #if CLV_ADAM_FLAT
   if (f.cols % 4 == 0 && f.offset % 4 == 0 && 8 * f.cols <= FAST_NT) {
-    wn_fast_update_body_flat(f, (int)blockIdx.x, params, grads, m, v, mg, vg, s, h);
+    wn_fast_update_body_flat(f, (int)blockIdx.x, params, grads, m, v, mg, vg, s, h, clip...);
     return;
   }
 #endif
-  wn_fast_update_body(f, (int)blockIdx.x, params, grads, m, v, mg, vg, s, h);
+  wn_fast_update_body(f, (int)blockIdx.x, params, grads, m, v, mg, vg, s, h, clip...);
 }
 
 __global__ __launch_bounds__(FAST_NT) void wn_fast_rescale_kernel(AdamFast f, float* params, float* s, int32_t* iterations) {
@@ -652,6 +750,45 @@ __global__ __launch_bounds__(FAST_NT) void wn_fast_rescale_kernel(AdamFast f, fl
         *reinterpret_cast<float2*>(params + f.offset + (size_t)(row0 + ry + 16 * i) * f.cols + 2 * cx) =
             make_float2(pv[i].x * sn.x, pv[i].y * sn.y);
   }
+}
+
+// ---------------------------------------------------------------------------
+// Global gradient norm (clv_grad_norm_scale): the plan's units are the work items -- a unit is nrows x cols CONTIGUOUS
+// floats of one tensor, so the padding between tensors is never read.  Launch 1: sum g^2 of a unit (a thread's strided
+// share in fp32, then a fixed tree over the 256 threads) -> part[unit].  Launch 2, one block: the partials in fp64, a
+// fixed share per thread and the same tree; norm and Keras' clipnorm factor.  No atomics: the same bits every run.
+// ---------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ T tree256(T* red, T x) {
+  red[threadIdx.x] = x;
+  __syncthreads();
+#pragma unroll
+  for (int k = 128; k > 0; k >>= 1) {
+    if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+    __syncthreads();
+  }
+  return red[0];
+}
+__global__ __launch_bounds__(256) void grad_sq_kernel(const AdamUnit* units, const float* grads, float* part) {
+  __shared__ float red[256];
+  const AdamUnit un = units[blockIdx.x];
+  const int n = un.nrows * un.cols;
+  const float* g = grads + un.offset + (size_t)un.row0 * un.cols;
+  float a = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) { const float x = g[i]; a += x * x; }
+  a = tree256(red, a);
+  if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+__global__ __launch_bounds__(256) void grad_norm_kernel(int n_units, const float* part, float clipnorm, float* stats) {
+  __shared__ double red[256];
+  double a = 0.0;
+  for (int k = threadIdx.x; k < n_units; k += 256) a += (double)part[k];
+  a = tree256(red, a);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(a);
+  stats[0] = norm;
+  // K.switch(n >= c, g * c / n, g); a NaN norm compares false; clipnorm = +inf reports the norm and clips nothing
+  stats[1] = (norm >= clipnorm && clipnorm <= 3.402823466e+38f) ? clipnorm / norm : 1.f;
 }
 
 struct PlanCounts { int n_units, n_cols, n_part, n_small, n_big; };
@@ -733,11 +870,14 @@ extern "C" size_t clv_adam_wn_workspace_bytes(const clv_param_desc* host_table, 
   return (size_t)(3 * c.n_part + 4 * c.n_cols + 16) * sizeof(float);
 }
 
-extern "C" int clv_adam_wn_step(const clv_param_desc* host_table, int n_tensors, const void* plan_dev,
-                                   float* params, const float* grads, float* m, float* v,
-                                   float* mg, float* vg, float* s,
-                                   int32_t* iterations_dev, int step_t, float lr, float beta1, float beta2, float eps,
-                                   int weightnorm, const clv_adam_known_sums* known, void* ws, size_t ws_bytes, void* stream) {
+// clv_adam_wn_step (Clip empty) and clv_adam_wn_step_clipped (Clip = AdamClip): one launcher, two sets of instances
+template <class... Clip>
+static int adam_wn_launch(const clv_param_desc* host_table, int n_tensors, const void* plan_dev,
+                          float* params, const float* grads, float* m, float* v,
+                          float* mg, float* vg, float* s,
+                          int32_t* iterations_dev, int step_t, float lr, float beta1, float beta2, float eps,
+                          int weightnorm, const clv_adam_known_sums* known, void* ws, size_t ws_bytes, void* stream,
+                          Clip... clip) {
   if (!host_table || n_tensors <= 0 || !plan_dev || !params || !grads || !m || !v) return CLV_EINVAL;
   float* vn2 = known ? known->vnorm2 : nullptr;
   if (weightnorm < 0 || weightnorm > CLV_OPT_RMSPROP) return CLV_EINVAL;
@@ -778,23 +918,24 @@ extern "C" int clv_adam_wn_step(const clv_param_desc* host_table, int n_tensors,
   if (fast) {
     const clv_param_desc& t = host_table[known->tensor];
     AdamFast f{t.offset, t.col_offset, t.rows, t.cols, nunits, known->gdot, vn2, colscal, partC};
-    hipLaunchKernelGGL(wn_fast_update_kernel, dim3(nunits + c.n_small), dim3(FAST_NT), 0, st, f, small, params, grads, m, v, mg,
-                       vg, s, h);
+    hipLaunchKernelGGL((wn_fast_update_kernel<Clip...>), dim3(nunits + c.n_small), dim3(FAST_NT), 0, st, f, small, params, grads,
+                       m, v, mg, vg, s, h, clip...);
     hipLaunchKernelGGL(wn_fast_rescale_kernel, dim3(nunits), dim3(FAST_NT), 0, st, f, params, s, bump);
     return launch_status();
   }
   const bool chain = !wn || c.n_big > 0;      // tall matrices (partial slabs), or plain Adam for everything
   const int n_small = wn ? c.n_small : 0;     // small matrices and biases: whole update in their own blocks of K3
   if (wn && chain) {
-    hipLaunchKernelGGL(wn_stats_kernel, dim3(c.n_units), dim3(256), 0, st, units, params, grads, s, partA, partB);
-    hipLaunchKernelGGL(wn_cols_kernel, dim3((c.n_cols + CPB - 1) / CPB), dim3(256), 0, st, c.n_cols, cols, partA, partB, s,
-                       mg, vg, colscal, h);
+    hipLaunchKernelGGL((wn_stats_kernel<Clip...>), dim3(c.n_units), dim3(256), 0, st, units, params, grads, s, partA, partB,
+                       clip...);
+    hipLaunchKernelGGL((wn_cols_kernel<Clip...>), dim3((c.n_cols + CPB - 1) / CPB), dim3(256), 0, st, c.n_cols, cols, partA,
+                       partB, s, mg, vg, colscal, h, clip...);
   }
   {
     const int n_units = chain ? c.n_units : 0;
     if (n_units + n_small > 0)
-      hipLaunchKernelGGL(wn_update_kernel, dim3(n_units + n_small), dim3(256), 0, st, n_units, units, small, params, grads, m,
-                         v, mg, vg, s, colscal, colidx0, partC, h);
+      hipLaunchKernelGGL((wn_update_kernel<Clip...>), dim3(n_units + n_small), dim3(256), 0, st, n_units, units, small, params,
+                         grads, m, v, mg, vg, s, colscal, colidx0, partC, h, clip...);
   }
   if (wn && chain) {
     hipLaunchKernelGGL(wn_cols2_kernel, dim3((c.n_cols + CPB - 1) / CPB), dim3(256), 0, st, c.n_cols, cols, partC, s, colscal,
@@ -805,3 +946,47 @@ extern "C" int clv_adam_wn_step(const clv_param_desc* host_table, int n_tensors,
   }
   return launch_status();
 }
+
+extern "C" int clv_adam_wn_step(const clv_param_desc* host_table, int n_tensors, const void* plan_dev,
+                                   float* params, const float* grads, float* m, float* v,
+                                   float* mg, float* vg, float* s,
+                                   int32_t* iterations_dev, int step_t, float lr, float beta1, float beta2, float eps,
+                                   int weightnorm, const clv_adam_known_sums* known, void* ws, size_t ws_bytes, void* stream) {
+  return adam_wn_launch(host_table, n_tensors, plan_dev, params, grads, m, v, mg, vg, s, iterations_dev, step_t, lr, beta1,
+                        beta2, eps, weightnorm, known, ws, ws_bytes, stream);
+}
+
+extern "C" int clv_adam_wn_step_clipped(const clv_param_desc* host_table, int n_tensors, const void* plan_dev,
+                                        float* params, const float* grads, float* m, float* v,
+                                        float* mg, float* vg, float* s,
+                                        int32_t* iterations_dev, int step_t, float lr, float beta1, float beta2, float eps,
+                                        int weightnorm, const clv_adam_known_sums* known, void* ws, size_t ws_bytes, void* stream,
+                                        const float* grad_scale, float clipvalue, float decay) {
+  if (!(clipvalue >= 0.f) || !(decay >= 0.f) || decay > 3.402823466e+38f) return CLV_EINVAL;      // (a NaN fails both)
+  // a clamped gradient's sum g.V is not the one the backward pass formed
+  if (clipvalue > 0.f && known && known->use) return CLV_EINVAL;
+  if (!grad_scale && clipvalue == 0.f && decay == 0.f)      // nothing asked for: the unclipped instances themselves
+    return adam_wn_launch(host_table, n_tensors, plan_dev, params, grads, m, v, mg, vg, s, iterations_dev, step_t, lr, beta1,
+                          beta2, eps, weightnorm, known, ws, ws_bytes, stream);
+  return adam_wn_launch(host_table, n_tensors, plan_dev, params, grads, m, v, mg, vg, s, iterations_dev, step_t, lr, beta1,
+                        beta2, eps, weightnorm, known, ws, ws_bytes, stream, AdamClip{grad_scale, clipvalue, decay});
+}
+
+extern "C" size_t clv_grad_norm_workspace_bytes(const clv_param_desc* host_table, int n_tensors) {
+  if (!host_table || n_tensors <= 0) return 0;
+  return align_up(sizeof(float) * plan_counts(host_table, n_tensors).n_units, 16);
+}
+
+extern "C" int clv_grad_norm_scale(const clv_param_desc* host_table, int n_tensors, const void* plan_dev, const float* grads,
+                                   float clipnorm, float* stats, void* ws, size_t ws_bytes, void* stream) {
+  if (!host_table || n_tensors <= 0 || !plan_dev || !grads || !stats || !(clipnorm > 0.f)) return CLV_EINVAL;
+  if (!ws || ws_bytes < clv_grad_norm_workspace_bytes(host_table, n_tensors)) return CLV_EINVAL;
+  const int n_units = plan_counts(host_table, n_tensors).n_units;
+  if (n_units <= 0) return CLV_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope pr("grad_norm_scale", st);
+  hipLaunchKernelGGL(grad_sq_kernel, dim3(n_units), dim3(256), 0, st, (const AdamUnit*)plan_dev, grads, (float*)ws);
+  hipLaunchKernelGGL(grad_norm_kernel, dim3(1), dim3(256), 0, st, n_units, (const float*)ws, clipnorm, stats);
+  return launch_status();
+}
+

@@ -106,19 +106,30 @@ class Layer:
 class OptimizerSpec:
     """What utils/weightnorm.AdamWithWeightnorm / the strings 'adam' resolve to on the HIP path."""
 
-    def __init__(self, name='adam-wn', lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-8, decay=0.0):
-        if decay != 0.0:
-            raise ValueError("learning-rate decay is not used by the reference and not supported")
+    def __init__(self, name='adam-wn', lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-8, decay=0.0, clipnorm=0.0,
+                 clipvalue=0.0):
+        """decay, clipnorm, clipvalue as Keras' optimizer constructors take them (lr / (1 + decay * iterations); the global
+        gradient norm scaled down to clipnorm; then every element clamped to +-clipvalue); 0 = off.  They are applied on the
+        device, inside the optimizer's launches."""
+        for key, val in (('decay', decay), ('clipnorm', clipnorm), ('clipvalue', clipvalue)):
+            if not float(val) >= 0.0:                  # negative or NaN
+                raise ValueError("%s must be >= 0 (0 = off), got %r" % (key, val))
+        if float(decay) == float('inf'):
+            raise ValueError("decay must be finite")
         self.name, self.lr, self.beta_1, self.beta_2, self.epsilon = name, lr, beta_1, beta_2, epsilon
+        self.decay, self.clipnorm, self.clipvalue = float(decay), float(clipnorm), float(clipvalue)
 
     @staticmethod
-    def resolve(opt):
+    def resolve(opt, **clip):
+        """clip: decay / clipnorm / clipvalue for an optimizer given by its name"""
         if isinstance(opt, OptimizerSpec):
+            if clip:
+                raise ValueError("pass decay, clipnorm and clipvalue to the optimizer object itself")
             return opt
         if opt in ('adam', 'adam-wn'):
-            return OptimizerSpec(opt)
+            return OptimizerSpec(opt, **clip)
         if opt == 'rmsprop':          # Keras 2.0.0 defaults: lr 0.001, rho 0.9 (carried as beta_2), epsilon 1e-8
-            return OptimizerSpec('rmsprop', lr=1e-3, beta_2=0.9, epsilon=1e-8)
+            return OptimizerSpec('rmsprop', lr=1e-3, beta_2=0.9, epsilon=1e-8, **clip)
         raise ValueError("optimizer %r is not supported on the HIP path (use 'adam-wn', 'adam' or 'rmsprop')" % (opt,))
 
 
@@ -219,8 +230,9 @@ class Model:
         w = self._sync_loss_weights()
         if self._step is None:
             rank, world = _dp()
-            self._step = TrainStep(self.engine, seed=self.seed, rank=rank, world=world, optimizer=self.optimizer.name,
-                                   lr=self.optimizer.lr)
+            o = self.optimizer
+            self._step = TrainStep(self.engine, seed=self.seed, rank=rank, world=world, optimizer=o.name, lr=o.lr,
+                                   clipnorm=o.clipnorm, clipvalue=o.clipvalue, decay=o.decay)
             self._step_weights = w
         elif self._step_weights != w:       # same step object (streams, staging buffers): only the graphs are stale
             self._step.recapture()

@@ -84,6 +84,10 @@ class FlatParams:
         self.plan = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(device)
         self.adam_ws = torch.empty(L.clv_adam_wn_workspace_bytes(table, len(self.shapes)), dtype=torch.uint8,
                                    device=device)
+        # gradient clipping (adam_step(clipnorm=...)): the pre-clip global norm and the scale of the last clipped step
+        self.grad_stats = torch.tensor([0.0, 1.0], **f)
+        self.norm_ws = torch.empty(max(L.clv_grad_norm_workspace_bytes(table, len(self.shapes)), 16), dtype=torch.uint8,
+                                   device=device)
 
     # views ---------------------------------------------------------------
     def view(self, buf, name):
@@ -147,26 +151,39 @@ class FlatParams:
         return tall[0] if len(tall) == 1 else None
 
     def adam_step(self, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, weightnorm=True, only=None, advance=True, advanced=False,
-                  gdot=None):
+                  gdot=None, clipnorm=0.0, clipvalue=0.0, decay=0.0):
         """utils/weightnorm.py:75-143; t comes from the device `iterations` counter.
         only: names of the tensors to update (default all); advance=False leaves `iterations` alone, so one optimizer step
         can be issued in pieces (the multi-GPU schedule updates a bucket as soon as its all-reduce has landed).
         advanced=True: the counter was already advanced by the launch that produced the gradients (the fused cl_vae
         step) and holds t.
         gdot [cols]: sum_j K[j,c] dK[j,c] of the tall matrix (ops.sparse_outer(gdot=...)), for gradients that were not
-        averaged across ranks afterwards: with norms_valid the step takes the two-launch form (clv_adam_wn_step)."""
+        averaged across ranks afterwards: with norms_valid the step takes the two-launch form (clv_adam_wn_step).
+        clipnorm / clipvalue / decay (0 = off; Keras' Optimizer.get_gradients and lr / (1 + decay * iterations), DESIGN.md
+        20): with any of them the step is clv_adam_wn_step_clipped.  clipnorm > 0: two launches first leave the norm of
+        the gradient over the WHOLE table (whatever `only` names: the pieces of a split step share one scale) and the scale
+        in `grad_stats`.  clipvalue > 0 takes the five-launch form: gdot was formed from the unclamped gradient."""
         table, n, plan = (self.table, len(self.shapes), self.plan) if only is None else self._subplan(only)
         known, tall = None, self.tall_tensor()
         if int(weightnorm) == 1 and tall is not None and (only is None or tall[1] in only):
-            use = gdot is not None and self.norms_valid
+            use = gdot is not None and self.norms_valid and not clipvalue > 0
             pos = tall[0] if only is None else [name for name, _ in self.shapes if name in only].index(tall[1])
             known = _lib.AdamKnownSums(pos, int(use), ops._ptr(gdot) if use else None, ops._ptr(self.vn2))
-        _lib.check(_lib.lib().clv_adam_wn_step(
-            table, n, ops._ptr(plan), ops._ptr(self.params), ops._ptr(self.grads),
-            ops._ptr(self.m), ops._ptr(self.v), ops._ptr(self.mg), ops._ptr(self.vg), ops._ptr(self.s),
-            ops._ptr(self.iterations), -2 if advanced else (0 if advance else -1), lr, b1, b2, eps, int(weightnorm),
-            C.byref(known) if known is not None else None, ops._ptr(self.adam_ws),
-            self.adam_ws.numel(), ops._stream()), "clv_adam_wn_step")
+        L = _lib.lib()
+        args = (table, n, ops._ptr(plan), ops._ptr(self.params), ops._ptr(self.grads),
+                ops._ptr(self.m), ops._ptr(self.v), ops._ptr(self.mg), ops._ptr(self.vg), ops._ptr(self.s),
+                ops._ptr(self.iterations), -2 if advanced else (0 if advance else -1), lr, b1, b2, eps, int(weightnorm),
+                C.byref(known) if known is not None else None, ops._ptr(self.adam_ws),
+                self.adam_ws.numel(), ops._stream())
+        if not (clipnorm > 0 or clipvalue > 0 or decay > 0):
+            _lib.check(L.clv_adam_wn_step(*args), "clv_adam_wn_step")
+        else:
+            if clipnorm > 0:
+                _lib.check(L.clv_grad_norm_scale(self.table, len(self.shapes), ops._ptr(self.plan), ops._ptr(self.grads),
+                                                 clipnorm, ops._ptr(self.grad_stats), ops._ptr(self.norm_ws),
+                                                 self.norm_ws.numel(), ops._stream()), "clv_grad_norm_scale")
+            _lib.check(L.clv_adam_wn_step_clipped(*args, ops._ptr(self.grad_stats[1:]) if clipnorm > 0 else None,
+                                                  clipvalue, decay), "clv_adam_wn_step_clipped")
         # vn2 follows the parameters through whole Adam-WN steps only
         self.norms_valid = known is not None or (self.norms_valid and tall is not None and only is not None
                                                  and tall[1] not in only)

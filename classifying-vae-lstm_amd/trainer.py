@@ -52,7 +52,9 @@ class DevWindows:
 
 class TrainStep:
     def __init__(self, engine, seed=1234, rank=0, world=1, group=None, optimizer='adam-wn',
-                 lr=1e-3, use_graph=True, fast_adam=True):
+                 lr=1e-3, use_graph=True, fast_adam=True, clipnorm=0.0, clipvalue=0.0, decay=0.0):
+        """clipnorm, clipvalue, decay: Keras' optimizer arguments (0 = off), applied on the device inside the optimizer's launches
+        and captured with them (FlatParams.adam_step); `grad_stats` holds the last step's pre-clip norm and scale."""
         self.eng = engine
         self.seed, self.rank, self.world = int(seed), int(rank), int(world)
         if optimizer not in ('adam-wn', 'adam', 'rmsprop'):
@@ -60,6 +62,10 @@ class TrainStep:
         self.weightnorm = {'adam': 0, 'adam-wn': 1, 'rmsprop': 2}[optimizer]      # CLV_OPT_* of include/clvae.h
         self.b2 = 0.9 if optimizer == 'rmsprop' else 0.999                       # rmsprop: rho
         self.lr = lr
+        for key, val in (('clipnorm', clipnorm), ('clipvalue', clipvalue), ('decay', decay)):
+            if not float(val) >= 0.0:
+                raise ValueError("%s must be >= 0 (0 = off), got %r" % (key, val))
+        self.clip = dict(clipnorm=float(clipnorm), clipvalue=float(clipvalue), decay=float(decay))
         self.use_graph = use_graph
         cfg, B, d = engine.cfg, engine.B, engine.device
         self.is_vrnn = 'T' in cfg
@@ -110,7 +116,9 @@ class TrainStep:
         self.tail_names = [n for n, _ in engine.P.shapes if tail[1] and engine.P.offsets[n] == tail[0]
                            and int(np.prod(dict(engine.P.shapes)[n])) == tail[1]]
         self.rest_names = [n for n, _ in engine.P.shapes if n not in self.tail_names]
-        self.split_update = self.ar is not None and len(self.tail_names) == 1
+        # clipnorm: the norm is that of the AVERAGED gradient over the whole table, so it can only be taken once both buckets have
+        # landed -- the one-piece _update() after ar.wait().  clipvalue and decay are element-wise and keep the split update
+        self.split_update = self.ar is not None and len(self.tail_names) == 1 and not self.clip['clipnorm'] > 0
         # The big bucket's all-reduce runs next to the LSTM weight-gradient products (VrnnEngine.fine_grid: twice the
         # workgroups, half the K each, so that a few CUs held by RCCL do not cost a whole second round).  Alone on a GPU
         # the fine grid is 8-15 % slower (profiles/r03_dp_schedule_one_gpu.txt) and nobody has measured it next to a real
@@ -268,7 +276,14 @@ class TrainStep:
     def _update(self):
         # single GPU, cl_vrnn: the backward pass left sum_j K dK of the hW kernel (VrnnEngine.gdot), so Adam-WN runs in two
         # launches instead of five (FlatParams.adam_step); not under data parallelism (the gradient is averaged afterwards)
-        self.eng.P.adam_step(lr=self.lr, b2=self.b2, weightnorm=self.weightnorm, advanced=self._folded(), gdot=self._gdot())
+        self.eng.P.adam_step(lr=self.lr, b2=self.b2, weightnorm=self.weightnorm, advanced=self._folded(), gdot=self._gdot(),
+                             **self.clip)
+
+    @property
+    def grad_stats(self):
+        """device [2]: the gradient's norm before clipping and the scale applied, of the last step with clipnorm > 0 (written by
+        the step's own launches: reading it costs the reader a sync, the step none)"""
+        return self.eng.P.grad_stats
 
     def _gdot(self):
         """The hW kernel's sum g.V when this step's backward pass left it AND it went through whatever averaged the
@@ -282,11 +297,11 @@ class TrainStep:
     # _tail()), the rest once the main bucket is in; `iterations` advances with the second piece
     def _update_tail(self):
         self.eng.P.adam_step(lr=self.lr, b2=self.b2, weightnorm=self.weightnorm, only=self.tail_names, advance=False,
-                             advanced=self._folded(), gdot=self._gdot())
+                             advanced=self._folded(), gdot=self._gdot(), **self.clip)
 
     def _update_rest(self):
         self.eng.P.adam_step(lr=self.lr, b2=self.b2, weightnorm=self.weightnorm, only=self.rest_names,
-                             advanced=self._folded())
+                             advanced=self._folded(), **self.clip)
 
     # -- public -----------------------------------------------------------
     def _segments(self, cur, hist, w, target=None, bytes_out=None):

@@ -11,8 +11,10 @@ from ..keras_like import OptimizerSpec
 
 
 class AdamWithWeightnorm(OptimizerSpec):
-    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-08, decay=0.0):
-        super().__init__('adam-wn', lr, beta_1, beta_2, epsilon, decay)
+    def __init__(self, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-08, decay=0.0, clipnorm=0.0, clipvalue=0.0):
+        """decay, and the clipnorm / clipvalue that Keras' Optimizer takes as keyword arguments (:77-85: get_gradients
+        and the decayed rate); 0 = off"""
+        super().__init__('adam-wn', lr, beta_1, beta_2, epsilon, decay, clipnorm, clipvalue)
 
 
 def data_based_init(model, input):

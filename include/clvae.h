@@ -931,6 +931,36 @@ int clv_adam_wn_step(const clv_param_desc* host_table, int n_tensors, const void
                         int32_t* iterations_dev, int step_t, float lr, float beta1, float beta2, float eps,
                         int weightnorm, const clv_adam_known_sums* known, void* ws, size_t ws_bytes, void* stream);
 
+/* Gradient clipping and learning-rate decay as Keras' optimizers apply them (Optimizer.get_gradients: clipnorm, then
+ * clipvalue; lr *= 1 / (1 + decay * iterations); utils/weightnorm.py:77-85 of the reference), on the device and inside
+ * the optimizer's own launches, so that a captured step needs no host round trip.
+ *
+ * clv_grad_norm_scale: stats[0] = norm = sqrt(sum g^2) over the elements of the tensors of host_table (the padding
+ * between tensors is not read), stats[1] = norm >= clipnorm ? clipnorm / norm : 1 (Keras' K.switch; a NaN norm leaves 1).
+ * Two launches over the plan's units (plan_dev: the plan of the same table), per-unit partials in fp32, their sum in
+ * fp64, a fixed order and no atomics: the same bits on every run.  clipnorm = +inf reports the norm and clips nothing.
+ * ws: clv_grad_norm_workspace_bytes of the table.  CLV_EINVAL, and nothing launched: clipnorm <= 0 or NaN, a NULL
+ * table, plan, grads or stats, a missing or short workspace.  grads are only read.
+ *
+ * clv_adam_wn_step_clipped: clv_adam_wn_step on g_eff = clampv(fl32(g * scale)) in the place of g, in every kernel of
+ * every route; scale = grad_scale ? *grad_scale : 1 (device float, e.g. stats + 1), clampv the clamp to
+ * [-clipvalue, clipvalue] when clipvalue > 0 and the identity at 0.  The gradient buffer is not written.  The known-sums
+ * form reads fl32(gdot[c] * scale) for gdot[c]; clipvalue > 0 with known->use != 0 is refused (a clamped gradient's
+ * sum g.V is not the one the backward pass formed).  decay > 0: the rate that enters lr_t (and RMSprop's lr) is the fp32
+ * nearest to lr / (1 + decay * it) evaluated in fp64, it = t - 1 = Keras' `iterations` before the step under every
+ * step_t rule.  CLV_EINVAL: clipvalue < 0 or NaN, decay < 0, NaN or inf; else as clv_adam_wn_step.
+ * (..., NULL, 0, 0) launches clv_adam_wn_step's own kernels; a grad_scale that holds 1 gives clv_adam_wn_step's outputs bit
+ * for bit on every route. */
+size_t clv_grad_norm_workspace_bytes(const clv_param_desc* host_table, int n_tensors);
+int clv_grad_norm_scale(const clv_param_desc* host_table, int n_tensors, const void* plan_dev, const float* grads,
+                        float clipnorm, float* stats, void* ws, size_t ws_bytes, void* stream);
+int clv_adam_wn_step_clipped(const clv_param_desc* host_table, int n_tensors, const void* plan_dev,
+                        float* params, const float* grads, float* m, float* v,
+                        float* mg, float* vg, float* s,
+                        int32_t* iterations_dev, int step_t, float lr, float beta1, float beta2, float eps,
+                        int weightnorm, const clv_adam_known_sums* known, void* ws, size_t ws_bytes, void* stream,
+                        const float* grad_scale, float clipvalue, float decay);
+
 /* -------------------------------------------------------------------- RNG --
  * Counter-based Philox4x32-10, key = (seed_lo, seed_hi), counter =
  * ((index>>2)_lo, (index>>2)_hi, stream_id, step): element i of a draw is a pure
