@@ -1,5 +1,5 @@
 // wgrad_bf16.hip -- every kernel gradient of one LSTM in one pass over dz, on the bf16 matrix cores from bf16 piece
-// products: 6 of the 9 piece pairs of an fp32 x fp32 product (what is dropped is below 2^-25 of it, about the one rounding
+// products: 6 of the 9 piece pairs of an fp32 x fp32 product (what is dropped is below 2^-23 of it, typically 2^-27: the one rounding
 // an fp32 multiply makes -- fp32-rounding accuracy, NOT exact), all pairs for byte-valued frames (gfx950).
 //
 //   dK_x [nx,4H] = X^T . dz      (input frames; binary piano-roll, or any values)
@@ -12,7 +12,7 @@
 // sum of three bf16 numbers (8 + 8 + 8 mantissa bits, same exponent range), and a product of two bf16 numbers is exact
 // in fp32, so  a.b = sum_{i,j} a_i.b_j  over the 3 x 3 piece pairs has EXACT partial products that accumulate in fp32 like
 // any other summation order of the same products.  The three pairs with i + j >= 3 (a1.b2, a2.b1, a2.b2) together are below
-// 2^-25 |a.b| -- less than the ONE rounding an fp32 multiply of a and b makes -- and are left out (round 4): 6 bf16 MFMAs
+// 2^-23 |a.b| (random mantissas: ~2^-27) -- about the ONE rounding an fp32 multiply of a and b makes -- and are left out (round 4): 6 bf16 MFMAs
 // (96 cycles per 16x16 tile and 32 k) replace 8 f32 MFMAs (256 cycles).  -DWB_PRODUCTS=9 keeps all nine (measured, us per
 // launch: 36.0 -> 33.8 at K = 32768, 218 -> 196 at K = 262144 with six; profiles/r04_out_head_log.txt).  Frames that are
 // exactly representable in bf16 (0/1 piano-roll, any uint8) need one piece: their 3 MFMAs are all kept, those products
@@ -496,6 +496,11 @@ static bool wgrad_problem_ok(const clv_wgrad_problem& p) {
       (p.nz > 0 && (!p.Z || !p.dKz)))
     return false;
   if (!clv_lstm_wgrad_rows_supported(p.K, p.ldx, p.x_exact_bf16, p.ldh, p.ldz, p.nz, p.lddz)) return false;
+  // rows shorter than what is read or written of them would be mis-read (or overlap); a negative shift would read H beyond
+  // row K - 1, and the window test takes k % period of a period >= 0 (tests/test_gpu_wgrad.py: refusals)
+  if (p.ldx < p.nx || p.ldh < p.nh || p.lddz < p.N || (p.nz > 0 && (p.ldz < p.nz || p.ld_kz < p.N)) || p.ld_kx < p.N || p.ld_u < p.N ||
+      p.h_shift < 0 || p.h_zero_period < 0)
+    return false;
   // (the frames as bytes have ldx in bytes and 4-byte aligned rows)
   return !(p.ldx % 4 || p.ldh % 4 || p.lddz % 4 || ((uintptr_t)p.H | (uintptr_t)p.dz) % 16 ||
            ((uintptr_t)p.X) % (p.x_exact_bf16 == CLV_FRAMES_U8 ? 4 : 16));

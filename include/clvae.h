@@ -225,8 +225,8 @@ int clv_splitk_reduce_multi_outer(const clv_reduce_job* jobs, int njobs, const f
  *   dKz [nz,N] = Z^T . dz            Z [K,ldz]: the latent columns of the decoder input; nz = 0: absent
  * computed on the bf16 matrix cores from exact piece products: every fp32 operand is split into three bf16 pieces
  * (x = p0 + p1 + p2 exactly), a product of two pieces is exact in fp32 and the partial products accumulate in fp32.  Of the
- * 3 x 3 piece pairs of an H or Z value and a dz value, the three below 2^-25 of the product (less than the rounding of one
- * fp32 multiply) are left out since round 4: 6 bf16 MFMAs instead of 8 f32 MFMAs at 1/16 of the rate.  x_exact_bf16 != 0
+ * 3 x 3 piece pairs of an H or Z value and a dz value, the three with i + j >= 3 (below 2^-23 of the product for ANY operands: a piece is
+ * at most 2^-8 of the one before; near 2^-27, one fp32 multiply's rounding, for random mantissas) are left out since round 4: 6 bf16 MFMAs instead of 8 f32 MFMAs at 1/16 of the rate.  x_exact_bf16 != 0
  * promises that every X value is exactly representable in bf16 (0/1 piano-roll frames, any uint8): those rows then need
  * one piece, and their products with all three dz pieces are exact.  The products leave as split-K slabs: ws >= clv_lstm_wgrad_workspace_bytes,
  * and like the GEMMs' deferred form (job) the final sums (C = beta*C + sum) are formed by the reduction, now (job == NULL) or by
