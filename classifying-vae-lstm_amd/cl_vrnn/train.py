@@ -9,7 +9,7 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn.model import get_model  # noqa: E402
-from clvae_amd.cli import OPTIMIZER_FLAGS, TrainPlan, parser_for  # noqa: E402
+from clvae_amd.cli import AUGMENT_FLAGS, OPTIMIZER_FLAGS, TrainPlan, parser_for  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
 from clvae_amd.utils.weightnorm import data_based_init  # noqa: E402
 
@@ -51,4 +51,4 @@ def build_parser():
 
 
 if __name__ == '__main__':
-    train(parser_for('cl_vrnn.train', OPTIMIZER_FLAGS).parse_args())
+    train(parser_for('cl_vrnn.train', OPTIMIZER_FLAGS + AUGMENT_FLAGS).parse_args())

@@ -107,6 +107,13 @@ OPTIMIZER_FLAGS = [
     Flag(('--lr_decay',), float, 0.0, 'learning rate lr / (1 + lr_decay * iterations) (0: off)'),
 ]
 
+# transposition augmentation of the training windows (not in the reference; both train.py)
+AUGMENT_FLAGS = [
+    Flag(('--transpose',), int, 0, 'transpose every training window by a random number of semitones in -K..K, drawn per step on '
+                                   'the device among the shifts that keep its notes on the keyboard and its key among the '
+                                   'classes (0: off; at most 12)'),
+]
+
 DEVICE_LOOP_FLAGS = [
     Flag(('--device_loop',), ON, False, 'generate all -n samples in one device-side frame loop (Philox noise; opt-in: the default is the reference host loop)'),
     Flag(('--host_loop',), ON, False, 'frame loop on the host with np.random, like the reference (the default; overrides --device_loop)'),
@@ -325,6 +332,8 @@ class _Parser(argparse.ArgumentParser):
                 self.error(str(e))
             if getattr(ns, 'host_loop', False):
                 self.error('--voices runs on the device loop: not with --host_loop')
+        if not 0 <= getattr(ns, 'transpose', 0) <= 12:
+            self.error('--transpose must be in 0..12')
         temper = temperature_kwargs(ns)
         if temper:
             from .engine_generate import temper_args
@@ -403,6 +412,23 @@ class TrainPlan:
             return type(opt)(lr=opt.lr, beta_1=opt.beta_1, beta_2=opt.beta_2, epsilon=opt.epsilon, **clip)
         return OptimizerSpec.resolve(opt, **clip)   # 'adam', 'rmsprop'
 
+    def augment(self, P, w_train):
+        """--transpose K: the augment.TransposePlan of the training windows (None when the flag is 0 or absent)"""
+        K = getattr(self.args, 'transpose', 0)
+        if not K:
+            return None
+        if np.ndim(P.x_train) == 2 and self.args.seq_length > 1:
+            # cl_vae's flattened windows keep only the notes that sound somewhere: a column is no semitone any more
+            raise SystemExit("--transpose shifts frames of all 88 notes: not with cl_vae's --seq_length > 1")
+        from .augment import TransposePlan
+        plan = TransposePlan.build([P.y_train, P.x_train], P.train_song_keys, P.key_map, semitones=K,
+                                   n_classes=w_train.shape[1])
+        if self.rank == 0:
+            n = plan.counts()
+            print("Transposing by up to %d semitones: %d to %d of %d shifts allowed per window."
+                  % (K, n.min(), n.max(), 2 * K + 1))
+        return plan
+
     def describe(self, model):
         if self.rank == 0:
             save_model_in_pieces(model, self.args)
@@ -417,7 +443,7 @@ class TrainPlan:
         else:
             x_tr, x_va = P.x_train, P.x_valid
         hist = model.fit(x_tr, [P.y_train, w_train, w_train, P.y_train], shuffle=True, epochs=a.num_epochs,
-                         batch_size=a.batch_size, callbacks=self.callbacks,
+                         batch_size=a.batch_size, callbacks=self.callbacks, augment=self.augment(P, w_train),
                          validation_data=(x_va, [P.y_valid, w_valid, w_valid, P.y_valid]))
         at = best_epoch(hist.history['val_loss'], self.first_epoch if best_from is None else best_from)
         return {k: v[at] for k, v in hist.history.items()}

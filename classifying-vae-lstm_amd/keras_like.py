@@ -250,12 +250,14 @@ class Model:
         return logs
 
     def fit(self, x, y, shuffle=True, epochs=1, batch_size=None, callbacks=None, validation_data=None, verbose=1,
-            initial_epoch=0):
+            initial_epoch=0, augment=None):
         """Keras' fit() loop on device-resident data.  Under torch.distributed (one process per GPU) the
         model holds this rank's slice of every global batch: `batch_size` is the GLOBAL batch (world x the model's
         batch), rank 0 draws the epoch permutation and broadcasts it, rank r takes rows [r*B, (r+1)*B) of each
         global batch, gradients are averaged inside the step, the epoch's loss sums and the validation sums are
-        all-reduced once per epoch, and callbacks that write files run on rank 0 only (Callback.rank0_only)."""
+        all-reduced once per epoch, and callbacks that write files run on rank 0 only (Callback.rank0_only).
+        augment: an augment.TransposePlan for the training rows -- every row of every training batch is transposed by a
+        random allowed shift, drawn and applied by the step's staging launch; validation is never augmented."""
         eng = self.engine
         rank, world = _dp()
         B = eng.B
@@ -272,6 +274,8 @@ class Model:
         d_cur, d_hist = self._data_to_dev(cur, hist, dev)
         d_w = _to_dev(w_true, dev)
         d_tgt = None if tgt is None else self._data_to_dev(tgt, None, dev)[0]
+        if augment is not None:
+            augment = augment.to(dev)
         val = None
         if validation_data is not None:
             vc, vh, vw = self._split_inputs(validation_data[0], validation_data[1])
@@ -316,7 +320,8 @@ class Model:
                 if ts._bound is None or ts._bound['cur'] is not d_cur:
                     # the epoch's batches are assembled by the step itself, from the device step counter: batch j of an epoch
                     # = rows idx_dev[j * GB + rank * B ..] (the permutation is rewritten in place per epoch)
-                    ts.bind_batches(d_cur, d_hist, d_w, idx=idx_dev, period=n // GB, stride=GB, offset=rank * B, d_target=d_tgt)
+                    ts.bind_batches(d_cur, d_hist, d_w, idx=idx_dev, period=n // GB, stride=GB, offset=rank * B, d_target=d_tgt,
+                                    augment=augment)
                     ts.loss_acc = self._acc
                 if world > 1 and ts.dp_trials is None and ts.ar is not None:
                     # once per fit: which weight-gradient grid is faster next to the real all-reduce on this node (timed on

@@ -720,15 +720,8 @@ def gather_rows(rows, row_elems, src, idx, out, chunk=0, out_ld=0):
 NOTE_ROW, NOTE_NONE = 96, 88       # CLV_NOTE_ROW / CLV_NOTE_NONE (include/clvae.h)
 
 
-def gather_rows_multi(rows, idx, segs, row0=0, notes=None, cursor=None):
-    """segs: up to 4 (src, out, row_elems, chunk, out_ld[, stride, offset, table]); one launch; idx None = rows
-    row0..row0+rows-1.  A uint8 src (binary frames kept as bytes) is converted to float on the way -- or copied as bytes when
-    `out` is a uint8 tensor too.  With (stride,
-    offset, table) source row r starts at element table[idx[r]] * stride + offset: windows of a frame store.
-    notes: per segment None or a uint8 tensor [rows * pieces, NOTE_ROW] that receives the frames' note lists (uint8
-    sources of binary frames only): what lstm_pair_fwd gathers the input projections from.
-    cursor = (step_dev, step0, period, stride, offset): batch j = (step - step0) mod period, rows j * stride + offset ..
-    of the row list, chosen by the launch itself from the device step counter (a node of the step's graph)."""
+def _gather_args(segs, notes, cursor):
+    """the segment arrays, note outputs and batch cursor of gather_rows_multi / gather_transposed as ctypes arguments"""
     n = len(segs)
     P, I, U = C.c_void_p * n, C.c_int64 * n, C.c_int32 * n
     src = P(*[s_[0].data_ptr() for s_ in segs])
@@ -748,8 +741,44 @@ def gather_rows_multi(rows, idx, segs, row0=0, notes=None, cursor=None):
     cur = None      # (step_dev int32 tensor, step0, period, stride, offset): the batch is chosen on the device
     if cursor is not None:
         cur = C.byref(_lib.BatchCursor(cursor[0].data_ptr(), int(cursor[1]), int(cursor[2]), int(cursor[3]), int(cursor[4])))
+    return n, src, u8, out, re, ch, ld, st, of, tb, nt, cur
+
+
+def gather_rows_multi(rows, idx, segs, row0=0, notes=None, cursor=None):
+    """segs: up to 4 (src, out, row_elems, chunk, out_ld[, stride, offset, table]); one launch; idx None = rows
+    row0..row0+rows-1.  A uint8 src (binary frames kept as bytes) is converted to float on the way -- or copied as bytes when
+    `out` is a uint8 tensor too.  With (stride,
+    offset, table) source row r starts at element table[idx[r]] * stride + offset: windows of a frame store.
+    notes: per segment None or a uint8 tensor [rows * pieces, NOTE_ROW] that receives the frames' note lists (uint8
+    sources of binary frames only): what lstm_pair_fwd gathers the input projections from.
+    cursor = (step_dev, step0, period, stride, offset): batch j = (step - step0) mod period, rows j * stride + offset ..
+    of the row list, chosen by the launch itself from the device step counter (a node of the step's graph)."""
+    n, src, u8, out, re, ch, ld, st, of, tb, nt, cur = _gather_args(segs, notes, cursor)
     check(_lib.lib().clv_gather_rows_multi(rows, _ptr(idx), int(row0), n, src, u8, out, re, ch, ld, st, of, tb, nt, cur, _stream()),
           "clv_gather_rows_multi")
+
+
+class TransposeDraw(C.Structure):
+    """clv_transpose_draw (include/clvae.h)."""
+    _fields_ = [("allowed", C.c_void_p), ("class_map", C.c_void_p),
+                ("K", C.c_int32), ("C", C.c_int32), ("D", C.c_int32), ("label_seg", C.c_int32),
+                ("seed", C.c_uint64), ("first_row", C.c_uint64), ("step", C.c_uint32),
+                ("step_dev", C.c_void_p), ("shift_out", C.c_void_p)]
+
+
+def gather_transposed(rows, idx, segs, allowed, class_map, K, D, seed, step=0, step_dev=None, first_row=0, shift_out=None,
+                      label_seg=None, row0=0, notes=None, cursor=None):
+    """gather_rows_multi with a random transposition per output row: segs, idx, row0, notes and cursor as
+    there; every segment is a uint8 source of frames of D bytes (float or uint8 output) but segs[label_seg], the float labels
+    [*, C].  allowed: uint32 [n] per SOURCE row, bit j = shift j - K allowed; class_map: int32 [(2K+1) * C]; the shift of output
+    row r is drawn from the Philox uniform of (seed, step or *step_dev, TRANSPOSE_STREAM, first_row + r) and written to
+    shift_out (int32 [rows], optional)."""
+    n, src, u8, out, re, ch, ld, st, of, tb, nt, cur = _gather_args(segs, notes, cursor)
+    n_cls = int(segs[label_seg][2]) if label_seg is not None else int(class_map.numel()) // (2 * int(K) + 1)
+    draw = TransposeDraw(_ptr(allowed), _ptr(class_map), int(K), n_cls, int(D), -1 if label_seg is None else int(label_seg),
+                         int(seed) & (2 ** 64 - 1), int(first_row), int(step) & 0xFFFFFFFF, _ptr(step_dev), _ptr(shift_out))
+    check(_lib.lib().clv_gather_transposed(rows, _ptr(idx), int(row0), n, src, u8, out, re, ch, ld, st, of, tb, nt, cur,
+                                           C.byref(draw), _stream()), "clv_gather_transposed")
 
 
 def philox_normal2(out0, n0, stream0, first0, out1, n1, stream1, first1, seed, step=0, step_dev=None):

@@ -39,6 +39,9 @@ KEY_STREAM = 0xFFFFFFFB
 # (engine_generate.generate_gibbs; step = generation step, index = GLOBAL row; drawn inside csrc/smc.hip), the
 # one below that:
 GIBBS_STREAM = 0xFFFFFFFA
+# and, for the uniform that picks a training window's transposition (augment.py; step = the optimizer's
+# `iterations`, index = GLOBAL batch row; drawn inside csrc/transpose_aug.hip), the one below that:
+TRANSPOSE_STREAM = 0xFFFFFFF9
 
 
 class DevWindows:
@@ -139,6 +142,7 @@ class TrainStep:
         self._warm = False
         self._bound = None          # bind_batches(): the mini-batch assembly as the first node of the captured step
         self.loss_acc = None        # a [>= 5] float tensor: every step adds its five loss means to it (inside the graph)
+        self.shifts = None          # int32 [B]: the transpositions of the last step's rows (bind_batches(augment=...))
 
     # -- pieces -----------------------------------------------------------
     def noise_spec(self, stream_offset=0, row0=None):
@@ -172,15 +176,32 @@ class TrainStep:
             self.Y = torch.zeros_like(self.X) if on else None
             self.recapture()
 
-    def bind_batches(self, d_cur, d_hist, d_w, idx=None, period=1, stride=None, offset=0, d_target=None):
+    def bind_batches(self, d_cur, d_hist, d_w, idx=None, period=1, stride=None, offset=0, d_target=None, augment=None):
         """From now on step() assembles its own mini-batch, as the first node of the captured graph: batch j =
         (iterations - iterations at the first bound step) mod `period`, rows idx[j * stride + offset + r] (idx None: rows
         j * stride + offset + r) of the device-resident data set, r < B.  `iterations` is the optimizer's device counter,
         so nothing is staged from the host: a step is one graph launch (Model.fit: idx = the epoch's permutation, rewritten
-        in place per epoch; period = batches per epoch; stride = global batch; offset = rank * B)."""
+        in place per epoch; period = batches per epoch; stride = global batch; offset = rank * B).
+        augment: an augment.TransposePlan on the device -- every row of every batch is transposed by a shift drawn in the
+        staging launch (keyed by the step's seed, `iterations` and the row's global number rank * B + r; the
+        label moves with it); `shifts` holds the last step's.  Needs uint8 frames."""
+        if augment is not None:
+            D = self.eng.cfg['D']
+            for x in (d_cur, d_hist, d_target):
+                t = x.store if isinstance(x, DevWindows) else x
+                if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous()):
+                    raise ValueError("transposition augmentation shifts uint8 frames; got %s frames" % (t.dtype,))
+            if D % 4 or d_w is None or augment.class_map.numel() != (2 * augment.K + 1) * int(self.w_true.shape[1]):
+                raise ValueError("the plan's class map does not fit the model's %d classes (or D %% 4 != 0)"
+                                 % int(self.w_true.shape[1]))
+            if augment.allowed.device.type != self.X.device.type or int(augment.allowed.shape[0]) != int(d_cur.shape[0]):
+                raise ValueError("the plan must be on the model's device and hold one mask per row of the data set")
+            if self.shifts is None:
+                self.shifts = torch.zeros(self.eng.B, dtype=torch.int32, device=self.X.device)
         self.set_target(d_target is not None)
         self._bound = dict(cur=d_cur, hist=d_hist, w=d_w, idx=idx, period=int(period),
                            stride=int(self.eng.B if stride is None else stride), offset=int(offset), target=d_target,
+                           augment=augment,
                            step0=int(self.eng.P.iterations.item()))       # (one host read, here: never inside a capture)
         self.recapture()
 
@@ -214,8 +235,16 @@ class TrainStep:
         b = self._bound
         self._f8 = self._bytes_batch(b)
         segs = self._segments(b['cur'], b['hist'], b['w'], b['target'], bytes_out=self._f8)
-        ops.gather_rows_multi(self.eng.B, b['idx'], segs, notes=self._note_outputs(b['cur'], b['hist'], len(segs)),
-                              cursor=(self.eng.P.iterations, b['step0'], b['period'], b['stride'], b['offset']))
+        notes = self._note_outputs(b['cur'], b['hist'], len(segs))
+        cursor = (self.eng.P.iterations, b['step0'], b['period'], b['stride'], b['offset'])
+        plan = b['augment']
+        if plan is None:
+            ops.gather_rows_multi(self.eng.B, b['idx'], segs, notes=notes, cursor=cursor)
+            return
+        # the same segments, every row's frames moved by the shift the launch draws for it
+        ops.gather_transposed(self.eng.B, b['idx'], segs, plan.allowed, plan.class_map, plan.K, self.eng.cfg['D'], self.seed,
+                              step_dev=self.eng.P.iterations, first_row=self.rank * self.eng.B, shift_out=self.shifts,
+                              label_seg=[k for k, s_ in enumerate(segs) if s_[0] is b['w']][0], notes=notes, cursor=cursor)
 
     def _label_stage(self):
         """ops.label_stage of the bound batches when the step's first launch can assemble them itself -- cl_vrnn: the label
@@ -254,7 +283,8 @@ class TrainStep:
     def _main(self):
         self._f8 = st = None
         if self._bound is not None:
-            st = self._label_stage()         # the step's first launch assembles the mini-batch (stage=), else a launch of its own
+            # the step's first launch assembles the mini-batch (stage=), else a launch of its own (always with a transposition plan)
+            st = self._label_stage() if self._bound['augment'] is None else None
             if st is None:
                 self._stage_bound()
         if self._folded():

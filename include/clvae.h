@@ -93,6 +93,25 @@ typedef struct clv_label_stage {
                                             * later launches read frames as bytes (x_u8 / y_u8 / CLV_FRAMES_U8) */
 } clv_label_stage;
 
+/* clv_gather_transposed: the TRANSPOSITION every output row of the staging launch gets, drawn by the launch.
+ * Source row sr = idx[base + r] (before any window table) has the mask m = allowed[sr] & (2^(2K+1) - 1): bit j set = the
+ * shift s = j - K semitones is allowed.  n = popcount(m); n == 0: s = 0; else u = the clv_philox_uniform value of (seed,
+ * step, stream 0xFFFFFFF9, index first_row + r), k = min((int)(u * (float)n), n - 1) in fp32, and s = (position of the k-th
+ * set bit of m, counted from bit 0) - K.  step is *step_dev when step_dev is not NULL, else `step`.  All frame segments
+ * and note lists of output row r use that one s; shift_out[r] = s (shift_out may be NULL).
+ * label_seg (< 0: none): the segment that holds the float labels [*, C]; its output row is zeroed and then
+ * w_out[r, class_map[(s + K) * C + c]] += w_src[sr, c] for every c whose map entry is >= 0 (ascending c).
+ * D: bytes of a frame, a multiple of 4; every other segment is a uint8 source of whole frames. */
+typedef struct clv_transpose_draw {
+  const uint32_t* allowed;
+  const int32_t* class_map;                /* [(2K+1) * C] */
+  int32_t K, C, D, label_seg;              /* 0 <= K <= 12 */
+  uint64_t seed, first_row;
+  uint32_t step;
+  const int32_t* step_dev;
+  int32_t* shift_out;
+} clv_transpose_draw;
+
 /* clv_vrnn_label_fwd_x(proj != NULL; needs stage with X8): the launch ALSO forms the LSTMs' frame projections of the same
  * mini-batch (clv_sparse_proj2's product, bit for bit) -- out_cur[b * T + t, :N] = frame t of the current row b . K_cur
  * ([D, N]), out_hist likewise over the history rows and K_hist (NULL: none) -- in workgroups of their own that read the byte
@@ -866,6 +885,21 @@ int clv_gather_rows_multi(int64_t rows, const int64_t* idx, int64_t row0, int ns
                                  const int64_t* src_stride, const int64_t* src_offset,
                                  const int64_t* const* src_table, unsigned char* const* notes_out,
                                  const clv_batch_cursor* cursor, void* stream);
+
+/* clv_gather_rows_multi with a random transposition per output row (transposition augmentation of the training windows,
+ * DESIGN.md 21; not in the reference).  Same segment list, row list, batch cursor and note-list outputs; `draw` says how the
+ * shifts are drawn (clv_transpose_draw).  Frame segments are uint8 sources of frames of draw->D bytes (src_u8[k] 1: float
+ * output, 2: uint8 output; chunk[k] is 0 -- frames packed, out_ld = D -- or D with out_ld[k] >= D between the frames of the
+ * output): out[p] = in[p - s] where 0 <= p - s < D, else 0, frame by frame -- a shifted read never takes a byte of the
+ * neighbouring frame and never leaves the store.  The note lists are those of the shifted frames.  Segment draw->label_seg
+ * holds the float labels (src_u8 0, row_elems C, no table).  CLV_EINVAL before any launch: K > 12, a float frame source, D,
+ * a stride, an offset or out_ld not a multiple of 4, allowed or class_map NULL, more than 4 segments, misaligned bases. */
+int clv_gather_transposed(int64_t rows, const int64_t* idx, int64_t row0, int nseg,
+                          const void* const* src, const int32_t* src_u8, void* const* out,
+                          const int64_t* row_elems, const int64_t* chunk, const int64_t* out_ld,
+                          const int64_t* src_stride, const int64_t* src_offset,
+                          const int64_t* const* src_table, unsigned char* const* notes_out,
+                          const clv_batch_cursor* cursor, const clv_transpose_draw* draw, void* stream);
 
 /* the five loss scalars of a step in one launch: out[k] = scale[k] * sum_{i<n[k]} x[k][i*stride[k]], k < 5
  * (vae, kl_z, kl_w, w_rec, acc means; fixed summation order => deterministic). */
