@@ -174,7 +174,7 @@ class TrainStep:
         input frames.  Changes what the captured step reads, so the graphs are dropped."""
         if bool(on) != (self.Y is not None):
             self.Y = torch.zeros_like(self.X) if on else None
-            self.recapture()
+            self._route_changed()
 
     def bind_batches(self, d_cur, d_hist, d_w, idx=None, period=1, stride=None, offset=0, d_target=None, augment=None):
         """From now on step() assembles its own mini-batch, as the first node of the captured graph: batch j =
@@ -182,6 +182,9 @@ class TrainStep:
         j * stride + offset + r) of the device-resident data set, r < B.  `iterations` is the optimizer's device counter,
         so nothing is staged from the host: a step is one graph launch (Model.fit: idx = the epoch's permutation, rewritten
         in place per epoch; period = batches per epoch; stride = global batch; offset = rank * B).
+        d_cur / d_hist / d_target: DevWindows, or tensors of whole rows -- contiguous, or a view whose rows are each contiguous
+        (x[:, 1:] of windows of T + 1 frames: taken by its row stride, through the gather launch); anything else is refused.
+        The step after a bind runs eagerly, the one after that is captured (_route_changed).
         augment: an augment.TransposePlan on the device -- every row of every batch is transposed by a shift drawn in the
         staging launch (keyed by the step's seed, `iterations` and the row's global number rank * B + r; the
         label moves with it); `shifts` holds the last step's.  Needs uint8 frames."""
@@ -203,12 +206,25 @@ class TrainStep:
                            stride=int(self.eng.B if stride is None else stride), offset=int(offset), target=d_target,
                            augment=augment,
                            step0=int(self.eng.P.iterations.item()))       # (one host read, here: never inside a capture)
-        self.recapture()
+        self._prepare_bound()
+        self._route_changed()
+
+    def _prepare_bound(self):
+        """Whatever the first bound step would otherwise do at its first use -- which, on a step that is already warm, is
+        inside the capture: the allocation of the byte batch (a hipMalloc on the capture's fresh stream) and the host read
+        of _is_binary_u8 (a sync).  Both happen here, once per bind_batches()."""
+        b, eng = self._bound, self.eng
+        if self.is_vrnn and eng.frames_u8_route() is not None:
+            self._byte_buffers(eng.off > 0)
+        if getattr(eng, 'fuse_notes', False):
+            for x in (b['cur'], b['hist']):
+                if x is not None:
+                    self._is_binary_u8(x.store if isinstance(x, DevWindows) else x)
 
     def unbind_batches(self):
         if self._bound is not None:
             self._bound = None
-            self.recapture()
+            self._route_changed()
 
     def _bytes_batch(self, b):
         """(X8, Xp8) when the bound batches can stay uint8 for the whole step, else None (see __init__)."""
@@ -225,7 +241,8 @@ class TrainStep:
         return self._byte_buffers(need_hist)
 
     def _byte_buffers(self, need_hist):
-        """(X8, Xp8): the uint8 twins of X / Xp (Xp8 None without history frames), allocated at their first use"""
+        """(X8, Xp8): the uint8 twins of X / Xp (Xp8 None without history frames).  Allocated by bind_batches() (_prepare_bound),
+        never at their first use: that is inside the step's capture once the step is warm."""
         if self.X8 is None:
             self.X8 = torch.zeros_like(self.X, dtype=torch.uint8)
             self.Xp8 = torch.zeros_like(self.X, dtype=torch.uint8) if need_hist else None
@@ -273,7 +290,7 @@ class TrainStep:
             return None
         if not eng.frames_exact_bf16:      # byte frames (what _segments() notes for the gather)
             eng.frames_exact_bf16 = True
-            self.recapture()
+            self._route_changed()
         hist_chunk, hist_ld = (D, self.xp_ld) if self.xp_ld else (row, row)
         # the label launch leaves the batch as BYTES (a quarter of its stores) and every later launch of the step reads bytes
         self._f8 = f8 = self._byte_buffers(need_hist) if eng.frames_u8_route() == 'label' else None
@@ -341,13 +358,21 @@ class TrainStep:
         row, D = int(self.X[0].numel()), self.eng.cfg['D']
 
         def src(x):
-            return (x.store, (D, x.t0 * D, x.starts)) if isinstance(x, DevWindows) else (x, ())
+            if isinstance(x, DevWindows):
+                return (x.store, (D, x.t0 * D, x.starts))
+            if x.is_contiguous():
+                return (x, ())
+            # a view whose rows are whole but not back to back (frames 1 .. T of windows of T + 1): the launch takes the row
+            # stride; it reads memory, not the tensor's strides, so anything else would be assembled from the wrong elements
+            if x.dim() < 2 or not x[0].is_contiguous() or x.stride(0) <= 0:
+                raise ValueError("the rows of a batch source must each be contiguous in memory (strides %s)" % (tuple(x.stride()),))
+            return (x, (int(x.stride(0)), 0, None))
         # frames that arrive as bytes are exactly representable in bf16: the LSTM kernel-gradient products then need
         # one bf16 piece for the frame rows (VrnnEngine.frames_exact_bf16); the choice is baked into the captured step
         exact = all(src(x)[0].dtype == torch.uint8 for x in (cur, hist) if x is not None)
         if self.eng.frames_exact_bf16 != exact:
             self.eng.frames_exact_bf16 = exact
-            self.recapture()
+            self._route_changed()
         c, cx = src(cur)
         if bytes_out is not None:
             segs = [(c, bytes_out[0], row, D, D) + cx]
@@ -380,7 +405,7 @@ class TrainStep:
         ok = all(x is not None and self._is_binary_u8(x.store if isinstance(x, DevWindows) else x) for x in need)
         if eng.notes_valid != ok:
             eng.notes_valid = ok
-            self.recapture()
+            self._route_changed()
         if not ok:
             return None
         out = [None] * nseg                                # segments: current frames, [history frames], labels, [targets]
@@ -390,10 +415,11 @@ class TrainStep:
         return out
 
     def _is_binary_u8(self, t):
-        """uint8 and every value 0 or 1; one reduction (and host sync) per distinct storage, remembered."""
+        """uint8 and every value 0 or 1; one reduction (and host sync) per distinct storage, remembered -- until the storage
+        is written again (the tensor's version counter, which its views share): a store overwritten in place is read anew."""
         if t.dtype != torch.uint8:
             return False
-        key = (t.untyped_storage().data_ptr(), t.untyped_storage().nbytes())
+        key = (t.untyped_storage().data_ptr(), t.untyped_storage().nbytes(), t._version)
         cache = self.__dict__.setdefault('_binary_stores', {})
         if key not in cache:
             whole = torch.empty(0, dtype=torch.uint8, device=t.device).set_(t.untyped_storage())
@@ -486,6 +512,14 @@ class TrainStep:
         """Drop the captured graphs (values baked into them changed, e.g. annealed loss weights); the next step()
         captures again.  Buffers, streams and the all-reduce buckets stay."""
         self._graphs = None
+
+    def _route_changed(self):
+        """The next step takes other launches than the last one did (another source of batches, another form of the
+        assembly, frames of another kind): the graphs are dropped AND the next step runs eagerly, like the first one -- the
+        engine creates and grows workspaces at the first use of a launch, and a capture is no place for an allocation (its
+        stream is fresh: the allocator has no cached block for it and would have to ask the driver)."""
+        self.recapture()
+        self._warm = False
 
     def step(self):
         if not self.use_graph:

@@ -1,4 +1,4 @@
-"""-m gpu: the entry points of csrc/pointwise.hip (all but clv_gather_rows_multi) against the fp64 reference of
+"""-m gpu: the entry points of csrc/pointwise.hip (clv_gather_rows_multi: tests/test_gpu_gather.py) against the fp64 reference of
 tests/pointwise_reference.py, over its case tables: EVERY output of every call, element by element, within its own bound
 (bit for bit where the reference says so), flagged elements excepted.
 
