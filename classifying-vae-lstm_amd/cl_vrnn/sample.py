@@ -8,9 +8,9 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, RESUME_FLAGS, TEMPERATURE_FLAGS,  # noqa: E402
-                           VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, morph_kwargs, parser_for, resume_kwargs, resuming, temperature_kwargs,
-                           voices_kwargs)
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, NOVELTY_FLAGS, RESUME_FLAGS,  # noqa: E402
+                           TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, morph_kwargs, novelty_check, parser_for,
+                           resume_kwargs, resuming, temperature_kwargs, voices_kwargs)
 from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, print_renewed, voice_constraints,  # noqa: E402
                                  voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
@@ -18,6 +18,7 @@ from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
 from clvae_amd.morph import morph  # noqa: E402
+from clvae_amd.novelty import audit_samples  # noqa: E402
 from clvae_amd.vary import vary  # noqa: E402
 
 
@@ -175,7 +176,10 @@ def sample(args):
     on_device = bool(voice) or getattr(args, 'voices', None) is not None or bool(getattr(args, 'vary', False)) or getattr(args, 'morph', None) is not None or bool(
         temperature_kwargs(args)) or resuming(args) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
-    return gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
+    novelty_check(args, margs['original_dim'])
+    rolls = gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
+    audit_samples(rolls, args)          # --novelty: the rolls just written against the training songs
+    return rolls
 
 
 def build_parser():
@@ -185,4 +189,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vrnn.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + NOVELTY_FLAGS).parse_args())

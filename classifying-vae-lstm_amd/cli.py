@@ -190,6 +190,24 @@ GIBBS_FLAGS = [
 ]
 
 
+# novelty audit (not in the reference): the rolls a sampling tool writes against the training split's songs
+NOVELTY_FLAGS = [
+    Flag(('--novelty',), int, None, 'audit the samples for copied passages: every window of this many frames of every sample '
+                                    "against every window of the training split's songs (Hamming distance on the device), and "
+                                    'the same for the test split as a baseline; prints per sample the nearest passage'),
+    Flag(('--novelty_transpose',), int, 0, 'with --novelty: also look for the passage transposed by up to this many '
+                                           'semitones (0..12)'),
+]
+
+
+def novelty_check(args, width):
+    """--novelty compares 88-key rolls with the data set's songs: SystemExit for a model whose samples are not such rolls
+    (cl_vae with --seq_length > 1 keeps only the notes that sound somewhere -- what --transpose is refused for)"""
+    if getattr(args, 'novelty', None) is not None and int(width) != 88:
+        raise SystemExit("--novelty compares 88-key rolls with the training songs: not for a model whose frames are %d wide"
+                         % width)
+
+
 def gibbs_kwargs(args):
     """--sweeps as keyword arguments of harmonize: empty without the flag (also for parsers without it)"""
     k = getattr(args, 'sweeps', None)
@@ -273,7 +291,7 @@ class _Parser(argparse.ArgumentParser):
     with --particles and not with --infer_key, a temperature other than 1 not with --host_loop (the host loop is the reference's and has none), --vary not with
     --harmonize or --host_loop, --to_key / --vary_history only with --vary, --morph >= 1 and not with --harmonize, --vary or
     --host_loop, --chunk >= 1 and a well-formed --modulate, neither with --particles, --vary, --morph or --host_loop, a
-    well-formed --voices LO[:HI] and not with --host_loop"""
+    well-formed --voices LO[:HI] and not with --host_loop, --novelty >= 1, --novelty_transpose in 0..12 and only with --novelty"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -334,6 +352,13 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--voices runs on the device loop: not with --host_loop')
         if not 0 <= getattr(ns, 'transpose', 0) <= 12:
             self.error('--transpose must be in 0..12')
+        novelty = getattr(ns, 'novelty', None)
+        if novelty is not None and novelty < 1:
+            self.error('--novelty must be >= 1')
+        if not 0 <= getattr(ns, 'novelty_transpose', 0) <= 12:
+            self.error('--novelty_transpose must be in 0..12')
+        if novelty is None and getattr(ns, 'novelty_transpose', 0):
+            self.error('--novelty_transpose needs --novelty')
         temper = temperature_kwargs(ns)
         if temper:
             from .engine_generate import temper_args

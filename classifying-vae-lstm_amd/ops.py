@@ -970,6 +970,29 @@ def key_track_smooth(N, Cn, win_off, logp, log_prior, log_trans, kappa, post, pa
                                           _stream()), "clv_key_track_smooth")
 
 
+def roll_nearest_workspace_bytes(Fq, Fc, Wq):
+    return int(_lib.lib().clv_roll_nearest_workspace_bytes(int(Fq), int(Fc), int(Wq)))
+
+
+def roll_nearest(Nq, Nc, W, hop, S, D, Fq, Fc, Wq, q_roll, q_off, c_roll, c_off, qwin_off, exclude, dist, shift, cframe,
+                 workspace=None):
+    """the nearest corpus window of every query window (clv_roll_nearest): q_roll [>= Fq, D], c_roll [>= Fc, D]
+    uint8 0/1; q_off [Nq+1], c_off [Nc+1], qwin_off [Nq+1] int64 on the device, their last entries Fq, Fc, Wq; exclude [Nq]
+    int32 or None; dist, shift [>= Wq] int32 and cframe [>= Wq] int64 receive (dist, s, global corpus frame) of the smallest
+    (dist, rank(s), frame), or (-1, 0, -1).  workspace: a uint8 tensor of roll_nearest_workspace_bytes(Fq, Fc, Wq) bytes,
+    or None to allocate one; it is returned."""
+    Fq, Fc, Wq = int(Fq), int(Fc), int(Wq)
+    if Fq > q_roll.shape[0] or Fc > c_roll.shape[0] or Wq > min(dist.numel(), shift.numel(), cframe.numel()):
+        raise _lib.ClvError("roll_nearest: Fq, Fc or Wq name more rows than the tensors hold")
+    if workspace is None:
+        workspace = torch.empty(max(roll_nearest_workspace_bytes(Fq, Fc, Wq), 16), dtype=torch.uint8, device=q_roll.device)
+    check(_lib.lib().clv_roll_nearest(int(Nq), int(Nc), int(W), int(hop), int(S), int(D), Fq, Fc, Wq, _ptr(q_roll), _ptr(q_off),
+                                      _ptr(c_roll), _ptr(c_off), _ptr(qwin_off), _ptr(exclude), _ptr(workspace),
+                                      int(workspace.numel()), _ptr(dist), _ptr(shift), _ptr(cframe), _stream()),
+          "clv_roll_nearest")
+    return workspace
+
+
 class Graph:
     """Capture the kernels enqueued inside the ``with`` block on the current stream; replay with launch()."""
 

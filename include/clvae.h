@@ -1184,6 +1184,37 @@ int clv_key_track_smooth(int N, int C, const int64_t* win_off, const float* logp
                          const double* log_trans, double kappa, double* post, int32_t* path, double* log_evidence,
                          double* piece_post, void* stream);
 
+/* ------------------------------------------------------------ novelty audit --
+ * The nearest corpus passage of every window of a batch of pieces: did a generated piece replay bars of a
+ * training piece, possibly in another key?
+ *
+ * clv_roll_nearest.  q_roll [Fq, D] and c_roll [Fc, D] are uint8 0/1 rolls, the pieces one after another; q_off [Nq+1] and
+ * c_off [Nc+1] (device int64) hold the first frame of every piece, q_off[Nq] = Fq, c_off[Nc] = Fc.  Query piece n of P_n
+ * frames has J_n = max(0, (P_n - W) / hop + 1) windows of W frames, window j starting at frame a = j * hop of the piece;
+ * its results go to row qwin_off[n] + j (qwin_off [Nq+1], device int64, qwin_off[Nq] = Wq).  Corpus piece m of L_m frames
+ * has a window at every offset b = 0 .. L_m - W.  No window straddles two pieces, on either side.
+ *   dist(q, s, c) = sum over t < W and 0 <= d < D of [Q[a + t, d - s] != C[b + t, d]], Q reading 0 outside 0 .. D-1.
+ * A shift s in -S .. S is allowed for a query window iff every note d that sounds in it keeps 0 <= d + s < D (s = 0
+ * always is; a silent window allows every s).  exclude (device int32 [Nq], or NULL) removes corpus piece exclude[n] >= 0
+ * from the candidates of query piece n.  Among the candidates (s allowed, corpus window c not excluded) of a query window
+ * the one with the smallest key (dist, rank(s), g), compared lexicographically, is reported: rank orders the shifts 0, -1,
+ * +1, -2, +2, ..., g = c_off[m] + b is the global corpus frame where the match starts.  dist [Wq] int32, shift [Wq] int32 =
+ * s, cframe [Wq] int64 = g; a window without any candidate gets dist = -1, shift = 0, cframe = -1.  All results are exact
+ * integers, and the minimum over a totally ordered key makes a row independent of the other pieces of the batch, of the
+ * order of the pieces and of how the corpus is tiled over workgroups.
+ * The entry cannot read the device-side offsets: the caller passes Fq, Fc and Wq as they stand in q_off[Nq], c_off[Nc]
+ * and qwin_off[Nq], and a workspace of clv_roll_nearest_workspace_bytes(Fq, Fc, Wq) bytes, 16-byte aligned (the frames
+ * of both rolls as 128 bits each, the piece of every corpus frame, a 64-bit key per query window).  Three launches on
+ * `stream`: packing, search (64-bit atomic minima on the keys), unpacking.
+ * CLV_EINVAL before any device work unless Nq, Nc >= 1, 1 <= W <= 1024, hop >= 1, 0 <= S <= 12, 1 <= D <= 116,
+ * 0 <= Fq, Fc, Wq < 2^31, no pointer other than exclude NULL, the workspace aligned and large enough.  Wq = 0 is CLV_OK
+ * and launches nothing.  clv_roll_nearest_workspace_bytes is 0 for sizes outside those ranges. */
+size_t clv_roll_nearest_workspace_bytes(int64_t Fq, int64_t Fc, int64_t Wq);
+int clv_roll_nearest(int Nq, int Nc, int W, int hop, int S, int D, int64_t Fq, int64_t Fc, int64_t Wq,
+                     const uint8_t* q_roll, const int64_t* q_off, const uint8_t* c_roll, const int64_t* c_off,
+                     const int64_t* qwin_off, const int32_t* exclude, void* workspace, size_t workspace_bytes,
+                     int32_t* dist, int32_t* shift, int64_t* cframe, void* stream);
+
 /* ----------------------------------------------------------------- graphs --
  * thin wrappers so a host without HIP bindings can capture a step once and
  * replay it (launch-bound inner loops: SURVEY.md 7.1 step 8). */
