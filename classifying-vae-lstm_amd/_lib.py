@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CLV_LIB: another build of the same ABI (A/B measurements inside one GPU session; tools/build_variant.sh)
 LIB_PATH = os.environ.get("CLV_LIB") or os.path.join(_HERE, "libclvae_hip.so")
 
-ABI_VERSION = 600      # CLV_ABI_VERSION of include/clvae.h
+ABI_VERSION = 610      # CLV_ABI_VERSION of include/clvae.h
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_MASKPOS = 0, 1, 2, 3
 GATE_HARD_SIGMOID, GATE_SIGMOID = 0, 1
 
@@ -115,7 +115,7 @@ class ProfRecord(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int32), ("total_ms", C.c_float)]
 
 
-# The argument lists of the fourteen entry points of the persistent sampling kernels, in named pieces: a count is the number
+# The argument lists of the six entry points of the persistent sampling kernels, in named pieces: a count is the number
 # of names in its piece, never typed by hand.  gate_act is cl_vrnn's, use_x_prev cl_vae's, at the same place.
 def _args(kind, names):
     return [kind] * len(names.split())
@@ -129,7 +129,8 @@ _VRNN_ENC, _VRNN_DEC = _args(_p, "Kx_enc Kw_enc b_enc U_enc Wz bz"), _args(_p, "
 _VAE_ENC, _VAE_DEC = _args(_p, "Kh bh Kz bz"), _args(_p, "Kd bd Ko bo")
 _TEMPER = [_p, _f, _f]                                 # clamp, inv_temperature, z_temperature (decode: the first two)
 _OUT, _OUT_Z = _args(_p, "Xs xhat stream"), _args(_p, "Xs xhat zout stream")
-_RESUME = [_u32] + _args(_p, "state_in state_out")      # _u32: t0, the Philox step of the call's frame 0
+# generate's tail: clamp, tempered, the two factors, t0 (_u32: the Philox step of the call's frame 0) and the two states
+_GENERATE_TAIL = [_p, _i, _f, _f, _u32] + _args(_p, "state_in state_out")
 
 # name -> (restype, argtypes); must list every function of include/clvae.h
 SIGNATURES = {
@@ -188,22 +189,14 @@ SIGNATURES = {
     "clv_latent_head_fwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
     "clv_latent_head_bwd": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "clv_vrnn_generate_supported": (_i, [_i, _i, _i, _i]),
-    "clv_vrnn_generate": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _OUT),
+    "clv_vrnn_generate": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _GENERATE_TAIL + _OUT),
     "clv_vae_generate_supported": (_i, [_i, _i, _i, _i]),
-    "clv_vae_generate": (_i, _VAE_GENERATE + _VAE_ENC + _VAE_DEC + _OUT),
-    "clv_vrnn_generate_clamped": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _args(_p, "clamp") + _OUT),
-    "clv_vae_generate_clamped": (_i, _VAE_GENERATE + _VAE_ENC + _VAE_DEC + _args(_p, "clamp") + _OUT),
-    "clv_vrnn_generate_tempered": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _TEMPER + _OUT),
-    "clv_vae_generate_tempered": (_i, _VAE_GENERATE + _VAE_ENC + _VAE_DEC + _TEMPER + _OUT),
-    "clv_vrnn_vary": (_i, _VARY + _VRNN_ENC + _VRNN_DEC + _TEMPER + _OUT),
-    "clv_vae_vary": (_i, _VARY + _VAE_ENC + _VAE_DEC + _TEMPER + _OUT),
+    "clv_vae_generate": (_i, _VAE_GENERATE + _VAE_ENC + _VAE_DEC + _GENERATE_TAIL + _OUT),
+    "clv_vrnn_vary": (_i, _VARY + _VRNN_ENC + _VRNN_DEC + _TEMPER + _OUT_Z),
+    "clv_vae_vary": (_i, _VARY + _VAE_ENC + _VAE_DEC + _TEMPER + _OUT_Z),
     "clv_take_frame": (_i, [_i64, _i, _i, _p, _p, _p, _p]),
-    "clv_vrnn_vary_latents": (_i, _VARY + _VRNN_ENC + _VRNN_DEC + _TEMPER + _OUT_Z),
-    "clv_vae_vary_latents": (_i, _VARY + _VAE_ENC + _VAE_DEC + _TEMPER + _OUT_Z),
     "clv_vrnn_decode": (_i, _DECODE + _VRNN_DEC + _TEMPER[:2] + _OUT),
     "clv_vae_decode": (_i, _DECODE + _VAE_DEC + _TEMPER[:2] + _OUT),
-    "clv_vrnn_generate_resume": (_i, _VRNN_GENERATE + _VRNN_ENC + _VRNN_DEC + _TEMPER + _RESUME + _OUT),
-    "clv_vae_generate_resume": (_i, _VAE_GENERATE[:-2] + _args(_p, "w") + _VAE_ENC + _VAE_DEC + _TEMPER + _RESUME + _OUT),
     "clv_lerp_rows": (_i, [_i64, _i64] + [_p] * 7),
     "clv_sigmoid_temper": (_i, [_i64, _p, _f, _p]),
     "clv_scale_temper": (_i, [_i64, _p, _f, _p]),

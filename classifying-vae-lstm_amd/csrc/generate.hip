@@ -532,7 +532,7 @@ GenKernel pick_vrnn_kernel(Mode mode, bool hard, bool wide, bool clamped, bool t
   }
 }
 
-// The one launcher: every refusal of the seven entry points, the kernel pick and the launch.  `a` is the call as its entry
+// The one launcher: every refusal of the three entry points, the kernel pick and the launch.  `a` is the call as its entry
 // point filled it (vary and decode: S = 0, nsteps = T; absent inputs null; absent temperatures 1.0f, which is exact).
 int vrnn_launch(const clv::GenArgs& a, Mode mode, bool tempered, int D, int H, int gate_act, void* stream) {
   using namespace clv;
@@ -599,79 +599,24 @@ void set_decoder(clv::GenArgs& a, const float* Kx_dec, const float* Kz, const fl
 }
 }  // namespace
 
+// One entry point per operation (include/clvae.h): a call from or to a state runs the ST instance, any other call the CL and TP
+// instances that its roll and its `tempered` flag name.
 extern "C" int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
                                  uint64_t seed, const float* x_seed, const float* w,
                                  const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
                                  const float* Wz, const float* bz,
                                  const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                                 const float* U_dec, const float* Wo, const float* bo,
-                                 float* Xs, float* xhat, void* stream) {
-  clv::GenArgs a = vrnn_args(N, S, nsteps, L, C, seed, nullptr, Xs, xhat);
-  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
-  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
-  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w;
-  return vrnn_launch(a, Mode::generate, false, D, H, gate_act, stream);
-}
-
-extern "C" int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
-                                         uint64_t seed, const float* x_seed, const float* w,
-                                         const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                                         const float* Wz, const float* bz,
-                                         const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                                         const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                                         float* Xs, float* xhat, void* stream) {
-  if (!clamp) return CLV_EINVAL;             // this entry point is the roll
-  clv::GenArgs a = vrnn_args(N, S, nsteps, L, C, seed, clamp, Xs, xhat);
-  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
-  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
-  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w;
-  return vrnn_launch(a, Mode::generate, false, D, H, gate_act, stream);
-}
-
-extern "C" int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
-                                          uint64_t seed, const float* x_seed, const float* w,
-                                          const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                                          const float* Wz, const float* bz,
-                                          const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                                          const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                                          float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream) {
-  clv::GenArgs a = vrnn_args(N, S, nsteps, L, C, seed, clamp, Xs, xhat);
-  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
-  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
-  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
-  return vrnn_launch(a, Mode::generate, true, D, H, gate_act, stream);
-}
-
-extern "C" int clv_vrnn_generate_resume(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
-                                        uint64_t seed, const float* x_seed, const float* w,
-                                        const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                                        const float* Wz, const float* bz,
-                                        const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                                        const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                                        float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
-                                        float* state_out, float* Xs, float* xhat, void* stream) {
+                                 const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                                 int tempered, float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
+                                 float* state_out, float* Xs, float* xhat, void* stream) {
+  if (!tempered && (inv_temperature != 1.0f || z_temperature != 1.0f)) return CLV_EINVAL;
+  const bool state = state_in || state_out || t0 != 0;
   clv::GenArgs a = vrnn_args(N, S, nsteps, L, C, seed, clamp, Xs, xhat);
   set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
   set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
   a.z_prior = z_prior; a.x_seed = x_seed; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
   a.t0 = t0; a.state_in = state_in; a.state_out = state_out;
-  return vrnn_launch(a, Mode::resume, true, D, H, gate_act, stream);
-}
-
-extern "C" int clv_vrnn_vary_latents(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
-                                     const float* sources, const float* x0, const float* w_enc, const float* w_dec,
-                                     const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                                     const float* Wz, const float* bz,
-                                     const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                                     const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                                     float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout,
-                                     void* stream) {
-  clv::GenArgs a = vrnn_args(N, 0, T, L, C, seed, clamp, Xs, xhat);
-  set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
-  set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
-  a.x_seed = sources; a.x0 = x0; a.w = w_enc; a.w_dec = w_dec; a.hist_source = hist_source != 0;
-  a.inv_T = inv_temperature; a.Tz = z_temperature; a.zout = zout;
-  return vrnn_launch(a, Mode::vary, true, D, H, gate_act, stream);
+  return vrnn_launch(a, state ? Mode::resume : Mode::generate, state || tempered, D, H, gate_act, stream);
 }
 
 extern "C" int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
@@ -680,12 +625,13 @@ extern "C" int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_
                              const float* Wz, const float* bz,
                              const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                              const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                             float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream) {
+                             float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout,
+                             void* stream) {
   clv::GenArgs a = vrnn_args(N, 0, T, L, C, seed, clamp, Xs, xhat);
   set_encoder(a, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz);
   set_decoder(a, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo);
   a.x_seed = sources; a.x0 = x0; a.w = w_enc; a.w_dec = w_dec; a.hist_source = hist_source != 0;
-  a.inv_T = inv_temperature; a.Tz = z_temperature;
+  a.inv_T = inv_temperature; a.Tz = z_temperature; a.zout = zout;
   return vrnn_launch(a, Mode::vary, true, D, H, gate_act, stream);
 }
 

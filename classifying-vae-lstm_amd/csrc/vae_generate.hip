@@ -293,7 +293,7 @@ VaeKernel pick_vae_kernel(Mode mode, bool clamped, bool tempered, bool latents_o
   }
 }
 
-// The one launcher: every refusal of the seven entry points, the kernel pick and the launch.  `a` is the call as its entry
+// The one launcher: every refusal of the three entry points, the kernel pick and the launch.  `a` is the call as its entry
 // point filled it (vary and decode: nsteps = T; absent inputs null; absent temperatures 1.0f, which is exact).
 int vae_launch(const clv::VaeGenArgs& a, Mode mode, bool tempered, int D, int H, void* stream) {
   using namespace clv;
@@ -347,78 +347,34 @@ void set_encoder(clv::VaeGenArgs& a, const float* Kh, const float* bh, const flo
 void set_decoder(clv::VaeGenArgs& a, const float* Kd, const float* bd, const float* Ko, const float* bo) { a.Kd = Kd; a.bd = bd; a.Ko = Ko; a.bo = bo; }
 }  // namespace
 
+// One entry point per operation (include/clvae.h): a call from or to a state runs the ST instance, any other call the CL and TP
+// instances that its roll and its `tempered` flag name.
 extern "C" int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
                                 const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
                                 const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
-                                float* Xs, float* xhat, void* stream) {
-  clv::VaeGenArgs a = vae_args(N, nsteps, L, C, use_x_prev, seed, nullptr, Xs, xhat);
-  set_encoder(a, Kh, bh, Kz, bz);
-  set_decoder(a, Kd, bd, Ko, bo);
-  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w;
-  return vae_launch(a, Mode::generate, false, D, H, stream);
-}
-
-extern "C" int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
-                                        uint64_t seed, const float* x_seed, const float* w, const float* Kh, const float* bh,
-                                        const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
-                                        const float* bo, const uint8_t* clamp, float* Xs, float* xhat, void* stream) {
-  if (!clamp) return CLV_EINVAL;             // this entry point is the roll
-  clv::VaeGenArgs a = vae_args(N, nsteps, L, C, use_x_prev, seed, clamp, Xs, xhat);
-  set_encoder(a, Kh, bh, Kz, bz);
-  set_decoder(a, Kd, bd, Ko, bo);
-  a.z_prior = z_prior; a.x_seed = x_seed; a.w = w;
-  return vae_launch(a, Mode::generate, false, D, H, stream);
-}
-
-extern "C" int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
-                                         uint64_t seed, const float* x_seed, const float* w, const float* Kh, const float* bh,
-                                         const float* Kz, const float* bz, const float* Kd, const float* bd, const float* Ko,
-                                         const float* bo, const uint8_t* clamp, float inv_temperature, float z_temperature,
-                                         float* Xs, float* xhat, void* stream) {
+                                const uint8_t* clamp, int tempered, float inv_temperature, float z_temperature, uint32_t t0,
+                                const float* state_in, float* state_out, float* Xs, float* xhat, void* stream) {
+  if (!tempered && (inv_temperature != 1.0f || z_temperature != 1.0f)) return CLV_EINVAL;
+  const bool state = state_in || state_out || t0 != 0;
+  if (state && x_seed) return CLV_EINVAL;    // the state's two rows stand for the seed frame
   clv::VaeGenArgs a = vae_args(N, nsteps, L, C, use_x_prev, seed, clamp, Xs, xhat);
   set_encoder(a, Kh, bh, Kz, bz);
   set_decoder(a, Kd, bd, Ko, bo);
   a.z_prior = z_prior; a.x_seed = x_seed; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
-  return vae_launch(a, Mode::generate, true, D, H, stream);
-}
-
-extern "C" int clv_vae_generate_resume(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior,
-                                       uint64_t seed, const float* w, const float* Kh, const float* bh, const float* Kz,
-                                       const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
-                                       const uint8_t* clamp, float inv_temperature, float z_temperature, uint32_t t0,
-                                       const float* state_in, float* state_out, float* Xs, float* xhat, void* stream) {
-  clv::VaeGenArgs a = vae_args(N, nsteps, L, C, use_x_prev, seed, clamp, Xs, xhat);
-  set_encoder(a, Kh, bh, Kz, bz);
-  set_decoder(a, Kd, bd, Ko, bo);
-  a.z_prior = z_prior; a.w = w; a.inv_T = inv_temperature; a.Tz = z_temperature;
   a.t0 = t0; a.state_in = state_in; a.state_out = state_out;
-  return vae_launch(a, Mode::resume, true, D, H, stream);
-}
-
-extern "C" int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
-                                    const float* sources, const float* x0, const float* w_enc, const float* w_dec,
-                                    const float* Kh, const float* bh, const float* Kz, const float* bz, const float* Kd,
-                                    const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
-                                    float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout,
-                                    void* stream) {
-  clv::VaeGenArgs a = vae_args(N, T, L, C, use_x_prev, seed, clamp, Xs, xhat);
-  set_encoder(a, Kh, bh, Kz, bz);
-  set_decoder(a, Kd, bd, Ko, bo);
-  a.x_seed = sources; a.x0 = x0; a.w = w_enc; a.w_dec = w_dec; a.hist_source = hist_source != 0;
-  a.inv_T = inv_temperature; a.Tz = z_temperature; a.zout = zout;
-  return vae_launch(a, Mode::vary, true, D, H, stream);
+  return vae_launch(a, state ? Mode::resume : Mode::generate, state || tempered, D, H, stream);
 }
 
 extern "C" int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
                             const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
                             const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
                             const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
-                            float z_temperature, float* Xs, float* xhat, void* stream) {
+                            float z_temperature, float* Xs, float* xhat, float* zout, void* stream) {
   clv::VaeGenArgs a = vae_args(N, T, L, C, use_x_prev, seed, clamp, Xs, xhat);
   set_encoder(a, Kh, bh, Kz, bz);
   set_decoder(a, Kd, bd, Ko, bo);
   a.x_seed = sources; a.x0 = x0; a.w = w_enc; a.w_dec = w_dec; a.hist_source = hist_source != 0;
-  a.inv_T = inv_temperature; a.Tz = z_temperature;
+  a.inv_T = inv_temperature; a.Tz = z_temperature; a.zout = zout;
   return vae_launch(a, Mode::vary, true, D, H, stream);
 }
 

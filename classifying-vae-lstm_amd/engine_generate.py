@@ -1062,7 +1062,7 @@ class _Generate:
     _check_frames(**frames)     cl_vae reads frames as on / off: binary_frames; cl_vrnn takes any float: nothing
     _vary_fits(clamp, T, zout)  does a re-decoding fit the persistent kernel's 32-bit addressing
     _smc_seed(xs), _smc_cap()   how the filter's chain holds its seed rows xs; the most rows of a chunk (None: any)
-    _vary_op, _decode_op        ops.vae_* / ops.vrnn_*: vary_latents (without a zout it IS the family's vary) and decode
+    _vary_op, _decode_op        ops.vae_* / ops.vrnn_*: vary (with or without a zout) and decode
     _weights(encoder=True)      the weight arguments of those, in their order
     Every refusal (ValueError) comes before the first launch and before anything of the engine but cfg and device is read."""
 
@@ -1096,7 +1096,7 @@ class _Generate:
         Xs = torch.zeros(N, T, D, dtype=torch.float32, device=d)
         if persistent and not isinstance(clamp, Constraints) and self._vary_fits(clamp, T, zout) and self._persistent_ok():
             self._vary_op(N, T, D, cfg['H'], L, cfg['C'], self._family_flag(), hist_source, seed, sources, x0, w_enc, w_dec,
-                          *self._weights(), Xs, zout, xhat_out, clamp=clamp, temper=temper)
+                          *self._weights(), Xs, xhat_out, clamp=clamp, temper=temper, zout=zout)
             return Xs
         chain = _Chain(self.ROWS(self, N), w_enc, w_dec, T, seed, temper, 'enc_input' if hist_source else 'sample',
                        x_dec=None if x0 is None else x0.clone(), sources=sources, clamp=clamp)
@@ -1234,7 +1234,7 @@ class VaeGenerate(_Generate):
     STATE_KIND = 'cl_vae'
     ROWS = _VaeRows
     _check_frames = staticmethod(binary_frames)
-    _vary_op, _decode_op = staticmethod(ops.vae_vary_latents), staticmethod(ops.vae_decode)
+    _vary_op, _decode_op = staticmethod(ops.vae_vary), staticmethod(ops.vae_decode)
 
     def _persistent_ok(self):
         cfg = self.cfg
@@ -1278,8 +1278,8 @@ class VaeGenerate(_Generate):
         state, return_state: continue from a GenState (x_seed is then None: the state holds the last two
         frames) with the Philox steps counted on from state.t, and / or return (Xs, GenState after the last frame).  A
         piece generated in several such calls is bit for bit the piece of one call; the state is the same on both routes
-        and is not written.  Neither given (default): exactly the launches above -- the plain, clamped or tempered entry;
-        with either, the ST instance behind vae_generate_resume.
+        and is not written.  Neither given (default): exactly the launches above -- the plain, clamped or tempered instance;
+        with either, the ST instance (ops.vae_generate from / to a state).
         Frames are read as on / off: ValueError (binary_frames) for an x_seed, or a state not returned by a sampler, with
         an entry other than 0 and 1, on both routes and before anything is launched."""
         cfg, d = self.cfg, self.device
@@ -1310,11 +1310,10 @@ class VaeGenerate(_Generate):
             return self._generate_frames(x_in, hist, w, nsteps, seed, use_graph, z_prior, clamp, temper, t0, return_state)
         Xs = torch.zeros(N, nsteps, D, **f)
         head = (N, nsteps, D, cfg['H'], cfg['L'], cfg['C'], cfg['use_x_prev'], z_prior, seed)
-        if not resume:
-            ops.vae_generate(*head, x_in, w, *self._weights(), Xs, xhat_out, clamp=clamp, temper=temper)
-            return Xs
         out = torch.empty(N, 2, D, **f) if return_state else None
-        ops.vae_generate_resume(*head, w, *self._weights(), Xs, t0, state.rows, out, xhat=xhat_out, clamp=clamp, temper=temper)
+        from_state = dict(t0=t0, state_in=state.rows, state_out=out) if resume else {}     # the state stands for the seed frame
+        ops.vae_generate(*head, None if resume else x_in, w, *self._weights(), Xs, xhat_out, clamp=clamp, temper=temper,
+                         **from_state)
         return (Xs, GenState('cl_vae', None, t0 + nsteps, rows=out)._sampled()) if return_state else Xs
 
     def _generate_frames(self, x_in, hist, w, nsteps, seed, use_graph, z_prior, clamp, temper, t0=0, return_state=False):
@@ -1334,7 +1333,7 @@ class VrnnGenerate(_Generate):
     STATE_KIND = 'cl_vrnn'
     ROWS = _VrnnRows
     _check_frames = staticmethod(lambda **frames: None)
-    _vary_op, _decode_op = staticmethod(ops.vrnn_vary_latents), staticmethod(ops.vrnn_decode)
+    _vary_op, _decode_op = staticmethod(ops.vrnn_vary), staticmethod(ops.vrnn_decode)
 
     def _persistent_ok(self):
         cfg = self.cfg
@@ -1435,8 +1434,8 @@ class VrnnGenerate(_Generate):
         may be None or [N,0,D] (the free run goes on from the state's x) or hold more teacher-forced frames.  nsteps = 0
         with seed frames primes a state: its x is then the bridge sample.  A piece generated in several such calls is bit
         for bit the piece of one call; the state is the same on both routes and is not written.  Neither given (default):
-        exactly the launches above -- the plain, clamped or tempered entry; with either, the ST instances behind
-        vrnn_generate_resume (they need D = H: one row width)."""
+        exactly the launches above -- the plain, clamped or tempered instance; with either, the ST instances
+        (ops.vrnn_generate from / to a state; they need D = H: one row width)."""
         cfg = self.cfg
         temper = temper_args(temperature, z_temperature)
         resume = state is not None or return_state
@@ -1462,12 +1461,9 @@ class VrnnGenerate(_Generate):
         Xs = torch.zeros(N, nsteps, cfg['D'], dtype=torch.float32, device=self.device)
         head = (N, S, nsteps, cfg['D'], cfg['H'], cfg['L'], cfg['C'], self.gate_act, z_prior, seed, x_seed if S else None, w,
                 *self._weights())
-        if not resume:
-            ops.vrnn_generate(*head, Xs, xhat_out, clamp=clamp, temper=temper)
-            return Xs
         out = torch.empty(N, 5, cfg['D'], dtype=torch.float32, device=self.device) if return_state else None
-        ops.vrnn_generate_resume(*head, Xs if nsteps else None, t0, None if state is None else state.rows, out, xhat=xhat_out,
-                                 clamp=clamp, temper=temper)
+        from_state = dict(t0=t0, state_in=None if state is None else state.rows, state_out=out) if resume else {}
+        ops.vrnn_generate(*head, Xs if nsteps else None, xhat_out, clamp=clamp, temper=temper, **from_state)
         return (Xs, GenState('cl_vrnn', None, t0 + S + nsteps, rows=out)) if return_state else Xs
 
     def _generate_frames(self, x_seed, w, nsteps, seed=0, use_graph=True, z_prior=False, clamp=None, temper=None, t0=0,

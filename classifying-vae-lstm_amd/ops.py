@@ -384,22 +384,10 @@ def _sample(name, *args):
     check(getattr(_lib.lib(), name)(*args, _stream()), name)
 
 
-def _generate(name, head, clamp, temper, Xs, xhat):
-    """name (no roll), name_clamped (a roll) or name_tempered (the two factors, with or without a roll): the symbol decides
-    the kernel instance"""
-    if temper is not None:
-        _sample(name + "_tempered", *head, _ptr(clamp), float(temper[0]), float(temper[1]), *_ptrs(Xs, xhat))
-    elif clamp is None:
-        _sample(name, *head, *_ptrs(Xs, xhat))
-    else:
-        _sample(name + "_clamped", *head, *_ptrs(clamp, Xs, xhat))
-
-
-def _vary(name, head, clamp, temper, Xs, xhat, zout):
-    """name, or name_latents with a zout: the roll, the two factors and the outputs behind a family's own head"""
+def _temper(temper):
+    """the flag and the two factors of a sampling entry point: None is the untempered call (0, 1.0, 1.0)"""
     inv_T, Tz = (1.0, 1.0) if temper is None else temper
-    outs = _ptrs(Xs, xhat) if zout is None else _ptrs(Xs, xhat, zout)
-    _sample(name if zout is None else name + "_latents", *head, _ptr(clamp), float(inv_T), float(Tz), *outs)
+    return [int(temper is not None), float(inv_T), float(Tz)]
 
 
 def vrnn_generate_supported(D, H, L, Cn):
@@ -407,13 +395,16 @@ def vrnn_generate_supported(D, H, L, Cn):
 
 
 def vrnn_generate(N, S, nsteps, D, H, L, Cn, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
-                  Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None, temper=None):
-    """cl_vrnn frame loop for N sequences in one persistent launch (csrc/generate.hip); clamp: uint8 [N,nsteps,D]
-    constraint roll (clv_vrnn_generate_clamped) or None; temper: None or (inv_temperature, z_temperature), the tempered
-    model's two factors (clv_vrnn_generate_tempered, with or without a roll)."""
-    _generate("clv_vrnn_generate", [N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed),
-                                    *_ptrs(x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo)],
-              clamp, temper, Xs, xhat)
+                  Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None, temper=None, t0=0, state_in=None,
+                  state_out=None):
+    """cl_vrnn frame loop for N sequences in one persistent launch (clv_vrnn_generate, csrc/generate.hip); clamp: uint8
+    [N,nsteps,D] constraint roll or None; temper: None or (inv_temperature, z_temperature), the tempered model's two factors.
+    From and to a state once t0, state_in or state_out is given: t0 the Philox step of the call's frame 0,
+    state_in / state_out [N,5,88] (h_enc, c_enc, h_dec, c_dec, x; either may be None, they may be one tensor); then x_seed
+    may be None with S = 0 and Xs None with nsteps = 0."""
+    _sample("clv_vrnn_generate", N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed),
+            *_ptrs(x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp),
+            *_temper(temper), int(t0), *_ptrs(state_in, state_out, Xs, xhat))
 
 
 def vae_generate_supported(D, H, L, Cn):
@@ -421,64 +412,30 @@ def vae_generate_supported(D, H, L, Cn):
 
 
 def vae_generate(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs, xhat=None,
-                 clamp=None, temper=None):
-    """cl_vae frame loop for N sequences in one persistent launch (csrc/vae_generate.hip); clamp: uint8 [N,nsteps,D]
-    constraint roll (clv_vae_generate_clamped) or None; temper: None or (inv_temperature, z_temperature)
-    (clv_vae_generate_tempered, with or without a roll)."""
-    _generate("clv_vae_generate", [N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed),
-                                   *_ptrs(x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo)], clamp, temper, Xs, xhat)
-
-
-def vrnn_generate_resume(N, S, nsteps, D, H, L, Cn, gate_act, z_prior, seed, x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
-                         Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, t0, state_in, state_out, xhat=None, clamp=None,
-                         temper=None):
-    """vrnn_generate from and to a state (clv_vrnn_generate_resume): t0 the Philox step of the call's frame 0,
-    state_in / state_out [N,5,88] (h_enc, c_enc, h_dec, c_dec, x; either may be None, they may be one tensor); x_seed None
-    with S = 0, Xs None with nsteps = 0; clamp, temper as vrnn_generate's (None: no roll, both factors 1)"""
-    inv_T, Tz = (1.0, 1.0) if temper is None else temper
-    _sample("clv_vrnn_generate_resume", N, S, nsteps, D, H, L, Cn, gate_act, int(bool(z_prior)), int(seed),
-            *_ptrs(x_seed, w, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp),
-            float(inv_T), float(Tz), int(t0), *_ptrs(state_in, state_out, Xs, xhat))
-
-
-def vae_generate_resume(N, nsteps, D, H, L, Cn, use_x_prev, z_prior, seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs, t0, state_in,
-                        state_out, xhat=None, clamp=None, temper=None):
-    """vae_generate from and to a state (clv_vae_generate_resume): state_in [N,2,88] (x_in, hist) stands for the
-    seed frame, state_out may be None or state_in; the rest as vrnn_generate_resume"""
-    inv_T, Tz = (1.0, 1.0) if temper is None else temper
-    _sample("clv_vae_generate_resume", N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed),
-            *_ptrs(w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, clamp), float(inv_T), float(Tz), int(t0),
+                 clamp=None, temper=None, t0=0, state_in=None, state_out=None):
+    """cl_vae frame loop for N sequences in one persistent launch (clv_vae_generate, csrc/vae_generate.hip); clamp, temper,
+    t0 as vrnn_generate's.  From and to a state: state_in [N,2,88] (x_in, hist) stands for the seed frame, so x_seed is
+    None; state_out may be None or state_in."""
+    _sample("clv_vae_generate", N, nsteps, D, H, L, Cn, int(bool(use_x_prev)), int(bool(z_prior)), int(seed),
+            *_ptrs(x_seed, w, Kh, bh, Kz, bz, Kd, bd, Ko, bo, clamp), *_temper(temper), int(t0),
             *_ptrs(state_in, state_out, Xs, xhat))
 
 
 def vrnn_vary(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz,
-              Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None, temper=None):
+              Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, xhat=None, clamp=None, temper=None, zout=None):
     """cl_vrnn re-decoding of sources [N,T,D] in one persistent launch (clv_vrnn_vary); x0, clamp, xhat may be
-    None; temper: None or (inv_temperature, z_temperature)."""
-    vrnn_vary_latents(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz,
-                      bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, None, xhat=xhat, clamp=clamp, temper=temper)
+    None; temper: None or (inv_temperature, z_temperature); zout [3,N,T,L] = (z_mean, z_log_var, z) also stores the latents
+    (DESIGN.md 15)."""
+    _sample("clv_vrnn_vary", N, T, D, H, L, Cn, gate_act, int(bool(hist_source)), int(seed),
+            *_ptrs(sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, clamp),
+            *_temper(temper)[1:], *_ptrs(Xs, xhat, zout))
 
 
 def vae_vary(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo, Xs,
-             xhat=None, clamp=None, temper=None):
+             xhat=None, clamp=None, temper=None, zout=None):
     """cl_vae re-decoding of sources [N,T,D] in one persistent launch (clv_vae_vary); arguments as vrnn_vary"""
-    vae_vary_latents(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
-                     Xs, None, xhat=xhat, clamp=clamp, temper=temper)
-
-
-def vrnn_vary_latents(N, T, D, H, L, Cn, gate_act, hist_source, seed, sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc,
-                      Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo, bo, Xs, zout, xhat=None, clamp=None, temper=None):
-    """vrnn_vary that also stores the latents: zout [3,N,T,L] = (z_mean, z_log_var, z) (clv_vrnn_vary_latents)"""
-    _vary("clv_vrnn_vary", [N, T, D, H, L, Cn, gate_act, int(bool(hist_source)), int(seed),
-                            *_ptrs(sources, x0, w_enc, w_dec, Kx_enc, Kw_enc, b_enc, U_enc, Wz, bz, Kx_dec, Kz, Kw_dec, b_dec, U_dec,
-                                   Wo, bo)], clamp, temper, Xs, xhat, zout)
-
-
-def vae_vary_latents(N, T, D, H, L, Cn, use_x_prev, hist_source, seed, sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo,
-                     Xs, zout, xhat=None, clamp=None, temper=None):
-    """vae_vary that also stores the latents: zout [3,N,T,L] (clv_vae_vary_latents)"""
-    _vary("clv_vae_vary", [N, T, D, H, L, Cn, int(bool(use_x_prev)), int(bool(hist_source)), int(seed),
-                           *_ptrs(sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo)], clamp, temper, Xs, xhat, zout)
+    _sample("clv_vae_vary", N, T, D, H, L, Cn, int(bool(use_x_prev)), int(bool(hist_source)), int(seed),
+            *_ptrs(sources, x0, w_enc, w_dec, Kh, bh, Kz, bz, Kd, bd, Ko, bo, clamp), *_temper(temper)[1:], *_ptrs(Xs, xhat, zout))
 
 
 def vrnn_decode(N, T, D, H, L, Cn, gate_act, seed, z_in, x0, history, w_dec, noise_rows, Kx_dec, Kz, Kw_dec, b_dec, U_dec, Wo,

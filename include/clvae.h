@@ -140,8 +140,10 @@ typedef struct clv_frame_proj {
  *        gather); clv_latent_head_fwd draws its own eps (noise); removed: the 4x4x1 f32-MFMA sequence forward
  *        (lstm_seq_fwd_z) and the in-kernel input gather of the single-LSTM forward (lstm_seq_fwd_x), which no shipped path
  *        launched
- *        (still 600: + clv_splitk_reduce_multi_outer / _supported, an addition; no existing entry point changed) */
-#define CLV_ABI_VERSION 600
+ *        (still 600: + clv_splitk_reduce_multi_outer / _supported, an addition; no existing entry point changed)
+ *   610  sampling follows the 600 rule: _clamped / _tempered / _resume took over clv_*_generate, _vary_latents took over
+ *        clv_*_vary */
+#define CLV_ABI_VERSION 610
 int clv_version(void);
 /* number of visible HIP devices whose arch is gfx950 (0 => the product must fail loudly) */
 int clv_device_count(void);
@@ -443,29 +445,39 @@ int clv_lstm_pair_bwd(int B, int T, int H, int L, int gate_act, float kl_scale,
  * clv_philox_uniform value for (seed, step t, stream 1, index n*D+j).  Kernel pieces are the row blocks of the
  * Keras tensors: encoder_h/kernel = [Kx_enc (D rows) ; Kw_enc (C rows)], decoder_h/kernel = [Kx_dec (D rows,
  * NULL without use_x_prev) ; Kz (L rows) ; Kw_dec (C rows)], Wz = [Z_mean | Z_log_var] kernel [H,2L].
- * clv_vrnn_generate_supported: D == H == 88, L <= 32, C <= 32. */
+ * clv_vrnn_generate_supported: D == H == 88, L <= 32, C <= 32.
+ * THE ROLL (clamped ancestral sampling): clamp [N,nsteps,D] uint8 or NULL (no constraint), one row per returned
+ * frame; byte 0 forces the note off, 1 forces it on, any other byte (Python: FREE = 255) leaves it free.  The draw is made
+ * as above (u is drawn for a clamped note too and discarded), then the constraint replaces it; the clamped frame is
+ * stored to Xs and fed back as the next input.  xhat keeps the model's own probabilities.  BRIDGE RULE: with S > 0 the
+ * sample drawn at step S-1 feeds step S but is not returned; it stays unconstrained, and row j applies to the sample drawn
+ * at step S+j, Xs[n,j].  An all-free roll gives bit for bit the frames of a NULL one.  With a roll nsteps >= 1 and
+ * N*nsteps*D < 2^32.
+ * THE TWO FACTORS (the tempered model): inv_temperature = float32(1 / T), T > 0, multiplies a note's logit
+ * (product plus bias, rounded once) before the same sigmoid; z_temperature = Tz >= 0 multiplies the latent noise,
+ * z = mean + exp(log_var/2) * fl(Tz * eps) (Tz = 0: z = mean, or 0 under z_prior).  The Philox keys, streams, steps and
+ * indices stay (runs that differ only in T share their uniforms), and so does the bridge rule; xhat receives the TEMPERED
+ * probabilities.  Both factors at 1.0f give bit for bit the untempered frames.  tempered == 0 is the untempered call and
+ * requires both factors == 1.0f; tempered != 0 runs the tempered kernels, at any factors (1.0f included).  CLV_EINVAL for an
+ * inv_temperature that is zero, negative or not finite and a z_temperature that is negative or not finite.
+ * FROM AND TO A STATE (resumable generation): a call with state_in != NULL, state_out != NULL or t0 != 0.  The
+ * Philox steps are offset by t0: local frame t of the call draws step t0 + t, so a piece generated in several calls, each
+ * starting at the t the one before ended at, is bit for bit the piece of one call.  Seed frames, Xs, xhat and the roll stay
+ * indexed by the call's own frames.  The roll and the two factors hold as above (tempered or not: the same kernels).
+ * cl_vrnn: state_in / state_out [N,5,88] float32, rows h_enc, c_enc, h_dec, c_dec after the last frame's cells and x, the
+ * input of the next step (the last clamped sample; the bridge sample of step S-1 when nsteps = 0).  state_in NULL: the zero
+ * start of a call without a state (x then matters only for S = 0: the zero frame).  With S = 0 the first input is row x,
+ * with S > 0 the seed frames are teacher-forced from the given LSTM states.  nsteps = 0 (priming on the seed) is allowed.
+ * state_out NULL: not stored; it may alias state_in.  CLV_EINVAL also for t0 + S + nsteps > UINT32_MAX. */
 int clv_vrnn_generate_supported(int D, int H, int L, int C);
 int clv_vrnn_generate(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
                       uint64_t seed, const float* x_seed, const float* w,
                       const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
                       const float* Wz, const float* bz,
                       const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                      const float* U_dec, const float* Wo, const float* bo,
-                      float* Xs, float* xhat, void* stream);
-/* ... under a CONSTRAINT ROLL (clamped ancestral sampling): clamp [N,nsteps,D] uint8, one row per returned
- * frame; byte 0 forces the note off, 1 forces it on, any other byte (Python: FREE = 255) leaves it free.  The draw is made
- * as above (u is drawn for a clamped note too and discarded), then the constraint replaces it; the clamped frame is
- * stored to Xs and fed back as the next input.  xhat keeps the model's own probabilities.  BRIDGE RULE: with S > 0 the
- * sample drawn at step S-1 feeds step S but is not returned; it stays unconstrained, and row j applies to the sample drawn
- * at step S+j, Xs[n,j].  An all-free roll gives bit for bit the frames of clv_vrnn_generate.  nsteps >= 1, clamp != NULL,
- * N*nsteps*D < 2^32. */
-int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
-                              uint64_t seed, const float* x_seed, const float* w,
-                              const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                              const float* Wz, const float* bz,
-                              const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                              const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                              float* Xs, float* xhat, void* stream);
+                      const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
+                      int tempered, float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
+                      float* state_out, float* Xs, float* xhat, void* stream);
 
 /* ------------------------------------------------- cl_vae generation, persistent --
  * cl_vae/model.py:9-42 (generate_sample's frame loop) for N independent sequences, one workgroup per sequence for its
@@ -477,7 +489,14 @@ int clv_vrnn_generate_clamped(int N, int S, int nsteps, int D, int H, int L, int
  * Kh = h/kernel [D+C,H] (frame rows, label rows), Kz = the fused head [H,2L], Kd = decoder_h/kernel [C+(D)+L,H]
  * (label rows, history rows, latent rows), Ko = x_decoded_mean/kernel [H,D].  Xs [N,nsteps,D]; xhat (optional) the
  * probabilities.  clv_vae_generate_supported: D == H == 88, L <= 32, C <= 32 (models with hidden layers).
- * FRAMES ARE READ AS ON / OFF by all seven clv_vae_* entry points below: a frame that comes in (x_seed, sources, x0, history,
+ * The roll, the two factors and `tempered` are clv_vrnn_generate's; there is no seed run, so row t of clamp [N,nsteps,D]
+ * constrains frame t, which is then the next input (and the decoder's history one frame later), and this family sets no
+ * bound on the roll.
+ * From and to a state (as clv_vrnn_generate: state_in != NULL, state_out != NULL or t0 != 0): state_in / state_out [N,2,88],
+ * rows x_in (the last frame) and hist (the frame before it); a fresh start is both rows = the seed frame, t0 = 0.  The state
+ * stands for the seed frame: state_in is required and x_seed must be NULL.  state_out NULL: not stored; it may alias
+ * state_in.  CLV_EINVAL also for t0 + nsteps > UINT32_MAX.
+ * FRAMES ARE READ AS ON / OFF by all three clv_vae_* entry points below: a frame that comes in (x_seed, sources, x0, history,
  * both rows of state_in) contributes the kernel row of every note whose entry is not 0, unweighted; an entry other than 0 or
  * 1 is the caller's error (the host cannot see device memory: the Python layer refuses such frames, engine_generate.
  * binary_frames, so that this kernel and the per-frame chain, which multiplies by the value, stay the same sampler).  The
@@ -486,36 +505,8 @@ int clv_vae_generate_supported(int D, int H, int L, int C);
 int clv_vae_generate(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
                      const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
                      const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
-                     float* Xs, float* xhat, void* stream);
-/* ... under a constraint roll clamp [N,nsteps,D] uint8 (encoding as clv_vrnn_generate_clamped): row t constrains frame t,
- * which is then the next input (and the decoder's history one frame later).  xhat keeps the model's own probabilities; an
- * all-free roll gives bit for bit the frames of clv_vae_generate.  clamp != NULL.  Frames are read as on / off. */
-int clv_vae_generate_clamped(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
-                             const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
-                             const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
-                             const uint8_t* clamp, float* Xs, float* xhat, void* stream);
-
-/* ----------------------------------------------- generation at a temperature --
- * The TEMPERED MODEL: inv_temperature = float32(1 / T), T > 0, multiplies a note's logit (product plus bias,
- * rounded once) before the same sigmoid; z_temperature = Tz >= 0 multiplies the latent noise, z = mean + exp(log_var/2) *
- * fl(Tz * eps) (Tz = 0: z = mean, or 0 under z_prior).  Everything else is clv_vrnn_generate / clv_vae_generate and their
- * _clamped forms: the same Philox keys, streams, steps and indices (runs that differ only in T share their uniforms), the
- * same bridge rule; xhat receives the TEMPERED probabilities.  clamp may be NULL (no constraint).  Both factors at 1.0f
- * give bit for bit the frames of the untempered entry points.  CLV_EINVAL for an inv_temperature that is zero, negative or
- * not finite and a z_temperature that is negative or not finite. */
-int clv_vrnn_generate_tempered(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
-                               uint64_t seed, const float* x_seed, const float* w,
-                               const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                               const float* Wz, const float* bz,
-                               const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                               const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                               float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream);
-/* cl_vae: frames are read as on / off (x_seed; see clv_vae_generate). */
-int clv_vae_generate_tempered(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
-                              const float* x_seed, const float* w, const float* Kh, const float* bh, const float* Kz,
-                              const float* bz, const float* Kd, const float* bd, const float* Ko, const float* bo,
-                              const uint8_t* clamp, float inv_temperature, float z_temperature, float* Xs, float* xhat,
-                              void* stream);
+                     const uint8_t* clamp, int tempered, float inv_temperature, float z_temperature, uint32_t t0,
+                     const float* state_in, float* state_out, float* Xs, float* xhat, void* stream);
 /* The same two factors for the per-frame chains, in place and with one rounding of the product, as the kernels above form
  * them: a[i] = sigmoid(fl(a[i] * inv_temperature)) on the output head's pre-activations (the head GEMM then runs with
  * CLV_ACT_NONE), eps[i] = fl(z_temperature * eps[i]) on the latent noise between clv_philox_normal and clv_gauss_fwd. */
@@ -532,43 +523,29 @@ int clv_scale_temper(int64_t n, float* eps, float z_temperature, void* stream);
  * / use_x_prev = 0) hist_source has no effect.  Philox keys, streams, steps and indices are those of clv_vrnn_generate /
  * clv_vae_generate with S = 0.  Xs [N,T,D]; xhat [N,T,D] (optional) the unclamped probabilities.  Shapes: those of
  * clv_vrnn_generate_supported / clv_vae_generate_supported; N, T >= 1; with a roll N*T*D < 2^32 (cl_vrnn).  CLV_EINVAL for the
- * temperatures clv_vrnn_generate_tempered refuses. */
+ * temperatures clv_vrnn_generate refuses.
+ * zout [3,N,T,L] (NULL: no latents are stored) receives every frame's (z_mean | z_log_var | z), z the float32
+ * value the decoder was fed: fma(exp(z_log_var/2), fl(z_temperature * eps), z_mean).  Xs, xhat and every draw are the same
+ * with and without it.  With a zout, CLV_EINVAL for N*T*L >= 2^32.
+ * cl_vae: frames are read as on / off (sources and x0; see clv_vae_generate). */
 int clv_vrnn_vary(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
                   const float* sources, const float* x0, const float* w_enc, const float* w_dec,
                   const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
                   const float* Wz, const float* bz,
                   const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                   const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                  float inv_temperature, float z_temperature, float* Xs, float* xhat, void* stream);
-/* cl_vae: frames are read as on / off (sources and x0; see clv_vae_generate). */
+                  float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout, void* stream);
 int clv_vae_vary(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
                  const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
                  const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
                  const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
-                 float z_temperature, float* Xs, float* xhat, void* stream);
+                 float z_temperature, float* Xs, float* xhat, float* zout, void* stream);
 /* The per-frame chains' read of the source: out[r,:] = src[r, *step_dev, :] for src [n/D, T, D] (n = rows * D elements), the
  * step read from the device counter of the captured frame; a step outside [0, T) leaves out untouched. */
 int clv_take_frame(int64_t n, int T, int D, const float* src, const int32_t* step_dev, float* out, void* stream);
 
 /* ------------------------------------- latent paths in and out (encode, decode, morph) --
- * DESIGN.md 15.  clv_*_vary_latents: clv_*_vary, which additionally stores every frame's latents to zout [3,N,T,L] =
- * (z_mean | z_log_var | z), z the float32 value the decoder was fed: fma(exp(z_log_var/2), fl(z_temperature * eps), z_mean).
- * Xs, xhat and every draw are those of clv_*_vary.  zout NULL: exactly clv_*_vary.  CLV_EINVAL for what clv_*_vary refuses
- * and, with a zout, for N*T*L >= 2^32. */
-int clv_vrnn_vary_latents(int N, int T, int D, int H, int L, int C, int gate_act, int hist_source, uint64_t seed,
-                          const float* sources, const float* x0, const float* w_enc, const float* w_dec,
-                          const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                          const float* Wz, const float* bz,
-                          const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                          const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                          float inv_temperature, float z_temperature, float* Xs, float* xhat, float* zout, void* stream);
-/* cl_vae: frames are read as on / off (sources and x0; see clv_vae_generate). */
-int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, int use_x_prev, int hist_source, uint64_t seed,
-                         const float* sources, const float* x0, const float* w_enc, const float* w_dec, const float* Kh,
-                         const float* bh, const float* Kz, const float* bz, const float* Kd, const float* bd,
-                         const float* Ko, const float* bo, const uint8_t* clamp, float inv_temperature,
-                         float z_temperature, float* Xs, float* xhat, float* zout, void* stream);
-/* Decoding a GIVEN latent path z_in [N,T,L]: the loop of clv_*_vary without its encoder.  Per frame t, from zero LSTM state:
+ * DESIGN.md 15.  Latents OUT: clv_*_vary with a zout.  Latents IN, z_in [N,T,L]: the loop of clv_*_vary without its encoder.  Per frame t, from zero LSTM state:
  * the decoder step on [xp, z_in[:, t], w_dec] with xp = x0 [N,D] (NULL: zeros) at t = 0, then the sample of frame t-1
  * (history NULL) or history[:, t-1] (history [N,T,D]: teacher forcing), x_hat = sigmoid(fl(logit * inv_temperature)),
  * x = [u <= x_hat] with u = Philox(seed, step t, stream 1, index noise_rows[n]*D + note), then the roll clamp [N,T,D] (NULL:
@@ -576,45 +553,17 @@ int clv_vae_vary_latents(int N, int T, int D, int H, int L, int C, int use_x_pre
  * equal entries share their uniforms.  Every entry must be >= 0: the caller's contract (the host cannot see device memory;
  * the Python layer validates it).  Xs [N,T,D]; xhat [N,T,D] (optional) the unclamped probabilities.  Shapes as
  * clv_vrnn_generate_supported / clv_vae_generate_supported.  CLV_EINVAL, before any launch, for a NULL z_in, w_dec or Xs,
- * N or T < 1, N*T*L or N*T*D >= 2^32, and an inv_temperature that is zero, negative or not finite. */
+ * N or T < 1, N*T*L or N*T*D >= 2^32, and an inv_temperature that is zero, negative or not finite.
+ * cl_vae: frames are read as on / off (x0 and history; see clv_vae_generate). */
 int clv_vrnn_decode(int N, int T, int D, int H, int L, int C, int gate_act, uint64_t seed, const float* z_in,
                     const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
                     const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
                     const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
                     float inv_temperature, float* Xs, float* xhat, void* stream);
-/* cl_vae: frames are read as on / off (x0 and history; see clv_vae_generate). */
 int clv_vae_decode(int N, int T, int D, int H, int L, int C, int use_x_prev, uint64_t seed, const float* z_in,
                    const float* x0, const float* history, const float* w_dec, const int32_t* noise_rows,
                    const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
                    float inv_temperature, float* Xs, float* xhat, void* stream);
-
-/* ------------------------------------------------ resumable generation (chunks, modulation, branching) --
- * DESIGN.md 16.  clv_*_generate_tempered (roll nullable, both factors 1.0f exact) FROM and TO a state, with the Philox steps
- * offset by t0: local frame t of the call draws step t0 + t, so a piece generated in several calls, each starting at the t
- * the one before ended at, is bit for bit the piece of one call.  Seed frames, Xs, xhat and the roll stay indexed by the
- * call's own frames.
- * cl_vrnn: state_in / state_out [N,5,88] float32, rows h_enc, c_enc, h_dec, c_dec after the last frame's cells and x, the
- * input of the next step (the last clamped sample; the bridge sample of step S-1 when nsteps = 0).  state_in NULL: the zero
- * start of clv_vrnn_generate (x then matters only for S = 0: the zero frame).  With S = 0 the first input is row x, with
- * S > 0 the seed frames are teacher-forced from the given LSTM states.  nsteps = 0 (priming on the seed) is allowed.
- * cl_vae: state_in / state_out [N,2,88], rows x_in (the last frame) and hist (the frame before it); a fresh start is both
- * rows = the seed frame, t0 = 0.  state_in is required (there is no seed argument).
- * state_out NULL: not stored; it may alias state_in.  CLV_EINVAL for everything clv_*_generate_tempered refuses and for
- * t0 + S + nsteps > UINT32_MAX (cl_vae: t0 + nsteps). */
-int clv_vrnn_generate_resume(int N, int S, int nsteps, int D, int H, int L, int C, int gate_act, int z_prior,
-                             uint64_t seed, const float* x_seed, const float* w,
-                             const float* Kx_enc, const float* Kw_enc, const float* b_enc, const float* U_enc,
-                             const float* Wz, const float* bz,
-                             const float* Kx_dec, const float* Kz, const float* Kw_dec, const float* b_dec,
-                             const float* U_dec, const float* Wo, const float* bo, const uint8_t* clamp,
-                             float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
-                             float* state_out, float* Xs, float* xhat, void* stream);
-/* cl_vae: frames are read as on / off (both rows of state_in; see clv_vae_generate). */
-int clv_vae_generate_resume(int N, int nsteps, int D, int H, int L, int C, int use_x_prev, int z_prior, uint64_t seed,
-                            const float* w, const float* Kh, const float* bh, const float* Kz, const float* bz,
-                            const float* Kd, const float* bd, const float* Ko, const float* bo, const uint8_t* clamp,
-                            float inv_temperature, float z_temperature, uint32_t t0, const float* state_in,
-                            float* state_out, float* Xs, float* xhat, void* stream);
 
 /* Row-wise linear interpolation, one thread per element: out[r,:] = fmaf(alpha[r], b[ib[r],:], fmaf(-alpha[r], a[ia[r],:],
  * a[ia[r],:])) for R rows of n floats; exact at alpha = 0 (a's row) and alpha = 1 (b's row).  ia, ib [R] int32 row indices
@@ -1017,7 +966,7 @@ int clv_philox_normal2(float* out0, int64_t n0, uint32_t stream_id0, uint64_t fi
 int clv_i32_add(int32_t* counter, int32_t v, void* stream);
 /* x[i] = (u[i] <= p[i]) ? 1 : 0   -- sample_x */
 int clv_bernoulli_sample(int64_t n, const float* p, const float* u, float* x, void* stream);
-/* ... under a constraint roll clamp [n/D, nsteps, D] uint8 (encoding as clv_vrnn_generate_clamped), for the per-frame
+/* ... under a constraint roll clamp [n/D, nsteps, D] uint8 (encoding as clv_vrnn_generate's), for the per-frame
  * chains replayed from one captured graph: with c = *step_dev (the device step counter of the frame's Philox draws), c >= S
  * applies row c - S of every sequence, c < S (teacher-forced steps and the bridge) and c >= S + nsteps apply none. */
 int clv_bernoulli_sample_clamped(int64_t n, int D, int nsteps, int S, const float* p, const float* u, const uint8_t* clamp,

@@ -43,7 +43,7 @@ def test_header_signatures_and_ops_agree():
     assert _lib.SIGNATURES['clv_smc_resample_conditional'] == _lib.SIGNATURES['clv_smc_resample']
     assert list(inspect.signature(ops.smc_resample_conditional).parameters) == \
         list(inspect.signature(ops.smc_resample).parameters)
-    assert _lib.ABI_VERSION == 600 and _lib.lib().clv_version() == 600
+    assert _lib.ABI_VERSION == 610 and _lib.lib().clv_version() == 610
 
 
 def _changed(args, **at):

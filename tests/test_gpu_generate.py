@@ -18,9 +18,9 @@ kernel-trace pass over this file:
   vrnn<hs,wide,TAIL>     ... [cl_vrnn-MODE-1] (L = 17)
   vrnn<s,narrow,TAIL>    ... [cl_vrnn-MODE-2] (L = 2)
   vrnn<s,wide,TAIL>      ... [cl_vrnn-MODE-3] (L = 32), [cl_vrnn-MODE-5] (L = 17)
-      MODE -> TAIL:  plain -> none (clv_vrnn_generate), CL -> CL (_clamped), TP -> TP (_tempered, no roll), CL+TP -> CL,TP
-      (_tempered with a roll), vary -> CL,TP,VR (clv_vrnn_vary), vary_latents -> CL,TP,VR,ZO, decode -> CL,TP,VR,ZG
-      (clv_vrnn_decode), resume -> CL,TP,ST (clv_vrnn_generate_resume; the wide ones are the RBL variant)
+      MODE -> TAIL:  plain -> none (clv_vrnn_generate), CL -> CL (a roll), TP -> TP (tempered, no roll), CL+TP -> CL,TP
+      (tempered with a roll), vary -> CL,TP,VR (clv_vrnn_vary), vary_latents -> CL,TP,VR,ZO (with a zout), decode -> CL,TP,VR,ZG
+      (clv_vrnn_decode), resume -> CL,TP,ST (clv_vrnn_generate from / to a state; the wide ones are the RBL variant)
   vae<TAIL>              ... [cl_vae-MODE-0 .. 5], the same eight modes through the clv_vae_* entry points
   N = 260 (more workgroups than CUs)  ... [cl_vrnn-vary_latents-1-big], [cl_vrnn-resume-3-big], [cl_vae-...-big]
 """
@@ -85,7 +85,8 @@ def weights(c, p, dev):
 
 def launch(c, p, dev, xhat=True, state_out='second'):
     """one launch of the case's entry point on NaN-filled outputs with canaries behind them -> the outputs as float32 arrays.
-    state_out: None, 'second' (a buffer of its own) or 'alias' (state_in itself)."""
+    state_out: None, 'second' (a buffer of its own) or 'alias' (state_in itself).  (A resume case with t0 = 0 and no state
+    either way is a call without a state: state_out=None then launches the case's CL / TP instance.)"""
     from clvae_amd import ops
     vrnn, mode = c['which'] == 'cl_vrnn', c['mode']
     N, S, ns, L, C = c['N'], c['S'], c['nsteps'], c['L'], c['C']
@@ -99,30 +100,24 @@ def launch(c, p, dev, xhat=True, state_out='second'):
     w = T(c['w'], dev)
     gate = (0 if c['gate'] == 'hard_sigmoid' else 1,) if vrnn else (c['use_x_prev'],)
     got, zout, st_out = {}, None, None
-    if mode in GR.GENERATE_MODES:
+    if mode in GR.GENERATE_MODES or mode == 'resume':
+        state = {}
+        if mode == 'resume':
+            st_in = bufs.inp(c['state_in']) if c.get('state_in') is not None else None
+            assert state_out != 'alias' or st_in is not None
+            st_out = None if state_out is None else st_in if state_out == 'alias' else bufs.out(N, 5 if vrnn else 2, D)
+            state = dict(t0=c['t0'], state_in=st_in, state_out=st_out)
         if vrnn:
-            ops.vrnn_generate(N, S, ns, D, H, L, C, gate[0], c['z_prior'], c['seed'], T(c['seeds'], dev), w, *enc, *dec, Xs, xh,
-                              clamp=clamp, temper=temper)
+            ops.vrnn_generate(N, S, ns, D, H, L, C, gate[0], c['z_prior'], c['seed'], T(c.get('seeds'), dev), w, *enc, *dec, Xs, xh,
+                              clamp=clamp, temper=temper, **state)
         else:
-            ops.vae_generate(N, ns, D, H, L, C, c['use_x_prev'], c['z_prior'], c['seed'], T(c['seeds'], dev), w, *enc, *dec, Xs, xh,
-                             clamp=clamp, temper=temper)
-    elif mode == 'resume':
-        st_in = bufs.inp(c['state_in']) if c.get('state_in') is not None else None
-        assert state_out != 'alias' or st_in is not None
-        st_out = None if state_out is None else st_in if state_out == 'alias' else bufs.out(N, 5 if vrnn else 2, D)
-        if vrnn:
-            ops.vrnn_generate_resume(N, S, ns, D, H, L, C, gate[0], c['z_prior'], c['seed'], T(c.get('seeds'), dev), w, *enc, *dec,
-                                     Xs, c['t0'], st_in, st_out, xhat=xh, clamp=clamp, temper=temper)
-        else:
-            ops.vae_generate_resume(N, ns, D, H, L, C, c['use_x_prev'], c['z_prior'], c['seed'], w, *enc, *dec, Xs, c['t0'], st_in,
-                                    st_out, xhat=xh, clamp=clamp, temper=temper)
+            ops.vae_generate(N, ns, D, H, L, C, c['use_x_prev'], c['z_prior'], c['seed'], T(c.get('seeds'), dev), w, *enc, *dec, Xs,
+                             xh, clamp=clamp, temper=temper, **state)
     elif mode in ('vary', 'vary_latents'):
         zout = bufs.out(3, N, Tn, L) if mode == 'vary_latents' else None
         head = (N, Tn, D, H, L, C, gate[0], c['hist_source'], c['seed'], T(c['sources'], dev), T(c.get('x0'), dev), w,
                 T(c['w_dec'], dev), *enc, *dec, Xs)
-        f = {('cl_vrnn', 'vary'): ops.vrnn_vary, ('cl_vrnn', 'vary_latents'): ops.vrnn_vary_latents,
-             ('cl_vae', 'vary'): ops.vae_vary, ('cl_vae', 'vary_latents'): ops.vae_vary_latents}[c['which'], mode]
-        f(*head, *(() if zout is None else (zout,)), xhat=xh, clamp=clamp, temper=temper)
+        (ops.vrnn_vary if vrnn else ops.vae_vary)(*head, xhat=xh, clamp=clamp, temper=temper, zout=zout)
     else:
         f = ops.vrnn_decode if vrnn else ops.vae_decode
         f(N, Tn, D, H, L, C, gate[0], c['seed'], T(c['z_in'], dev), T(c.get('x0'), dev), T(c.get('history'), dev), T(c['w_dec'], dev),

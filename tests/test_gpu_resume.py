@@ -418,7 +418,7 @@ def test_refusals(dev):
 
     def vrnn_call(t0):
         try:
-            ops.vrnn_generate_resume(N, 2, 4, D, 88, 2, C, eng.gate_act, False, 1, x_seed, wv, *eng._weights(), Xs, t0, None, out)
+            ops.vrnn_generate(N, 2, 4, D, 88, 2, C, eng.gate_act, False, 1, x_seed, wv, *eng._weights(), Xs, t0=t0, state_out=out)
         except _lib.ClvError as e:
             return str(e)
         return None
@@ -429,7 +429,8 @@ def test_refusals(dev):
 
     def vae_call(t0, state_in=sin):
         try:
-            ops.vae_generate_resume(N, 4, D, 88, 3, 4, True, False, 1, w1, *ev._weights(), Xs, t0, state_in, out2)
+            ops.vae_generate(N, 4, D, 88, 3, 4, True, False, 1, None, w1, *ev._weights(), Xs, t0=t0, state_in=state_in,
+                             state_out=out2)
         except _lib.ClvError as e:
             return str(e)
         return None

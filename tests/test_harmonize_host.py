@@ -14,7 +14,9 @@ if ROOT not in sys.path:
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.harmonize import FREE, voice_constraints  # noqa: E402
 
-NEW = ('clv_vrnn_generate_clamped', 'clv_vae_generate_clamped', 'clv_bernoulli_sample_clamped')
+# the roll is an argument of the two generate entry points (ABI 610: _clamped took over the base name)
+NEW = ('clv_vrnn_generate', 'clv_vae_generate', 'clv_bernoulli_sample_clamped')
+GONE = ('clv_vrnn_generate_clamped', 'clv_vae_generate_clamped')
 
 
 def _roll(*frames):
@@ -109,25 +111,33 @@ def test_clamped_entry_points_are_declared_and_bound():
     for n in NEW:
         assert re.search(r'\bint %s\(' % n, hdr), n
         assert n in _lib.SIGNATURES, n
+    for n in GONE:
+        assert n not in hdr and n not in _lib.SIGNATURES, n
+    C = _lib.C
+    for n, n_args, at in (('clv_vrnn_generate', 35, 25), ('clv_vae_generate', 29, 19)):      # the roll follows the weights
+        params = [a.strip() for a in re.search(r'\bint %s\(([^;]*?)\);' % n, hdr, re.S).group(1).split(',')]
+        assert len(params) == len(_lib.SIGNATURES[n][1]) == n_args and params[at] == 'const uint8_t* clamp', n
+        assert _lib.SIGNATURES[n][1][at] is C.c_void_p, n
     assert 'FREE = 255' in hdr and 'BRIDGE RULE' in hdr
-    assert _lib.ABI_VERSION == 600
+    assert _lib.ABI_VERSION == 610
 
 
 def test_clamped_entry_points_refuse_null_and_zero_arguments():
-    """Every new entry point answers CLV_EINVAL before it touches the device when its constraint roll or step counter is
-    missing, or a size is zero, even with all other arguments valid-looking."""
+    """Every new entry point answers CLV_EINVAL before it touches the device when a roll has no frame to constrain, its step
+    counter is missing, or a size is zero, even with all other arguments valid-looking.  (A generate call without a roll is
+    the plain call since ABI 610, and accepted: tests/test_sampling_refusals.py.)"""
     import ctypes as C
     from clvae_amd import _lib
     L = _lib.lib()
-    einval = L.clv_vrnn_generate_clamped(*([0] * 9 + [0] + [None] * 19))
+    tail = [0, 1.0, 1.0, 0, None, None]                # tempered, the two factors, t0, no states
+    einval = L.clv_vrnn_generate(*([0] * 9 + [0] + [None] * 16 + tail + [None] * 3))
     assert einval < 0
     dummy = (C.c_float * 64)()
     p = C.cast(dummy, C.c_void_p)
-    # a supported shape with every pointer set but the clamp
-    assert L.clv_vrnn_generate_clamped(1, 0, 1, 88, 88, 2, 10, 0, 0, 0, *([p] * 15), None, p, None, None) == einval
-    assert L.clv_vrnn_generate_clamped(1, 0, 0, 88, 88, 2, 10, 0, 0, 0, *([p] * 15), p, p, None, None) == einval
-    assert L.clv_vae_generate_clamped(1, 1, 88, 88, 2, 10, 1, 0, 0, *([p] * 10), None, p, None, None) == einval
-    assert L.clv_vae_generate_clamped(1, 0, 88, 88, 2, 10, 1, 0, 0, *([p] * 10), p, p, None, None) == einval
+    # a supported shape with every pointer set, the roll too, and no frame for it to constrain
+    assert L.clv_vrnn_generate(1, 0, 0, 88, 88, 2, 10, 0, 0, 0, *([p] * 15), p, *tail, p, None, None) == einval
+    assert L.clv_vrnn_generate(1, 1, 0, 88, 88, 2, 10, 0, 0, 0, *([p] * 15), p, *tail, p, None, None) == einval
+    assert L.clv_vae_generate(1, 0, 88, 88, 2, 10, 1, 0, 0, *([p] * 10), p, *tail, p, None, None) == einval
     args = [88, 88, 1, 0, p, p, p, p, p, None]         # (never called as it is: every variant below has one bad argument)
     for i, bad in ((0, 0), (1, 0), (2, 0), (3, -1), (0, 87), (4, None), (5, None), (6, None), (7, None), (8, None)):
         a = list(args)

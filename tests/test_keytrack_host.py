@@ -38,7 +38,7 @@ def test_both_entries_are_declared_and_bound_with_their_argument_counts():
 
 def test_abi_version_and_the_reserved_stream():
     from clvae_amd import trainer
-    assert _lib.ABI_VERSION == 600 and _lib.lib().clv_version() == 600
+    assert _lib.ABI_VERSION == 610 and _lib.lib().clv_version() == 610
     assert trainer.KEY_STREAM == 0xFFFFFFFB == KR.KEY_STREAM
     reserved = [trainer.IW_STREAM_W, trainer.IW_STREAM_Z, trainer.SMC_STREAM, trainer.SMC_W_STREAM, trainer.KEY_STREAM]
     assert len(set(reserved)) == len(reserved)

@@ -1,4 +1,4 @@
-"""Host side of latent paths in and out, no GPU: the five new declarations and bindings, every refused
+"""Host side of latent paths in and out, no GPU: the five declarations and bindings, every refused
 argument of the decoding and of morph(), and the sample tools' --morph flag and its rules."""
 import importlib
 import inspect
@@ -18,7 +18,7 @@ from clvae_amd.engine_generate import (VaeGenerate, VrnnGenerate, decode_args, d
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 D = 88
 
-ENTRY_POINTS = (('clv_vrnn_vary_latents', 33), ('clv_vae_vary_latents', 28), ('clv_vrnn_decode', 25), ('clv_vae_decode', 22),
+ENTRY_POINTS = (('clv_vrnn_vary', 33), ('clv_vae_vary', 28), ('clv_vrnn_decode', 25), ('clv_vae_decode', 22),
                 ('clv_lerp_rows', 9))
 
 
@@ -31,18 +31,23 @@ def test_declarations_and_bindings():
         assert len(m.group(1).split(',')) == n_args, name
         restype, argtypes = _lib.SIGNATURES[name]
         assert restype is C.c_int and len(argtypes) == n_args, name
-    for name, base in (('clv_vrnn_vary_latents', 'clv_vrnn_vary'), ('clv_vae_vary_latents', 'clv_vae_vary')):
-        new, old = _lib.SIGNATURES[name][1], _lib.SIGNATURES[base][1]
-        assert new[:-2] == old[:-1] and new[-2:] == [C.c_void_p, C.c_void_p]           # clv_*_vary plus zout ahead of stream
+    for name in ('clv_vrnn_vary', 'clv_vae_vary'):                 # zout sits between xhat and the stream
+        params = [p.strip() for p in re.search(r'\bint %s\(([^;]*?)\);' % name, hdr, re.S).group(1).split(',')]
+        assert params[-4:] == ['float* Xs', 'float* xhat', 'float* zout', 'void* stream'], name
+        assert _lib.SIGNATURES[name][1][-4:] == [C.c_void_p] * 4 and _lib.SIGNATURES[name][1][-5] is C.c_float, name
+    for gone in ('clv_vrnn_vary_latents', 'clv_vae_vary_latents'):        # ABI 610: they took over clv_*_vary
+        assert gone not in _lib.SIGNATURES and gone not in hdr, gone
     for name in ('clv_vrnn_decode', 'clv_vae_decode'):             # one temperature (the notes') ahead of Xs, xhat, stream
         at = _lib.SIGNATURES[name][1]
         assert at[7] is C.c_uint64 and at[-4] is C.c_float and at.count(C.c_float) == 1
         assert all(a is C.c_void_p for a in at[-3:])
     assert _lib.SIGNATURES['clv_lerp_rows'][1][:2] == [C.c_int64, C.c_int64]
-    assert _lib.ABI_VERSION == 600
-    assert re.search(r'#define CLV_ABI_VERSION 600\b', hdr)
-    for f in (ops.vrnn_vary_latents, ops.vae_vary_latents, ops.vrnn_decode, ops.vae_decode, ops.lerp_rows):
+    assert _lib.ABI_VERSION == 610
+    assert re.search(r'#define CLV_ABI_VERSION 610\b', hdr)
+    for f in (ops.vrnn_vary, ops.vae_vary, ops.vrnn_decode, ops.vae_decode, ops.lerp_rows):
         assert callable(f)
+    assert all(inspect.signature(f).parameters['zout'].default is None for f in (ops.vrnn_vary, ops.vae_vary))
+    assert not hasattr(ops, 'vrnn_vary_latents') and not hasattr(ops, 'vae_vary_latents')
     # the C side documents the contract it cannot check from a host pointer
     doc = hdr[hdr.index('latent paths in and out'):hdr.index('int clv_lerp_rows')]
     assert "caller's contract" in doc and 'noise_rows' in doc
@@ -75,15 +80,15 @@ def test_host_refusals_of_the_library():
                     dict(N=2 ** 20, T=2 ** 11, L=2),             # N*T*L = 2^32
                     dict(N=2 ** 16, T=2 ** 10, L=1)):            # N*T*D = 88 * 2^26 >= 2^32
             assert call(**dict(ok, **bad)) == -1, (call.__name__, bad)
-    # clv_*_vary_latents refuse what clv_*_vary refuses (here: no sources), and N*T*L >= 2^32 with a zout
-    assert lib.clv_vrnn_vary_latents(1, 1, D, 88, 2, 4, 0, 0, 1, None, None, p, p, *([p] * 13), None, 1.0, 1.0, p, None, p,
-                                     None) == -1
-    assert lib.clv_vae_vary_latents(1, 1, D, 88, 2, 4, 1, 0, 1, None, None, p, p, *([p] * 8), None, 1.0, 1.0, p, None, p,
-                                    None) == -1
-    assert lib.clv_vrnn_vary_latents(2 ** 20, 2 ** 11, D, 88, 2, 4, 0, 0, 1, p, None, p, p, *([p] * 13), None, 1.0, 1.0, p,
-                                     None, p, None) == -1
-    assert lib.clv_vae_vary_latents(2 ** 20, 2 ** 11, D, 88, 2, 4, 1, 0, 1, p, None, p, p, *([p] * 8), None, 1.0, 1.0, p, None,
-                                    p, None) == -1
+    # with a zout clv_*_vary refuse what they refuse without one (here: no sources), and N*T*L >= 2^32
+    assert lib.clv_vrnn_vary(1, 1, D, 88, 2, 4, 0, 0, 1, None, None, p, p, *([p] * 13), None, 1.0, 1.0, p, None, p,
+                             None) == -1
+    assert lib.clv_vae_vary(1, 1, D, 88, 2, 4, 1, 0, 1, None, None, p, p, *([p] * 8), None, 1.0, 1.0, p, None, p,
+                            None) == -1
+    assert lib.clv_vrnn_vary(2 ** 20, 2 ** 11, D, 88, 2, 4, 0, 0, 1, p, None, p, p, *([p] * 13), None, 1.0, 1.0, p,
+                             None, p, None) == -1
+    assert lib.clv_vae_vary(2 ** 20, 2 ** 11, D, 88, 2, 4, 1, 0, 1, p, None, p, p, *([p] * 8), None, 1.0, 1.0, p, None,
+                            p, None) == -1
 
 
 def test_signatures_of_the_python_layers():

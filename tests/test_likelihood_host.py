@@ -61,8 +61,8 @@ def test_header_and_signatures_agree_on_the_new_entry_points():
             else:
                 assert ctypes.sizeof(t) == 4 and t is not ctypes.c_float, (name, a)
     assert "double* state" in protos['clv_iw_accumulate'] and "const double* state" in protos['clv_iw_finish']
-    assert re.search(r"#define CLV_ABI_VERSION 600\b", open(os.path.join(ROOT, "include", "clvae.h")).read())
-    assert _lib.ABI_VERSION == 600
+    assert re.search(r"#define CLV_ABI_VERSION 610\b", open(os.path.join(ROOT, "include", "clvae.h")).read())
+    assert _lib.ABI_VERSION == 610
 
 
 def test_new_entry_points_refuse_bad_arguments_before_touching_the_device():

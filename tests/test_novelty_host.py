@@ -30,7 +30,7 @@ def test_the_entries_are_declared_bound_and_exported():
         assert hasattr(_lib.lib(), name)
     a = _lib.SIGNATURES['clv_roll_nearest'][1]
     assert all(t is ctypes.c_int for t in a[:6]) and all(t is ctypes.c_int64 for t in a[6:9]) and a[16] is ctypes.c_size_t
-    assert _lib.ABI_VERSION == 600 and _lib.lib().clv_version() == 600
+    assert _lib.ABI_VERSION == 610 and _lib.lib().clv_version() == 610
     from clvae_amd import ops
     assert callable(ops.roll_nearest) and callable(ops.roll_nearest_workspace_bytes)
     src = open(os.path.join(ROOT, "classifying-vae-lstm_amd", "csrc", "Makefile")).read()

@@ -1,4 +1,4 @@
-"""Host side of resumable generation, no GPU: the two new declarations and their bindings, what the
+"""Host side of resumable generation, no GPU: the two declarations and their bindings, what the
 launchers refuse before any device work, GenState on CPU tensors, the public calls' refusals, the sample tools' --chunk /
 --modulate and every rule between them and the other flags, and the validation of a modulation plan."""
 import importlib
@@ -24,25 +24,27 @@ EINVAL = -1
 def test_declarations_and_bindings():
     hdr = open(os.path.join(ROOT, 'include', 'clvae.h')).read()
     C = _lib.C
-    for name, n_args, tempered in (('clv_vrnn_generate_resume', 34, 'clv_vrnn_generate_tempered'),
-                                   ('clv_vae_generate_resume', 27, 'clv_vae_generate_tempered')):
+    for name, n_args in (('clv_vrnn_generate', 35), ('clv_vae_generate', 29)):
         m = re.search(r'\bint %s\(([^;]*?)\);' % name, hdr, re.S)
         assert m, name
         params = [p.strip() for p in m.group(1).split(',')]
         assert len(params) == n_args, name
-        # t0, state_in, state_out sit between the two temperatures and the outputs
+        # t0, state_in, state_out sit between the two temperatures and the outputs; the roll and the flag before those
+        assert params[-10:-8] == ['const uint8_t* clamp', 'int tempered'], name
         assert params[-8:] == ['float inv_temperature', 'float z_temperature', 'uint32_t t0', 'const float* state_in',
                                'float* state_out', 'float* Xs', 'float* xhat', 'void* stream'], name
         restype, argtypes = _lib.SIGNATURES[name]
         assert restype is C.c_int and len(argtypes) == n_args, name
-        assert argtypes[-8:] == [C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 5, name
-        # the arguments of the tempered entry with its nullable roll, plus the three (cl_vae: minus the seed frame)
-        base = _lib.SIGNATURES[tempered][1]
-        assert len(argtypes) == len(base) + 3 - (name == 'clv_vae_generate_resume')
-        assert C.c_uint64 in argtypes[:10]
-    assert _lib.ABI_VERSION == 600 and re.search(r'#define CLV_ABI_VERSION 600\b', hdr)      # entries were added, none changed
-    for f in (ops.vrnn_generate_resume, ops.vae_generate_resume):
-        assert callable(f)
+        assert argtypes[-10:] == [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_uint32] + [C.c_void_p] * 5, name
+        # both families give their seed frames where they always did: right after the 64-bit seed
+        seed = argtypes.index(C.c_uint64)
+        assert params[seed:seed + 3] == ['uint64_t seed', 'const float* x_seed', 'const float* w'], name
+        assert hdr.count(name + '_resume') == 0 and name + '_resume' not in _lib.SIGNATURES, name
+    assert _lib.ABI_VERSION == 610 and re.search(r'#define CLV_ABI_VERSION 610\b', hdr)      # _resume took over clv_*_generate
+    for f in (ops.vrnn_generate, ops.vae_generate):
+        sig = inspect.signature(f).parameters
+        assert sig['t0'].default == 0 and sig['state_in'].default is None and sig['state_out'].default is None
+    assert not hasattr(ops, 'vrnn_generate_resume') and not hasattr(ops, 'vae_generate_resume')
     for cls in (VrnnGenerate, VaeGenerate):
         sig = inspect.signature(cls.generate).parameters
         assert sig['state'].default is None and sig['return_state'].default is False
@@ -57,22 +59,23 @@ def _vrnn_call(lib, p, **over):
     a = dict(N=1, S=1, nsteps=2, L=2, C=4, gate=0, x_seed=p, w=p, W=[p] * 13, clamp=None, inv_T=1.0, Tz=1.0, t0=0,
              state_in=None, state_out=None, Xs=p, xhat=None)
     a.update(over)
-    return lib.clv_vrnn_generate_resume(a['N'], a['S'], a['nsteps'], D, 88, a['L'], a['C'], a['gate'], 0, 1, a['x_seed'], a['w'],
-                                        *a['W'], a['clamp'], a['inv_T'], a['Tz'], a['t0'], a['state_in'], a['state_out'], a['Xs'],
-                                        a['xhat'], None)
+    return lib.clv_vrnn_generate(a['N'], a['S'], a['nsteps'], D, 88, a['L'], a['C'], a['gate'], 0, 1, a['x_seed'], a['w'],
+                                 *a['W'], a['clamp'], 1, a['inv_T'], a['Tz'], a['t0'], a['state_in'], a['state_out'], a['Xs'],
+                                 a['xhat'], None)
 
 
 def _vae_call(lib, p, **over):
-    a = dict(N=1, nsteps=2, L=2, C=4, w=p, W=[p] * 8, clamp=None, inv_T=1.0, Tz=1.0, t0=0, state_in=p, state_out=None, Xs=p,
-             xhat=None)
+    a = dict(N=1, nsteps=2, L=2, C=4, x_seed=None, w=p, W=[p] * 8, clamp=None, inv_T=1.0, Tz=1.0, t0=0, state_in=p,
+             state_out=None, Xs=p, xhat=None)
     a.update(over)
-    return lib.clv_vae_generate_resume(a['N'], a['nsteps'], D, 88, a['L'], a['C'], 1, 0, 1, a['w'], *a['W'], a['clamp'],
-                                       a['inv_T'], a['Tz'], a['t0'], a['state_in'], a['state_out'], a['Xs'], a['xhat'], None)
+    return lib.clv_vae_generate(a['N'], a['nsteps'], D, 88, a['L'], a['C'], 1, 0, 1, a['x_seed'], a['w'], *a['W'], a['clamp'],
+                                1, a['inv_T'], a['Tz'], a['t0'], a['state_in'], a['state_out'], a['Xs'], a['xhat'], None)
 
 
 def test_launchers_refuse_before_any_device_work():
     """CLV_EINVAL with no GPU: null required pointers, everything the generate mode refuses, the step overflow, a cl_vae
-    call without state_in.  (No accepted call is made here: its pointers are host memory.)"""
+    call from / to a state without state_in or with a seed frame beside it.  (No accepted call is made here: its pointers are
+    host memory.)"""
     lib = _lib.lib()
     p = np.zeros(64 * 1024, np.float32).ctypes.data
     U32 = 2 ** 32 - 1
@@ -89,7 +92,8 @@ def test_launchers_refuse_before_any_device_work():
         W = [p] * 13
         W[k] = None
         assert _vrnn_call(lib, p, W=W) == EINVAL, k
-    for bad in (dict(state_in=None), dict(state_in=None, state_out=p), dict(w=None), dict(Xs=None), dict(N=0), dict(nsteps=0),
+    for bad in (dict(state_in=None), dict(state_in=None, state_out=p), dict(state_in=None, t0=1), dict(x_seed=p),
+                dict(x_seed=p, state_out=p, t0=3), dict(w=None), dict(Xs=None), dict(N=0), dict(nsteps=0),
                 dict(L=0), dict(L=33), dict(C=33), dict(inv_T=0.0), dict(Tz=-1.0), dict(t0=U32), dict(t0=U32 - 1),
                 dict(t0=2 ** 31, nsteps=2 ** 31)):
         assert _vae_call(lib, p, **bad) == EINVAL, bad

@@ -87,9 +87,9 @@ def test_each_family_states_its_own_particulars(monkeypatch):
     assert sv['x_dec'] is not xs2 and torch.equal(sv['x_dec'], xs2)
     sr = vrnn._smc_seed(xs3)
     assert sorted(sr) == ['dec_prev', 'seed_frames'] and sr['dec_prev'] == 'shared' and sr['seed_frames'] is xs3
-    # the entry points (vary_latents without a zout is the family's vary) and the state layout
-    assert VaeGenerate._vary_op is ops.vae_vary_latents and VaeGenerate._decode_op is ops.vae_decode
-    assert VrnnGenerate._vary_op is ops.vrnn_vary_latents and VrnnGenerate._decode_op is ops.vrnn_decode
+    # the entry points (vary stores the latents where it gets a zout) and the state layout
+    assert VaeGenerate._vary_op is ops.vae_vary and VaeGenerate._decode_op is ops.vae_decode
+    assert VrnnGenerate._vary_op is ops.vrnn_vary and VrnnGenerate._decode_op is ops.vrnn_decode
     assert (VaeGenerate.STATE_KIND, VrnnGenerate.STATE_KIND) == ('cl_vae', 'cl_vrnn')
     assert EG.STATE_FIELDS == {'cl_vrnn': ('h_enc', 'c_enc', 'h_dec', 'c_dec', 'x'), 'cl_vae': ('x_in', 'hist')}
     assert EG.SEED_RANK == {'cl_vrnn': 3, 'cl_vae': 2}

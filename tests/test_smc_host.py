@@ -20,7 +20,7 @@ def test_smc_entry_points_are_declared_and_bound():
     for n in NEW:
         assert re.search(r'\bint %s\(' % n, hdr), n
         assert n in _lib.SIGNATURES, n
-    assert _lib.ABI_VERSION == 600
+    assert _lib.ABI_VERSION == 610
 
 
 def test_smc_entry_points_refuse_bad_arguments():

@@ -22,7 +22,7 @@ def test_key_entry_points_are_declared_and_bound():
         assert re.search(r'\bint %s\(' % n, hdr), n
         assert n in _lib.SIGNATURES, n
         assert hasattr(_lib.lib(), n), n
-    assert _lib.ABI_VERSION == 600
+    assert _lib.ABI_VERSION == 610
     from clvae_amd import trainer
     assert trainer.SMC_W_STREAM == 0xFFFFFFFC and trainer.SMC_W_STREAM == trainer.SMC_STREAM - 1
     src = open(os.path.join(ROOT, 'classifying-vae-lstm_amd', 'csrc', 'smc.hip')).read()

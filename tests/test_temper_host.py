@@ -2,6 +2,8 @@
 tools' flags, and the new bindings."""
 import importlib
 import inspect
+import os
+import re
 
 import numpy as np
 import pytest
@@ -64,15 +66,24 @@ def test_public_calls_refuse_before_touching_the_device():
 
 
 def test_bindings():
-    for name in ('clv_vrnn_generate_tempered', 'clv_vae_generate_tempered', 'clv_sigmoid_temper', 'clv_scale_temper'):
+    for name in ('clv_vrnn_generate', 'clv_vae_generate', 'clv_sigmoid_temper', 'clv_scale_temper'):
         assert name in _lib.SIGNATURES
     C = _lib.C
-    for name, base in (('clv_vrnn_generate_tempered', 'clv_vrnn_generate_clamped'), ('clv_vae_generate_tempered', 'clv_vae_generate_clamped')):
-        new, old = _lib.SIGNATURES[name][1], _lib.SIGNATURES[base][1]
-        assert len(new) == len(old) + 2 and new[-5:-3] == [C.c_float, C.c_float] and new[:-5] == old[:-3]
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'clvae.h')).read()
+    # the roll, the flag and the two factors follow the weights: clamp, tempered, inv_temperature, z_temperature
+    for name, n_args, at in (('clv_vrnn_generate', 35, 25), ('clv_vae_generate', 29, 19)):
+        argtypes = _lib.SIGNATURES[name][1]
+        assert len(argtypes) == n_args and argtypes[at:at + 4] == [C.c_void_p, C.c_int, C.c_float, C.c_float], name
+        assert argtypes.count(C.c_float) == 2 and all(a is C.c_void_p for a in argtypes[at - 4:at]), name
+        params = [p.strip() for p in re.search(r'\bint %s\(([^;]*?)\);' % name, hdr, re.S).group(1).split(',')]
+        assert len(params) == n_args, name
+        assert params[at:at + 4] == ['const uint8_t* clamp', 'int tempered', 'float inv_temperature', 'float z_temperature'], name
+    for fam in ('vrnn', 'vae'):                                # ABI 610: the base name took the variants over
+        for gone in ('clv_%s_generate_clamped' % fam, 'clv_%s_generate_tempered' % fam):
+            assert gone not in _lib.SIGNATURES and gone not in hdr
     assert callable(ops.sigmoid_temper) and callable(ops.scale_temper)
     assert 'temper' in inspect.signature(ops.vrnn_generate).parameters and 'temper' in inspect.signature(ops.vae_generate).parameters
-    assert _lib.ABI_VERSION == 600
+    assert _lib.ABI_VERSION == 610
 
 
 @pytest.mark.parametrize("which", ['cl_vae', 'cl_vrnn'])

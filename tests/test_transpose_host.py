@@ -182,7 +182,7 @@ def test_entry_is_declared_and_bound(tmp_path):
     plain = args('clv_gather_rows_multi')
     assert args('clv_gather_transposed') == plain[:-1] + ['draw', 'stream']          # the plain gather's list, plus the draw
     assert hasattr(_lib.lib(), 'clv_gather_transposed') and callable(ops.gather_transposed)
-    assert _lib.ABI_VERSION == 600 and _lib.lib().clv_version() == 600
+    assert _lib.ABI_VERSION == 610 and _lib.lib().clv_version() == 610
     mk = open(os.path.join(ROOT, 'classifying-vae-lstm_amd', 'csrc', 'Makefile')).read()
     assert 'transpose_aug.hip' in mk
     # ops.TransposeDraw against clv_transpose_draw as gcc lays it out

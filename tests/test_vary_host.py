@@ -21,17 +21,20 @@ D = 88
 def test_declarations_and_bindings():
     hdr = open(os.path.join(ROOT, 'include', 'clvae.h')).read()
     C = _lib.C
-    for name, n_args in (('clv_vrnn_vary', 32), ('clv_vae_vary', 27), ('clv_take_frame', 7)):
+    for name, n_args in (('clv_vrnn_vary', 33), ('clv_vae_vary', 28), ('clv_take_frame', 7)):
         m = re.search(r'\bint %s\(([^;]*?)\);' % name, hdr, re.S)
         assert m, name
         assert len(m.group(1).split(',')) == n_args, name
         restype, argtypes = _lib.SIGNATURES[name]
         assert restype is C.c_int and len(argtypes) == n_args, name
-    for name in ('clv_vrnn_vary', 'clv_vae_vary'):               # two temperatures ahead of Xs, xhat, stream
+    for name in ('clv_vrnn_vary', 'clv_vae_vary'):               # the roll and two temperatures ahead of Xs, xhat, zout, stream
         at = _lib.SIGNATURES[name][1]
-        assert at[8] is C.c_uint64 and at[-5:-3] == [C.c_float, C.c_float] and all(a is C.c_void_p for a in at[-3:])
-    assert _lib.ABI_VERSION == 600
-    assert re.search(r'#define CLV_ABI_VERSION 600\b', hdr)
+        assert at[8] is C.c_uint64 and at[-7:-4] == [C.c_void_p, C.c_float, C.c_float] and all(a is C.c_void_p for a in at[-4:])
+        params = [p.strip() for p in re.search(r'\bint %s\(([^;]*?)\);' % name, hdr, re.S).group(1).split(',')]
+        assert params[8] == 'uint64_t seed' and params[-7:] == ['const uint8_t* clamp', 'float inv_temperature',
+            'float z_temperature', 'float* Xs', 'float* xhat', 'float* zout', 'void* stream'], name
+    assert _lib.ABI_VERSION == 610
+    assert re.search(r'#define CLV_ABI_VERSION 610\b', hdr)
     for f in (ops.vrnn_vary, ops.vae_vary, ops.take_frame):
         assert callable(f)
     mk = open(os.path.join(ROOT, 'classifying-vae-lstm_amd', 'csrc', 'Makefile')).read()

@@ -306,7 +306,7 @@ def test_the_pinned_surfaces_are_what_they_were():
         for name in ('generate', 'vary', 'decode_latents', 'generate_smc'):
             params = list(inspect.signature(getattr(cls, name)).parameters)
             assert 'clamp' in params and 'voices' not in params, (cls.__name__, name)
-    assert _lib.ABI_VERSION == 600
+    assert _lib.ABI_VERSION == 610
     structs = {n for n in dir(_lib) if isinstance(getattr(_lib, n), type) and issubclass(getattr(_lib, n), ctypes.Structure)
                and getattr(_lib, n) is not ctypes.Structure}
     assert len(structs) == 14
