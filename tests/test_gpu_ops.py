@@ -416,7 +416,7 @@ def test_rmsprop_three_steps(dev):
 
 def test_philox_matches_oracle(dev):
     from clvae_amd import ops
-    for first in (0, 5, 1027):
+    for first in (0, 5, 1027, 2 ** 34 - 3, 2 ** 40 + 1):       # the last two: a carry into, and a non-zero, high counter word
         n = 4099
         out = torch.empty(n, device=dev)
         ops.philox_uniform(out, n, seed=0x123456789ABC, step=3, stream_id=2, first_index=first)
@@ -424,6 +424,12 @@ def test_philox_matches_oracle(dev):
                                       OP.uniform(n, 0x123456789ABC, 3, 2, first))
         ops.philox_normal(out, n, seed=99, step=1, stream_id=0, first_index=first)
         np.testing.assert_allclose(N(out), OP.normal(n, 99, 1, 0, first), atol=2e-5)
+    # both streams of one clv_philox_normal2 call are clv_philox_normal's values, bit for bit, past the carry as well
+    o0, o1, s0, s1 = (torch.empty(m, device=dev) for m in (1001, 517, 1001, 517))
+    ops.philox_normal2(o0, 1001, 3, 2 ** 34 - 3, o1, 517, 0xFFFFFFFC, 2 ** 40 + 1, seed=99, step=4)
+    ops.philox_normal(s0, 1001, seed=99, step=4, stream_id=3, first_index=2 ** 34 - 3)
+    ops.philox_normal(s1, 517, seed=99, step=4, stream_id=0xFFFFFFFC, first_index=2 ** 40 + 1)
+    assert torch.equal(o0, s0) and torch.equal(o1, s1)
     # step read from a device counter == step passed by value
     ctr = torch.tensor([7], dtype=torch.int32, device=dev)
     a = torch.empty(1000, device=dev); b = torch.empty(1000, device=dev)

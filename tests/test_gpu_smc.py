@@ -64,7 +64,7 @@ def test_smc_sample_kernel(dev):
             rows = np.repeat(roll[:, k], P, axis=0)
             want = SR.sample_frame(xhat, u, rows)
             assert np.array_equal(x.cpu().numpy(), want)
-            np.testing.assert_allclose(ell.cpu().numpy(), SR.increment(xhat, rows), rtol=1e-6, atol=0)
+            np.testing.assert_allclose(ell.cpu().numpy(), SR.increment(xhat, rows), rtol=1e-12, atol=0)
             assert np.all(ell.cpu().numpy()[:P] == 0.0)
             h = hist.cpu().numpy()
             assert np.array_equal(h[k], want.astype(np.uint8))
@@ -98,8 +98,8 @@ def test_smc_resample_kernel(dev, G, P, tau):
         np.testing.assert_allclose(ess[:, k].cpu().numpy(), ref.ess[:, k], rtol=1e-12)
         assert np.array_equal(flag.cpu().numpy().astype(bool), ref.resampled[k])
         a = anc[k].cpu().numpy()
-        ok = (a == ref.anc[k]) | ref.near[k]
-        assert ok.all(), (k, np.argwhere(~ok)[:4])
+        assert not ref.near[k].any()                      # no draw of this test sits within 1e-9 P of a grid point
+        assert np.array_equal(a, ref.anc[k]), (k, np.argwhere(a != ref.anc[k])[:4])
     assert np.array_equal(nres.cpu().numpy(), ref.nres)
     if tau == 0.0:
         assert ref.nres.sum() == 0
