@@ -254,6 +254,9 @@ SIGNATURES = {
     "clv_smc_pin_frame": (_i, [_i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "clv_smc_resample_conditional": (_i, [_i, _i, _i, _i, _u64, _i64, _d] + [_p] * 9),
     "clv_smc_backtrack_path": (_i, [_i] * 6 + [_p] * 10),
+    "clv_smc_resample_carry": (_i, [_i, _i, _i, _i, _u64, _i64, _d] + [_p] * 8 + [_u32, _i, _p]),
+    "clv_smc_commit": (_i, [_i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "clv_smc_collapse": (_i, [_i, _i, _i, _u64, _i64, _u32, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "clv_bernoulli_sample_voices": (_i, [_i64, _i, _i, _i] + [_p] * 8),
     "clv_smc_sample_voices": (_i, [_i] * 5 + [_p] * 10),
     "clv_key_track_windows": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _u64, _i64, _p, _p, _p]),

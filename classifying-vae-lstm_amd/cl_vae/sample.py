@@ -8,11 +8,11 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, NOVELTY_FLAGS, RESUME_FLAGS,  # noqa: E402
-                           TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, morph_kwargs, novelty_check, parser_for,
-                           resume_kwargs, resuming, temperature_kwargs, voices_kwargs)
-from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, print_renewed, voice_constraints,  # noqa: E402
-                                 voice_counts)
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, LIVE_FLAGS, MORPH_FLAGS, NOVELTY_FLAGS,  # noqa: E402
+                           RESUME_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, live_kwargs, morph_kwargs,
+                           novelty_check, parser_for, resume_kwargs, resuming, temperature_kwargs, voices_kwargs)
+from clvae_amd.harmonize import (accompany, harmonize, live_harmonize, print_evidence, print_key_posterior,  # noqa: E402
+                                 print_renewed, voice_constraints, voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
@@ -89,6 +89,12 @@ class Sampler:
             out = generate_chunked(self.model, seeds, self.args.t, np.vstack(ws), seed=getattr(self.args, 'seed', 0),
                                    z_prior=self.args.use_z_prior, clamp=kept_voice(self.args, sources),
                                    **resume, **temperature_kwargs(self.args))
+        elif live_kwargs(self.args)[0]:     # --live: the filter fed a chunk at a time, final frames handed out on the way
+            live, live_kw = live_kwargs(self.args)
+            out = live_harmonize(accompany(self.model, seeds, np.vstack(ws), voice=voice_of(self.args), particles=particles,
+                                           voices=voices_kwargs(self.args), seed=getattr(self.args, 'seed', 0),
+                                           z_prior=self.args.use_z_prior, **live_kw),
+                                 sources, live, **temperature_kwargs(self.args))
         else:
             out = harmonize(self.model, seeds, sources, None if ws is None else np.vstack(ws), voice=voice_of(self.args),
                             seed=getattr(self.args, 'seed', 0), z_prior=self.args.use_z_prior, particles=particles,
@@ -208,4 +214,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vae.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + NOVELTY_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + NOVELTY_FLAGS + LIVE_FLAGS).parse_args())

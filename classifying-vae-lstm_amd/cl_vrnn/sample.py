@@ -8,11 +8,11 @@ if __package__ in (None, ''):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
-from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, MORPH_FLAGS, NOVELTY_FLAGS, RESUME_FLAGS,  # noqa: E402
-                           TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, morph_kwargs, novelty_check, parser_for,
-                           resume_kwargs, resuming, temperature_kwargs, voices_kwargs)
-from clvae_amd.harmonize import (harmonize, print_evidence, print_key_posterior, print_renewed, voice_constraints,  # noqa: E402
-                                 voice_counts)
+from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, LIVE_FLAGS, MORPH_FLAGS, NOVELTY_FLAGS,  # noqa: E402
+                           RESUME_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, live_kwargs, morph_kwargs,
+                           novelty_check, parser_for, resume_kwargs, resuming, temperature_kwargs, voices_kwargs)
+from clvae_amd.harmonize import (accompany, harmonize, live_harmonize, print_evidence, print_key_posterior,  # noqa: E402
+                                 print_renewed, voice_constraints, voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
 from clvae_amd.utils.midi_utils import write_sample  # noqa: E402
 from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
@@ -87,9 +87,14 @@ def harmonize_samples(P, w_enc_model, args, margs, model, picks, label_of, voice
         if args.infer_w:
             ws = [M.infer_label(w_enc_model, s, margs['seq_length'], discrete=args.discrete_w) for s in seeds]
         resume = resume_kwargs(args, P.key_map, len(picks), margs['n_classes'])
+        live, live_kw = live_kwargs(args)
         if resume:              # --chunk / --modulate: harmonize()'s call a chunk at a time, the roll sliced per chunk
             out = generate_chunked(model, seeds, t, np.vstack(ws), seed=getattr(args, 'seed', 0),
                                    clamp=kept_voice(args, sources), **resume, **temperature_kwargs(args))
+        elif live:              # --live: the filter fed `live` frames at a time, final frames handed out on the way
+            out = live_harmonize(accompany(model, seeds, np.vstack(ws), voice=voice, particles=particles,
+                                           voices=voices_kwargs(args), seed=getattr(args, 'seed', 0), **live_kw),
+                                 sources, live, **temperature_kwargs(args))
         else:
             out = harmonize(model, seeds, sources, np.vstack(ws), voice=voice, seed=getattr(args, 'seed', 0),
                             particles=particles, return_evidence=particles is not None, **temperature_kwargs(args),
@@ -189,4 +194,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vrnn.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + NOVELTY_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + NOVELTY_FLAGS + LIVE_FLAGS).parse_args())

@@ -190,6 +190,22 @@ GIBBS_FLAGS = [
 ]
 
 
+# live harmonization (not in the reference): the particle filter fed a chunk of the melody at a time
+LIVE_FLAGS = [
+    Flag(('--live',), int, None, 'with --harmonize --particles: feed the -t frames to the filter in chunks of this many and '
+                                 'print per chunk how many frames are final and how many are held back; the files are those '
+                                 'of the run without --live'),
+    Flag(('--max_lag',), int, None, 'with --live: hold back at most this many frames per sample; a sample that exceeds it is '
+                                    'collapsed onto one particle (an approximation: the files may then differ)'),
+]
+
+
+def live_kwargs(args):
+    """--live / --max_lag as (chunk, dict(max_lag=...)); (None, {}) without --live (also for parsers without the flags)"""
+    k = getattr(args, 'live', None)
+    return (None, {}) if k is None else (int(k), dict(max_lag=getattr(args, 'max_lag', None)))
+
+
 # novelty audit (not in the reference; DESIGN.md 22): the rolls a sampling tool writes against the training split's songs
 NOVELTY_FLAGS = [
     Flag(('--novelty',), int, None, 'audit the samples for copied passages: every window of this many frames of every sample '
@@ -291,7 +307,8 @@ class _Parser(argparse.ArgumentParser):
     with --particles and not with --infer_key, a temperature other than 1 not with --host_loop (the host loop is the reference's and has none), --vary not with
     --harmonize or --host_loop, --to_key / --vary_history only with --vary, --morph >= 1 and not with --harmonize, --vary or
     --host_loop, --chunk >= 1 and a well-formed --modulate, neither with --particles, --vary, --morph or --host_loop, a
-    well-formed --voices LO[:HI] and not with --host_loop, --novelty >= 1, --novelty_transpose in 0..12 and only with --novelty"""
+    well-formed --voices LO[:HI] and not with --host_loop, --live >= 1 only with --particles and not with --sweeps,
+    --infer_key, --chunk, --modulate, --vary, --morph or --host_loop, --max_lag >= 0 only with --live, --novelty >= 1, --novelty_transpose in 0..12 and only with --novelty"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -325,6 +342,22 @@ class _Parser(argparse.ArgumentParser):
                 self.error('--sweeps must be >= 1')
             if getattr(ns, 'infer_key', None):
                 self.error('--sweeps pins no key: not with --infer_key')
+        live, lag = getattr(ns, 'live', None), getattr(ns, 'max_lag', None)
+        if live is not None:
+            if live < 1:
+                self.error('--live must be >= 1')
+            if particles is None:
+                self.error('--live feeds the particle filter: it needs --harmonize and --particles')
+            for flag, on in (('--sweeps', sweeps is not None), ('--infer_key', bool(getattr(ns, 'infer_key', None))),
+                             ('--chunk', chunk is not None), ('--modulate', mod is not None),
+                             ('--vary', getattr(ns, 'vary', False)), ('--morph', getattr(ns, 'morph', None) is not None),
+                             ('--host_loop', getattr(ns, 'host_loop', False))):
+                if on:
+                    self.error('--live streams one pass of the filter under one label: not with %s' % flag)
+            if lag is not None and lag < 0:
+                self.error('--max_lag must be >= 0')
+        elif lag is not None:
+            self.error('--max_lag needs --live')
         if getattr(ns, 'vary', False):
             if getattr(ns, 'harmonize', None):
                 self.error('--vary re-decodes whole pieces: not with --harmonize')

@@ -14,6 +14,10 @@
 // clv_smc_pin_z and clv_smc_pin_frame put that path's latents, frames and bridge into the pinned row, in the frame;
 // clv_smc_resample_conditional is clv_smc_resample with conditional multinomial resampling (one kernel body, two instances);
 // clv_smc_backtrack_path writes the lineage clv_smc_backtrack drew as the next retained path, latents included.
+// A filter stream stops the filter after any frame and continues it: clv_smc_resample_carry is clv_smc_resample
+// with a Philox step offset and a carry of the weights (the same kernel body), clv_smc_commit emits the pending frames on
+// which every lineage agrees and keeps the rest in a ring per melody, clv_smc_collapse draws the particle a melody is forced
+// onto (or ends on) and writes its pending lineage.
 // Every output element has one owner and no kernel uses atomics, so every result is bitwise reproducible.
 #include "common.h"
 #include "philox.h"
@@ -23,6 +27,7 @@ namespace clv {
 constexpr uint32_t SMC_STREAM = 0xFFFFFFFDu;        // trainer.py's stream map, next to the IW pair
 constexpr uint32_t SMC_W_STREAM = 0xFFFFFFFCu;      // the particles' keys: step 0 the categorical u0, step 1 the eps
 constexpr uint32_t GIBBS_STREAM = 0xFFFFFFFAu;      // a conditional sweep's own uniform per particle (0xFFFFFFFB: key_track)
+constexpr uint32_t COLLAPSE_STREAM = 0xFFFFFFF8u;   // a filter stream's forced pick; 0xFFFFFFF9: the transposer
 constexpr int SMC_MAX_C = 32;                        // classes of a label row (MAXC of the label kernels)
 constexpr int SMC_MAX_P = 1024;                      // particles per melody: one workgroup holds them
 constexpr int SMC_MAX_BUFS = 8;
@@ -87,8 +92,8 @@ __device__ __forceinline__ int systematic_pick(const double* cum, int P, double 
   return lo;
 }
 
-__device__ __forceinline__ double smc_uniform(uint64_t seed, int64_t melody, int step) {
-  return (double)philox_uniform_at((uint64_t)melody, (uint32_t)seed, (uint32_t)(seed >> 32), SMC_STREAM, (uint32_t)step);
+__device__ __forceinline__ double smc_uniform(uint64_t seed, int64_t melody, uint32_t step, uint32_t stream = SMC_STREAM) {
+  return (double)philox_uniform_at((uint64_t)melody, (uint32_t)seed, (uint32_t)(seed >> 32), stream, step);
 }
 
 constexpr int SMC_ROWS = 4;        // rows (waves) per workgroup of the row kernels
@@ -127,21 +132,24 @@ __global__ __launch_bounds__(64 * SMC_ROWS) void smc_sample_kernel(int R, int D,
 // CONDITIONAL (particle Gibbs): row m * P is the retained path and keeps itself as its ancestor; every other
 // particle draws its own uniform (GIBBS_STREAM, index = its GLOBAL row) and takes the first q with cum[q] > u, the last
 // one if none -- conditional multinomial resampling.  Weights, log Z, ESS and the rule are the filter's.
+// t0, carry (a filter stream): the Philox step of the uniforms is t0 + the chain step, and with carry the
+// launch's step 0 continues logW, logZ and nres instead of starting them.  0, 0: the filter of one call.
 template <bool CONDITIONAL>
 __global__ __launch_bounds__(SMC_MAX_P) void smc_resample_kernel(int P, int nsteps, int S, uint64_t seed, int64_t m0,
                                                                  double tau, const double* ell, double* logW, double* logZ,
                                                                  double* ess, int32_t* nres, int32_t* flag, int32_t* anc,
-                                                                 const int32_t* step_dev, int R) {
+                                                                 const int32_t* step_dev, int R, uint32_t t0, int carry) {
   __shared__ double red[SMC_MAX_P / 64];
   __shared__ double cum[SMC_MAX_P];
   const int k = *step_dev - S;
   if (k < 0 || k >= nsteps) return;             // seed steps and the bridge carry no weight (uniform exit: no barrier hit)
+  const bool first = k == 0 && !carry;
   const int m = blockIdx.x, p = threadIdx.x;
   const bool mine = p < P;
   const int64_t r = (int64_t)m * P + p;
   const double logP = log((double)P);
   // step 0 starts from uniform weights, log Z = 0 and no resamples: nothing to initialise before the first replay
-  const double lw = mine ? (k == 0 ? -logP : logW[r]) + ell[r] : -INFINITY;
+  const double lw = mine ? (first ? -logP : logW[r]) + ell[r] : -INFINITY;
   const double M = block_max(lw, red);
   const double a = mine ? exp(lw - M) : 0.0;
   const double s1 = block_sum(a, red);
@@ -155,10 +163,10 @@ __global__ __launch_bounds__(SMC_MAX_P) void smc_resample_kernel(int P, int nste
     if (mine) {
       if (CONDITIONAL) {
         const double up = (double)philox_uniform_at((uint64_t)((m0 + m) * P + p), (uint32_t)seed, (uint32_t)(seed >> 32),
-                                                    GIBBS_STREAM, (uint32_t)(k + S));
+                                                    GIBBS_STREAM, t0 + (uint32_t)(k + S));
         anc[(int64_t)k * R + r] = m * P + (p == 0 ? 0 : systematic_pick(cum, P, 1.0, up));
       } else {
-        const double u0 = smc_uniform(seed, m0 + m, k + S);
+        const double u0 = smc_uniform(seed, m0 + m, t0 + (uint32_t)(k + S));
         anc[(int64_t)k * R + r] = m * P + systematic_pick(cum, P, (double)P, u0 + (double)p);
       }
       logW[r] = -logP;
@@ -168,9 +176,9 @@ __global__ __launch_bounds__(SMC_MAX_P) void smc_resample_kernel(int P, int nste
     logW[r] = wn;
   }
   if (p == 0) {
-    logZ[m] = (k == 0 ? 0.0 : logZ[m]) + lse;
+    logZ[m] = (first ? 0.0 : logZ[m]) + lse;
     ess[(int64_t)m * nsteps + k] = e;
-    nres[m] = (k == 0 ? 0 : nres[m]) + (resample ? 1 : 0);
+    nres[m] = (first ? 0 : nres[m]) + (resample ? 1 : 0);
     flag[m] = resample ? 1 : 0;
   }
 }
@@ -215,7 +223,7 @@ __global__ __launch_bounds__(SMC_MAX_P) void smc_backtrack_kernel(int P, int nst
   __shared__ double cum[SMC_MAX_P];
   const int m = blockIdx.x, p = threadIdx.x;
   block_inclusive_scan(p < P ? exp(logW[(int64_t)m * P + p]) : 0.0, cum, red);
-  const double u0 = smc_uniform(seed, m0 + m, step);
+  const double u0 = smc_uniform(seed, m0 + m, (uint32_t)step);
   const int lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   for (int o = threadIdx.x >> 6; o < n_out; o += nw) {
     const int pick = systematic_pick(cum, P, (double)n_out, u0 + (double)o);
@@ -375,6 +383,122 @@ __global__ __launch_bounds__(64 * SMC_ROWS) void smc_backtrack_path_kernel(int G
     for (int j = lane; j < D; j += 64) bridge_ref[(int64_t)m * D + j] = bridge_rows[r * D + j];
 }
 
+// ---- a filter stream: the filter stops after any frame; frames on which every lineage agrees go out ----
+// The pending store keeps, per melody, the steps that are not emitted yet in a ring of `cap` slots: pending step j of
+// melody m lives in slot (head[m] + j) % cap, its ancestors in panc [cap, R] (global rows, as anc) and its frames in phist
+// [cap, R, D]; len[m] steps are live.  A melody's rows of a slot belong to that melody alone.
+__device__ __forceinline__ int smc_local(int32_t row, int m, int P) { return min(max((int)row - m * P, 0), P - 1); }
+
+// One workgroup per melody; thread p walks lineage p back through the n steps of the chunk just run (anc, hist) and then
+// through the len[m] pending ones.  Step j is coalesced when all P lineages pass through one row; the first such step
+// met on the way back, and every step before it, is final: from there on all threads hold the same row and copy its
+// frames out (out [G, out_cap, D], row j = pending step j), and no further test is needed.  The chunk's steps that stay
+// pending are appended to the ring.  The caller keeps len[m] + n <= min(cap, out_cap); a melody that breaks this is left
+// as it is and reports ncommit[m] = -1.
+__global__ __launch_bounds__(SMC_MAX_P) void smc_commit_kernel(int P, int D, int n, int R, const int32_t* anc,
+                                                               const uint8_t* hist, int cap, int32_t* panc, uint8_t* phist,
+                                                               int32_t* head, int32_t* len, int out_cap, int32_t* ncommit,
+                                                               uint8_t* out, int words) {
+  __shared__ int s_lo[SMC_MAX_P / 64], s_hi[SMC_MAX_P / 64];
+  const int m = blockIdx.x, p = threadIdx.x, lane = p & 63, w = p >> 6, nw = blockDim.x >> 6;
+  const int h0 = head[m], l0 = len[m];
+  const int total = l0 + n;
+  if (h0 < 0 || h0 >= cap || l0 < 0 || l0 > cap || total > cap || total > out_cap) {      // uniform over the workgroup
+    if (p == 0) ncommit[m] = -1;
+    return;
+  }
+  const int64_t first = (int64_t)m * P;
+  int cur = min(p, P - 1);                       // the threads past P repeat lineage P - 1: no effect on the test
+  bool one = false;
+  int nc = 0;
+  for (int j = total - 1; j >= 0; --j) {
+    const bool old = j < l0;
+    const int64_t at = old ? (int64_t)((h0 + j) % cap) * R : (int64_t)(j - l0) * R;
+    cur = smc_local((old ? panc : anc)[at + first + cur], m, P);
+    if (!one) {
+      int lo = cur, hi = cur;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o, 64));
+        hi = max(hi, __shfl_xor(hi, o, 64));
+      }
+      if (lane == 0) { s_lo[w] = lo; s_hi[w] = hi; }
+      __syncthreads();
+      lo = s_lo[0], hi = s_hi[0];
+      for (int i = 1; i < nw; ++i) { lo = min(lo, s_lo[i]); hi = max(hi, s_hi[i]); }
+      __syncthreads();
+      if (lo == hi) { one = true; nc = j + 1; }  // the same for every thread: steps 0 .. j are final
+    }
+    if (one) {
+      const uint8_t* h = (old ? phist : hist) + (at + first + cur) * D;
+      uint8_t* o = out + ((int64_t)m * out_cap + j) * D;
+      for (int i = p; i < D; i += blockDim.x) o[i] = h[i];
+    }
+  }
+  const int64_t nb = (int64_t)P * D;             // a melody's bytes of one step
+  for (int j = max(l0, nc); j < total; ++j) {    // what stays pending of the chunk joins the ring; its slots hold nothing live
+    const int64_t src = (int64_t)(j - l0) * R + first, dst = (int64_t)((h0 + j) % cap) * R + first;
+    for (int q = p; q < P; q += blockDim.x) panc[dst + q] = anc[src + q];
+    if (words) {
+      const uint32_t* s4 = (const uint32_t*)(hist + src * D);
+      uint32_t* d4 = (uint32_t*)(phist + dst * D);
+      for (int64_t i = p; i < nb / 4; i += blockDim.x) d4[i] = s4[i];
+    } else {
+      for (int64_t i = p; i < nb; i += blockDim.x) phist[dst * D + i] = hist[src * D + i];
+    }
+  }
+  __syncthreads();
+  if (p == 0) {
+    head[m] = (h0 + nc) % cap;
+    len[m] = total - nc;
+    ncommit[m] = nc;
+  }
+}
+
+// One workgroup per melody with pick_of[m] != 0 (NULL: every melody): one particle drawn from the current weights as
+// smc_backtrack_kernel draws its single path (the same scan, the same search, n = 1); its lineage through the pending
+// steps goes to out [G, out_cap, D].  final_: the uniform is the backtrack's (SMC_STREAM) and nothing else is written.
+// Otherwise the uniform is COLLAPSE_STREAM's and the melody restarts from the pick: anc_row [R] = the picked row for all
+// of its rows and flag[m] = 1 (what smc_gather_kernel reads), logW = -log P, no pending step.
+__global__ __launch_bounds__(SMC_MAX_P) void smc_collapse_kernel(int P, int D, int R, uint64_t seed, int64_t m0, uint32_t step,
+                                                                 int final_, const int32_t* pick_of, double* logW, int cap,
+                                                                 const int32_t* panc, const uint8_t* phist,
+                                                                 const int32_t* head, int32_t* len, int out_cap,
+                                                                 int32_t* picks, uint8_t* out, int32_t* anc_row,
+                                                                 int32_t* flag) {
+  __shared__ double red[SMC_MAX_P / 64];
+  __shared__ double cum[SMC_MAX_P];
+  const int m = blockIdx.x, p = threadIdx.x;
+  if (pick_of && !pick_of[m]) return;            // uniform over the workgroup: such a melody is not touched at all
+  const int h0 = head[m], l0 = len[m];
+  const int64_t first = (int64_t)m * P;
+  block_inclusive_scan(p < P ? exp(logW[first + p]) : 0.0, cum, red);
+  if (h0 < 0 || h0 >= cap || l0 < 0 || l0 > cap || l0 > out_cap) {
+    if (p == 0) picks[m] = -1;
+    return;
+  }
+  const double u0 = smc_uniform(seed, m0 + m, step, final_ ? SMC_STREAM : COLLAPSE_STREAM);
+  const int pick = systematic_pick(cum, P, 1.0, u0);
+  int cur = pick;
+  for (int j = l0 - 1; j >= 0; --j) {
+    const int64_t at = (int64_t)((h0 + j) % cap) * R + first;
+    cur = smc_local(panc[at + cur], m, P);
+    const uint8_t* h = phist + (at + cur) * D;
+    uint8_t* o = out + ((int64_t)m * out_cap + j) * D;
+    for (int i = p; i < D; i += blockDim.x) o[i] = h[i];
+  }
+  if (p == 0) picks[m] = pick;
+  if (final_) return;
+  if (p < P) {
+    anc_row[first + p] = (int32_t)(first + pick);
+    logW[first + p] = -log((double)P);
+  }
+  if (p == 0) {
+    flag[m] = 1;
+    len[m] = 0;
+  }
+}
+
 static inline int smc_block(int P) { return (P + 63) / 64 * 64; }
 
 }  // namespace clv
@@ -403,7 +527,7 @@ extern "C" int clv_smc_resample(int G, int P, int nsteps, int S, uint64_t seed, 
   hipStream_t s = (hipStream_t)stream;
   ProfScope pr("smc_resample", s);
   hipLaunchKernelGGL(smc_resample_kernel<false>, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, S, seed, m0, tau, ell, logW,
-                     logZ, ess, nres, flag, anc, step_dev, G * P);
+                     logZ, ess, nres, flag, anc, step_dev, G * P, 0u, 0);
   return launch_status();
 }
 
@@ -417,7 +541,7 @@ extern "C" int clv_smc_resample_conditional(int G, int P, int nsteps, int S, uin
   hipStream_t s = (hipStream_t)stream;
   ProfScope pr("smc_resample_conditional", s);
   hipLaunchKernelGGL(smc_resample_kernel<true>, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, S, seed, m0, tau, ell, logW,
-                     logZ, ess, nres, flag, anc, step_dev, G * P);
+                     logZ, ess, nres, flag, anc, step_dev, G * P, 0u, 0);
   return launch_status();
 }
 
@@ -530,5 +654,52 @@ extern "C" int clv_smc_take_w(int G, int P, int C, int n_out, const int32_t* pic
   ProfScope pr("smc_take_w", s);
   hipLaunchKernelGGL(smc_take_w_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (int)n, P, C, n_out, picks, wr,
                      w_out);
+  return launch_status();
+}
+
+// ---- a filter stream ----
+extern "C" int clv_smc_resample_carry(int G, int P, int nsteps, int S, uint64_t seed, int64_t m0, double tau,
+                                      const double* ell, double* logW, double* logZ, double* ess, int32_t* nres,
+                                      int32_t* flag, int32_t* anc, const int32_t* step_dev, uint32_t t0, int carry,
+                                      void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || nsteps <= 0 || S < 0 || m0 < 0 || !(tau >= 0.0 && tau <= 1.0) || !ell ||
+      !logW || !logZ || !ess || !nres || !flag || !anc || !step_dev)
+    return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_resample_carry", s);
+  hipLaunchKernelGGL(smc_resample_kernel<false>, dim3(G), dim3(smc_block(P)), 0, s, P, nsteps, S, seed, m0, tau, ell, logW,
+                     logZ, ess, nres, flag, anc, step_dev, G * P, t0, carry);
+  return launch_status();
+}
+
+extern "C" int clv_smc_commit(int G, int P, int D, int n, const int32_t* anc, const uint8_t* hist, int cap,
+                              int32_t* pend_anc, uint8_t* pend_hist, int32_t* head, int32_t* len, int out_cap,
+                              int32_t* ncommit, uint8_t* out, void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || D <= 0 || n <= 0 || cap <= 0 || out_cap <= 0 || !anc || !hist || !pend_anc ||
+      !pend_hist || !head || !len || !ncommit || !out)
+    return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_commit", s);
+  const int words = ((int64_t)P * D) % 4 == 0 && (((uintptr_t)hist | (uintptr_t)pend_hist) & 3) == 0;
+  hipLaunchKernelGGL(smc_commit_kernel, dim3(G), dim3(smc_block(P)), 0, s, P, D, n, G * P, anc, hist, cap, pend_anc,
+                     pend_hist, head, len, out_cap, ncommit, out, words);
+  return launch_status();
+}
+
+extern "C" int clv_smc_collapse(int G, int P, int D, uint64_t seed, int64_t m0, uint32_t step, int final_pick,
+                                const int32_t* pick_of, double* logW, int cap, const int32_t* pend_anc,
+                                const uint8_t* pend_hist, const int32_t* head, int32_t* len, int out_cap, int32_t* picks,
+                                uint8_t* out, int32_t* anc_row, int32_t* flag, void* stream) {
+  if (G <= 0 || P <= 0 || P > SMC_MAX_P || D <= 0 || cap <= 0 || out_cap <= 0 || m0 < 0 || !logW || !pend_anc ||
+      !pend_hist || !head || !len || !picks || !out)
+    return CLV_EINVAL;
+  if (!final_pick && (!anc_row || !flag)) return CLV_EINVAL;
+  if ((int64_t)G * P > INT32_MAX) return CLV_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope pr("smc_collapse", s);
+  hipLaunchKernelGGL(smc_collapse_kernel, dim3(G), dim3(smc_block(P)), 0, s, P, D, G * P, seed, m0, step, final_pick,
+                     pick_of, logW, cap, pend_anc, pend_hist, head, len, out_cap, picks, out, anc_row, flag);
   return launch_status();
 }

@@ -520,6 +520,110 @@ def state_widths(kind, cfg):
     return {k: cfg['H'] if k in LSTM_FIELDS[kind] else cfg['D'] for k in STATE_FIELDS[kind]}
 
 
+class FilterState:
+    """What a filter stream carries from one advance to the next, for N melodies x P particles (global row
+    m * P + p, R = N * P rows): gen, the rows' sampler state as a GenState over R rows (what a particle hands to its
+    descendants; gen.t is the Philox step of the next frame); logW [R] and logZ [N] fp64, nres [N] and collapses [N] int32;
+    and the pending store, the steps whose frames are not emitted yet -- per melody a ring of cap slots, pending step j
+    (oldest first) in slot (head[m] + j) % cap of pend_anc [cap, R] int32 (every row's ancestor) and pend_hist [cap, R, D]
+    uint8 (every row's frame), len[m] of them live; head, len [N] int32.  Unlike a GenState, a FilterState is CONSUMED by the
+    call that takes it (the store is too large to copy per call): clone() first to keep one."""
+    ARRAYS = ('logW', 'logZ', 'nres', 'collapses', 'pend_anc', 'pend_hist', 'head', 'len')
+    DTYPES = dict(logW=torch.float64, logZ=torch.float64, nres=torch.int32, collapses=torch.int32, pend_anc=torch.int32,
+                  pend_hist=torch.uint8, head=torch.int32, len=torch.int32)
+
+    def __init__(self, gen, P, **arrays):
+        if not isinstance(gen, GenState):
+            raise ValueError("gen must be a GenState, got %r" % type(gen).__name__)
+        if isinstance(P, (bool, np.bool_)) or int(P) != P or not 1 <= P <= SMC_MAX_PARTICLES or gen.N % int(P):
+            raise ValueError("particles must be an integer in [1, %d] that divides the state's %d rows, got %r"
+                             % (SMC_MAX_PARTICLES, gen.N, P))
+        if set(arrays) != set(self.ARRAYS):
+            raise ValueError("a filter state holds %s, got %s" % (self.ARRAYS, tuple(sorted(arrays))))
+        self.gen, self.P = gen, int(P)
+        R, N = gen.N, gen.N // int(P)
+        cap = int(arrays['pend_anc'].shape[0]) if arrays['pend_anc'].dim() == 2 else 0
+        D = int(arrays['pend_hist'].shape[2]) if arrays['pend_hist'].dim() == 3 else 0
+        shapes = dict(logW=(R,), logZ=(N,), nres=(N,), collapses=(N,), pend_anc=(cap, R), pend_hist=(cap, R, D), head=(N,),
+                      len=(N,))
+        for k in self.ARRAYS:
+            v = arrays[k]
+            if not isinstance(v, torch.Tensor) or v.dtype != self.DTYPES[k] or tuple(v.shape) != shapes[k] or cap < 1 \
+                    or D < 1 or v.device != gen.device:
+                raise ValueError("%s must be a %s tensor of shape %s on the state's device" % (k, self.DTYPES[k], shapes[k]))
+            setattr(self, k, v.contiguous())
+
+    @classmethod
+    def fresh(cls, gen, P, D, cap, logW, logZ, nres):
+        """the state after a stream's first chunk, before its commit: nothing pending, no collapse"""
+        N, d = gen.N // P, gen.device
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=d)
+        return cls(gen, P, logW=logW, logZ=logZ, nres=nres, collapses=i32(N), pend_anc=i32(cap, gen.N),
+                   pend_hist=torch.zeros(cap, gen.N, D, dtype=torch.uint8, device=d), head=i32(N), len=i32(N))
+
+    kind = property(lambda self: self.gen.kind)
+    t = property(lambda self: self.gen.t)
+    R = property(lambda self: self.gen.N)
+    N = property(lambda self: self.gen.N // self.P)
+    D = property(lambda self: int(self.pend_hist.shape[2]))
+    cap = property(lambda self: int(self.pend_anc.shape[0]))
+    device = property(lambda self: self.gen.device)
+
+    def pending(self):
+        """the pending frames per melody, [N] int64 on the host (one small copy, which waits for the device)"""
+        return self.len.cpu().numpy().astype(np.int64)
+
+    def buffers(self):
+        """the rows' state as contiguous fp32 [R, width] buffers (what clv_smc_gather permutes)"""
+        g = self.gen
+        return [g.rows.view(g.N, -1)] if g.rows is not None else [g[k] for k in STATE_FIELDS[g.kind]]
+
+    def reserve(self, need):
+        """make the ring hold `need` steps per melody: a larger store, every melody's live steps from slot 0 on"""
+        cap, N, P, D = self.cap, self.N, self.P, self.D
+        if need <= cap:
+            return
+        new = max(int(need), 2 * cap)
+        slot = ((self.head.to(torch.int64)[None, :] + torch.arange(new, device=self.device)[:, None]) % cap)   # [new, N]
+        m = torch.arange(N, device=self.device)[None, :]
+        self.pend_anc = self.pend_anc.view(cap, N, P)[slot, m].reshape(new, N * P).contiguous()
+        self.pend_hist = self.pend_hist.view(cap, N, P * D)[slot, m].reshape(new, N * P, D).contiguous()
+        self.head = torch.zeros_like(self.head)
+
+    def clone(self):
+        return FilterState(self.gen.clone(), self.P, **{k: getattr(self, k).clone() for k in self.ARRAYS})
+
+    def to_numpy(self):
+        """a dict of arrays that np.savez can hold: the GenState's (to_numpy), particles, and the arrays above"""
+        out = self.gen.to_numpy()
+        out['particles'] = np.asarray(self.P, np.int64)
+        out.update({k: getattr(self, k).detach().cpu().numpy().copy() for k in self.ARRAYS})
+        return out
+
+    @classmethod
+    def from_numpy(cls, d, device):
+        """the state of to_numpy() (or of np.load of its np.savez) on `device`"""
+        keys = set(d.keys() if hasattr(d, 'keys') else d)
+        if not set(cls.ARRAYS) | {'particles', 't'} <= keys:
+            raise ValueError("not a filter state: fields %s" % (tuple(sorted(keys)),))
+        gen = GenState.from_numpy({k: d[k] for k in keys - set(cls.ARRAYS) - {'particles'}}, device)
+        arrays = {k: torch.as_tensor(np.ascontiguousarray(np.asarray(d[k])), device=device).to(cls.DTYPES[k])
+                  for k in cls.ARRAYS}
+        return cls(gen, int(np.asarray(d['particles']).reshape(())), **arrays)
+
+
+def chunk_frames(clamp):
+    """the number of frames a chunk's constraints cover: row count of its roll, else of its voice-count array"""
+    parts = (clamp.roll, clamp.voices) if isinstance(clamp, Constraints) else (clamp,)
+    for a in parts:
+        if a is not None and not isinstance(a, tuple):
+            shape = tuple(a.shape) if isinstance(a, torch.Tensor) else np.asarray(a).shape
+            if len(shape) != 3 or shape[1] < 1:
+                raise ValueError("a chunk's constraints are [N, n, ...] with n >= 1 frames, got shape %s" % (shape,))
+            return int(shape[1])
+    raise ValueError("a filter stream's chunk needs a constraint roll, or voice counts given as an array [N, n, 2]")
+
+
 def generate_samples_numpy(engine, x_seeds, nsteps, w_vals=None, seed=0, z_prior=False, clamp=None, particles=None,
                            resample_threshold=0.5, return_evidence=False, w_prior=None, return_key=False, temperature=1.0,
                            z_temperature=1.0, state=None, return_state=False, kind=None, sweeps=None, return_renewed=False):
@@ -855,6 +959,29 @@ class _GibbsSmc(_Smc):
                                self.bridge_rows, path.x, path.z, path.b, renewed)
 
 
+class _StreamSmc(_Smc):
+    """One chunk of a filter stream: the filter whose resampling uniforms count their Philox step on from
+    t0 and which, given the FilterState of the chunks before, continues its logW, logZ and nres (in place)."""
+
+    def __init__(self, G, P, nsteps, S, D, tau, seed, clamp, device, t0=0, state=None):
+        super().__init__(G, P, nsteps, S, D, tau, seed, 0, clamp, device)
+        self.t0, self.carry = int(t0), state is not None
+        if state is not None:
+            self.logW, self.logZ, self.nres = state.logW, state.logZ, state.nres
+
+    def step(self, xhat, u, counter, x_next, gather):
+        self.sample(xhat, u, counter, x_next)
+        ops.smc_resample_carry(self.G, self.P, self.nsteps, self.S, self.seed, self.m0, self.tau, self.ell, self.logW,
+                               self.logZ, self.ess, self.nres, self.flag, self.anc, counter, self.t0, self.carry)
+        gather(self.anc, self.flag, counter)
+
+
+FilterEmit = namedtuple('FilterEmit', 'state frames counts ess picks')
+FilterEmit.__doc__ = """What a filter stream's call hands out (DESIGN.md 23): the FilterState to go on from; frames [N, max count, D]
+uint8 (device), of which row j < counts[m] of melody m is valid, oldest first; counts [N] int64 (host); ess [N, n] fp64 of
+an advance's frames (else None); picks [N] int64 (host) the particle a collapse or the finish drew, -1 where none."""
+
+
 def _smc_chunks(N, P, cap, chunk):
     """melody ranges [m0, m1): at most `chunk` melodies (default: all) and at most cap rows (None: no cap) per chunk"""
     g = N if chunk is None else int(chunk)
@@ -1053,7 +1180,8 @@ class _Chain:
 
 
 class _Generate:
-    """vary, decode_latents, generate_smc and generate_gibbs of both families, each written once.  What differs a family states itself
+    """vary, decode_latents, generate_smc, generate_gibbs and the filter stream (filter_advance, filter_collapse) of both
+    families, each written once.  What differs a family states itself
     (VaeGenerate, VrnnGenerate below) and the bodies here only ask for it:
     STATE_KIND                  its key in STATE_FIELDS, SEED_RANK, LSTM_FIELDS
     ROWS                        the rows of a frame chain: _VaeRows (at most the batch size) / _VrnnRows (any number)
@@ -1062,6 +1190,8 @@ class _Generate:
     _check_frames(**frames)     cl_vae reads frames as on / off: binary_frames; cl_vrnn takes any float: nothing
     _vary_fits(clamp, T, zout)  does a re-decoding fit the persistent kernel's 32-bit addressing
     _smc_seed(xs), _smc_cap()   how the filter's chain holds its seed rows xs; the most rows of a chunk (None: any)
+    _filter_start(rows, xs, gen), _filter_read(rows, chain, t)   a filter stream's chain from seed rows or a carried
+                                GenState, and the GenState its rows end on
     _vary_op, _decode_op        ops.vae_* / ops.vrnn_*: vary (with or without a zout) and decode
     _weights(encoder=True)      the weight arguments of those, in their order
     Every refusal (ValueError) comes before the first launch and before anything of the engine but cfg and device is read."""
@@ -1229,6 +1359,110 @@ class _Generate:
             out.z[m0:m1].copy_(path.z)
         return out
 
+    def filter_advance(self, state, x_seed, w, clamp_chunk, particles, resample_threshold=0.5, seed=0, z_prior=False,
+                       temperature=1.0, z_temperature=1.0, use_graph=True):
+        """The next n frames of a filter stream: generate_smc's filter stopped after any frame and continued.
+        state None starts the stream on x_seed (cl_vrnn [N, S, D]: the S seed frames and the bridge are teacher-forced,
+        unweighted, as in generate_smc; cl_vae [N, D]); a FilterState continues it (x_seed None; the state is consumed).
+        w [N, C]; clamp_chunk: the roll uint8 [N, n, D] of these frames, or a Constraints with voice counts for them; n is
+        its length.  Runs n filter steps with the launches of generate_smc -- the Philox step of local frame c is t + c for
+        the eps and u of the chain and for the resampling uniform; logW, logZ and nres continue -- and then commits: per
+        melody the frames of the longest prefix of its pending steps through which every surviving lineage passes by one
+        row are final, are returned and leave the pending store.  However a piece is cut into chunks, the rows' states,
+        logW, logZ, ess, the ancestors and the frames are those of one generate_smc call, bit for bit.  Every melody's
+        N * P rows run together: cl_vae needs N * P <= the batch size (ValueError).  Returns FilterEmit."""
+        cfg, d, kind = self.cfg, self.device, self.STATE_KIND
+        D = cfg['D']
+        temper = temper_args(temperature, z_temperature)
+        if (state is None) == (x_seed is None):
+            raise ValueError("give x_seed to start a filter stream or a FilterState to continue one, not both")
+        w = device_f32(w, d)
+        if w.dim() != 2 or w.shape[0] < 1 or w.shape[1] != cfg['C']:
+            raise ValueError("w must be [N, %d] with N >= 1, got shape %s" % (cfg['C'], tuple(w.shape)))
+        N, n = int(w.shape[0]), chunk_frames(clamp_chunk)
+        clamp = smc_args(clamp_chunk, particles, resample_threshold, 1, N, n, D, d)
+        P, tau = int(particles), float(resample_threshold)
+        R = N * P
+        if self._smc_cap() is not None and R > self._smc_cap():
+            raise ValueError("%d melodies x %d particles exceed the engine's batch size %d: a filter stream runs all of "
+                             "its rows together" % (N, P, self._smc_cap()))
+        if state is None:
+            xs = device_f32(x_seed, d)
+            if xs.dim() != SEED_RANK[kind] or xs.shape[0] != N or xs.shape[-1] != D:
+                raise ValueError("x_seed must be %s, got shape %s" % ("[%d, S, %d]" % (N, D) if SEED_RANK[kind] == 3 else
+                                                                     "[%d, %d]" % (N, D), tuple(xs.shape)))
+            S, t0 = seed_steps(kind, xs), resume_args(None, kind, None, None, seed_steps(kind, xs) + n)
+            xs = xs.repeat_interleave(P, 0)
+        else:
+            if not isinstance(state, FilterState):
+                raise ValueError("state must be a FilterState, got %r" % type(state).__name__)
+            if state.P != P or state.D != D:
+                raise ValueError("the state holds %d particles of %d notes, the call %d of %d" % (state.P, state.D, P, D))
+            S, xs, t0 = 0, None, resume_args(state.gen, kind, R, state_widths(kind, cfg), n)
+        wr = w.repeat_interleave(P, 0).contiguous()
+        smc = _StreamSmc(N, P, n, S, D, tau, seed, clamp, d, t0=t0, state=state)
+        rows = self.ROWS(self, R)
+        chain = _Chain(rows, wr, wr, n, seed, temper, z_prior=z_prior, smc=smc, t0=t0,
+                       **self._filter_start(rows, xs, None if state is None else state.gen))
+        chain.run(S + n, use_graph)
+        gen = self._filter_read(rows, chain, t0 + S + n)
+        if state is None:
+            state, longest = FilterState.fresh(gen, P, D, n, smc.logW, smc.logZ, smc.nres), 0
+        else:
+            state.gen, longest = gen, int(state.pending().max())
+        room = longest + n
+        state.reserve(room)
+        frames = torch.zeros(N, room, D, dtype=torch.uint8, device=d)
+        ncommit = torch.zeros(N, dtype=torch.int32, device=d)
+        ops.smc_commit(N, P, D, n, smc.anc, smc.hist, state.cap, state.pend_anc, state.pend_hist, state.head, state.len, room,
+                       ncommit, frames)
+        counts = ncommit.cpu().numpy().astype(np.int64)
+        if counts.min() < 0:
+            raise RuntimeError("clv_smc_commit: the pending store of melody %d is inconsistent" % int(counts.argmin()))
+        return FilterEmit(state, frames[:, :int(counts.max())], counts, smc.ess, np.full(N, -1, np.int64))
+
+    def filter_collapse(self, state, index=None, seed=0, final=False):
+        """Force the issue for the melodies `index` (None: all) of a filter stream: draw one particle per
+        melody from the current weights -- by systematic_pick with n = 1 and a Philox uniform of stream
+        trainer.COLLAPSE_STREAM at step state.t, index m --, return its whole pending lineage, make all P rows of the melody
+        copies of that particle (clv_smc_gather fed the pick as every row's ancestor), set logW = -log P and empty the
+        melody's pending store; logZ stays (after a collapse it is no longer the unbiased estimate), collapses[m] counts.
+        final=True is the stream's end instead: the draw of clv_smc_backtrack with n_out = 1 (SMC_STREAM, step state.t), for
+        every melody, and nothing of the state changes.  The state is consumed.  Returns FilterEmit (ess None)."""
+        if not isinstance(state, FilterState):
+            raise ValueError("state must be a FilterState, got %r" % type(state).__name__)
+        N, P, D, d = state.N, state.P, state.D, state.device
+        which = np.ones(N, bool)
+        if index is not None:
+            if final:
+                raise ValueError("the final draw takes every melody")
+            idx = np.asarray(index)
+            if idx.dtype == np.bool_ and idx.shape == (N,):
+                which = idx.copy()
+            elif idx.ndim == 1 and np.issubdtype(idx.dtype, np.integer) and (not idx.size or (idx.min() >= 0 and idx.max() < N)):
+                which = np.zeros(N, bool)
+                which[idx] = True
+            else:
+                raise ValueError("index must be melodies in [0, %d) or a boolean mask [%d], got %r" % (N, N, index))
+        lens = state.pending()
+        room = max(int(lens.max()), 1)
+        i32 = dict(dtype=torch.int32, device=d)
+        pick_of = torch.as_tensor(which.astype(np.int32), device=d)
+        picks, flag = torch.full((N,), -1, **i32), torch.zeros(N, **i32)
+        anc_row = torch.arange(N * P, **i32)
+        frames = torch.zeros(N, room, D, dtype=torch.uint8, device=d)
+        ops.smc_collapse(N, P, D, seed, 0, state.t, final, pick_of, state.logW, state.cap, state.pend_anc, state.pend_hist,
+                         state.head, state.len, room, picks, frames, anc_row, flag)
+        if not final:
+            ops.SmcGather(N * P, P, 1, 0, state.buffers())(anc_row.view(1, -1), flag, torch.zeros(1, **i32))
+            state.collapses += flag
+        picks = picks.cpu().numpy().astype(np.int64)
+        if (picks[which] < 0).any():
+            raise RuntimeError("clv_smc_collapse: the pending store of melody %d is inconsistent"
+                               % int(np.nonzero(which & (picks < 0))[0][0]))
+        counts = np.where(which, lens, 0)
+        return FilterEmit(state, frames[:, :int(counts.max())], counts, None, picks)
+
 
 class VaeGenerate(_Generate):
     STATE_KIND = 'cl_vae'
@@ -1252,6 +1486,13 @@ class VaeGenerate(_Generate):
 
     def _smc_cap(self):
         return self.B
+
+    def _filter_start(self, rows, xs, gen):
+        """a filter stream's chain arguments: from the seed rows xs as generate_smc's, or from a state's last two frames"""
+        return self._smc_seed(xs) if gen is None else dict(dec_prev='enc_input', x_enc=gen.x_in.clone(), x_dec=gen.hist.clone())
+
+    def _filter_read(self, rows, chain, t):
+        return GenState('cl_vae', None, t, rows=torch.stack([chain.x_enc, chain.x_dec], 1).contiguous())._sampled()
 
     def _weights(self, encoder=True):
         """the persistent kernels' weight arguments in the order ops.vae_* take them: the encoder half (vae_decode takes
@@ -1353,6 +1594,20 @@ class VrnnGenerate(_Generate):
 
     def _smc_cap(self):
         return None
+
+    def _filter_start(self, rows, xs, gen):
+        """a filter stream's chain arguments: from the seed rows xs as generate_smc's, or the rows' LSTM states and the
+        shared frame slot from a state (no seed step then)"""
+        if gen is None:
+            return self._smc_seed(xs)
+        for k in LSTM_FIELDS['cl_vrnn']:
+            rows.st[k].copy_(gen[k])
+        return dict(dec_prev='shared', x_enc=gen.x.clone())
+
+    def _filter_read(self, rows, chain, t):
+        tensors = {k: rows.st[k].clone() for k in LSTM_FIELDS['cl_vrnn']}
+        tensors['x'] = chain.x_enc.clone()
+        return GenState('cl_vrnn', tensors, t)
 
     # -- stateful single-step inference (the reference's stateful batch-1 sub-models,
     #    cl_vrnn/model.py:116-162; here for any batch of independent sequences) -------------

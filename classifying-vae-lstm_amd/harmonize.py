@@ -131,6 +131,68 @@ def harmonize(model, seeds, source_rolls, w_vals=None, voice='top', seed=0, fenc
                                    resample_threshold=resample_threshold, return_evidence=return_evidence, **extra)
 
 
+class Accompaniment:
+    """accompany()'s object: feed(source_chunk) harmonizes the next frames of the melodies, finish() ends the piece; .stream
+    is the stream.FilterStream underneath (emitted, pending, log_evidence, ess, collapses, collapse())."""
+
+    def __init__(self, stream, voice, fence, voices):
+        self.stream, self.voice, self.fence, self.voices = stream, voice, fence, voices
+
+    def feed(self, source_chunk, temperature=1.0, z_temperature=1.0):
+        """source_chunk [N, n, 88]: the next n >= 1 frames of the pieces whose voice is kept.  Returns (frames, counts) as
+        FilterStream.advance: the harmonized frames that became final."""
+        src = np.asarray(source_chunk)
+        if src.ndim != 3 or src.shape[0] != self.stream.N or src.shape[1] < 1:
+            raise ValueError("source_chunk must be [%d, n, 88] with n >= 1, got shape %s" % (self.stream.N, src.shape))
+        clamp = voice_constraints(src, self.voice, self.fence)
+        if self.voices is not None:
+            clamp = voice_counts(self.voices, src, clamp)
+        return self.stream.advance(clamp, temperature=temperature, z_temperature=z_temperature)
+
+    def finish(self):
+        return self.stream.finish()
+
+    emitted = property(lambda self: self.stream.emitted)
+    pending = property(lambda self: self.stream.pending)
+    log_evidence = property(lambda self: self.stream.log_evidence)
+    collapses = property(lambda self: self.stream.collapses)
+
+
+def accompany(model, seeds, w_vals, voice='top', particles=64, fence=True, voices=None, **stream_kw):
+    """harmonize(particles=P) for melodies that arrive a chunk at a time: returns an Accompaniment whose
+    feed(source_chunk) builds the chunk's constraints as harmonize does (voice_constraints, and voice_counts under
+    `voices`) and advances a stream.FilterStream by them, returning the frames that are final; finish() returns the rest.
+    All of them together are harmonize(model, seeds, the whole source, w_vals, particles=P)'s frames, bit for bit, unless
+    max_lag forces frames out early.  stream_kw: FilterStream's seed, resample_threshold, z_prior, max_lag."""
+    from .stream import FilterStream
+    if voice not in VOICES:
+        raise ValueError("voice must be one of %s, got %r" % (VOICES, voice))
+    if w_vals is None:
+        raise ValueError("accompany needs w_vals: a filter stream carries no key per particle")
+    return Accompaniment(FilterStream(model, seeds, w_vals, particles, **stream_kw), voice, fence, voices)
+
+
+def live_harmonize(acc, source_rolls, chunk, **temper):
+    """the sample CLIs' --live: source_rolls [N, nsteps, 88] fed to the Accompaniment `chunk` frames at a time, a line
+    printed per chunk, then finish().  Returns (frames [N, nsteps, 88] float64, log_evidence [N]) like
+    harmonize(particles=P, return_evidence=True)."""
+    source_rolls = np.asarray(source_rolls)
+    nsteps = source_rolls.shape[1]
+    for i, a in enumerate(range(0, nsteps, int(chunk))):
+        b = min(nsteps, a + int(chunk))
+        _, counts = acc.feed(source_rolls[:, a:b], **temper)
+        print_live(i, a, b, counts, acc.pending)
+    _, counts = acc.finish()
+    print('live finish: emitted %s' % ' '.join(str(int(c)) for c in counts))
+    return np.stack(acc.emitted), acc.log_evidence
+
+
+def print_live(chunk, first, last, counts, pending):
+    """one line per fed chunk (the sample CLIs' --live): what went out and what is still held back, per sample"""
+    print('live chunk %d (frames %d..%d): emitted %s pending %s' % (chunk, first, last - 1, ' '.join(str(int(c)) for c in counts),
+                                                                   ' '.join(str(int(p)) for p in pending)))
+
+
 def print_evidence(names, log_evidence, nsteps):
     """one line per harmonization: log p(voice | seed, w) per frame (the sample CLIs' --particles)"""
     for name, le in zip(names, np.asarray(log_evidence, dtype=np.float64)):

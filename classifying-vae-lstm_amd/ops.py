@@ -830,6 +830,33 @@ def smc_resample(G, P, nsteps, S, seed, m0, tau, ell, logW, logZ, ess, nres, fla
           "clv_smc_resample")
 
 
+def smc_resample_carry(G, P, nsteps, S, seed, m0, tau, ell, logW, logZ, ess, nres, flag, anc, step_dev, t0, carry):
+    """smc_resample of a filter stream: the resampling uniform's Philox step is t0 + *step_dev, and with
+    carry step 0 continues logW, logZ and nres instead of starting them.  t0 = 0, carry = False: smc_resample."""
+    check(_lib.lib().clv_smc_resample_carry(G, P, nsteps, S, int(seed), int(m0), float(tau), _ptr(ell), _ptr(logW),
+                                            _ptr(logZ), _ptr(ess), _ptr(nres), _ptr(flag), _ptr(anc), _ptr(step_dev),
+                                            int(t0), int(bool(carry)), _stream()), "clv_smc_resample_carry")
+
+
+def smc_commit(G, P, D, n, anc, hist, cap, pend_anc, pend_hist, head, length, out_cap, ncommit, out):
+    """after a chunk of n filter steps (anc [n, G*P] int32, hist [n, G*P, D] uint8): per melody the prefix of its pending
+    steps -- the ring pend_anc [cap, G*P], pend_hist [cap, G*P, D], head, length [G] int32, then the chunk -- through which
+    all P lineages pass by one row goes to out [G, out_cap, D] uint8 and leaves the ring, ncommit [G] int32 frames; the
+    rest of the chunk joins the ring.  The caller keeps length + n <= min(cap, out_cap) (else ncommit = -1)."""
+    check(_lib.lib().clv_smc_commit(G, P, D, n, _ptr(anc), _ptr(hist), int(cap), _ptr(pend_anc), _ptr(pend_hist), _ptr(head),
+                                    _ptr(length), int(out_cap), _ptr(ncommit), _ptr(out), _stream()), "clv_smc_commit")
+
+
+def smc_collapse(G, P, D, seed, m0, step, final, pick_of, logW, cap, pend_anc, pend_hist, head, length, out_cap, picks, out,
+                 anc_row=None, flag=None):
+    """per melody with pick_of != 0 (None: all): picks [G] int32 = one particle drawn from logW (Philox stream 0xFFFFFFF8,
+    step `step`, index m0 + m), its pending lineage to out [G, out_cap, D] uint8, anc_row [G*P] / flag [G] for SmcGather,
+    logW = -log P, length = 0.  final: the terminal draw of smc_backtrack (its stream); only picks and out are written."""
+    check(_lib.lib().clv_smc_collapse(G, P, D, int(seed), int(m0), int(step), int(bool(final)), _ptr(pick_of), _ptr(logW),
+                                      int(cap), _ptr(pend_anc), _ptr(pend_hist), _ptr(head), _ptr(length), int(out_cap),
+                                      _ptr(picks), _ptr(out), _ptr(anc_row), _ptr(flag), _stream()), "clv_smc_collapse")
+
+
 class SmcGather:
     """clv_smc_gather over a fixed list of fp32 [R, width] buffers: the pointer list lives on the host (the launch copies
     it into its arguments, so a captured graph keeps it) and the scratch buffer is allocated once."""

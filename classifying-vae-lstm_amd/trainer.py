@@ -42,6 +42,10 @@ GIBBS_STREAM = 0xFFFFFFFA
 # and, for the uniform that picks a training window's transposition (augment.py; step = the optimizer's
 # `iterations`, index = GLOBAL batch row; drawn inside csrc/transpose_aug.hip), the one below that:
 TRANSPOSE_STREAM = 0xFFFFFFF9
+# and, for the uniform that picks the particle a filter stream collapses a melody onto (stream.FilterStream.collapse,
+# DESIGN.md 23; step = the Philox step of the stream's next frame, index = GLOBAL melody; drawn inside csrc/smc.hip) -- not
+# SMC_STREAM, whose uniform of that step belongs to the next frame's resampling --, the one below that:
+COLLAPSE_STREAM = 0xFFFFFFF8
 
 
 class DevWindows:

@@ -142,7 +142,9 @@ typedef struct clv_frame_proj {
  *        launched
  *        (still 600: + clv_splitk_reduce_multi_outer / _supported, an addition; no existing entry point changed)
  *   610  sampling follows the 600 rule: _clamped / _tempered / _resume took over clv_*_generate, _vary_latents took over
- *        clv_*_vary */
+ *        clv_*_vary
+ *        (still 610: + clv_smc_resample_carry / clv_smc_commit / clv_smc_collapse, the filter stream's additions; no existing
+ *        entry point changed) */
 #define CLV_ABI_VERSION 610
 int clv_version(void);
 /* number of visible HIP devices whose arch is gfx950 (0 => the product must fail loudly) */
@@ -1074,6 +1076,42 @@ int clv_smc_resample_conditional(int G, int P, int nsteps, int S, uint64_t seed,
 int clv_smc_backtrack_path(int G, int P, int nsteps, int S, int D, int L, const int32_t* picks, const int32_t* anc,
                            const uint8_t* hist, const float* zhist, const float* bridge_rows, uint8_t* x_ref, float* z_ref,
                            float* bridge_ref, uint8_t* renewed, void* stream);
+
+/* ------------------------------------------------- a filter stream (the filter a chunk at a time) --
+ * The filter above stopped after any frame and continued.  Between calls the caller keeps the rows' sampler
+ * state, logW, logZ, nres, the Philox step t of the next frame and the PENDING STORE: the steps whose frames are not
+ * handed out yet, per melody in a ring of cap slots -- pending step j of melody m (oldest first) lives in slot
+ * (head[m] + j) % cap of pend_anc [cap, R] int32 (each row's ancestor, a global row, as anc) and pend_hist [cap, R, D]
+ * uint8 (each row's frame before that step's resampling, as hist); len[m] steps are live; head, len [G] int32.
+ * clv_smc_resample_carry: clv_smc_resample with two more arguments.  The Philox step of the resampling uniform is
+ *   t0 + *step_dev; with carry != 0 step k = 0 reads logW, logZ and nres like every later step instead of starting them.
+ *   t0 = 0, carry = 0: clv_smc_resample, bit for bit.
+ * clv_smc_commit: after a chunk of n steps (its anc [n, R] and hist [n, R, D]): one workgroup per melody, P <= 1024,
+ *   thread p walking lineage p back through the chunk and then through the len[m] pending steps, a_j(p) =
+ *   anc_j[a_{j+1}(p)].  A step is coalesced when a_j is one row for all p; coalesced steps form a prefix and
+ *   ncommit[m] is its length.  out [G, out_cap, D] uint8 receives row j = hist_j[a_j] for j < ncommit[m] (later rows are
+ *   not written); the rest of the chunk is appended to the ring, head[m] advances by ncommit[m] and len[m] becomes
+ *   len[m] + n - ncommit[m].  The caller keeps len[m] + n <= min(cap, out_cap); a melody that breaks it (or holds a
+ *   head / len outside the ring) is left as it is with ncommit[m] = -1.
+ * clv_smc_collapse: per melody with pick_of[m] != 0 (pick_of NULL: every melody) one particle is drawn from logW as
+ *   clv_smc_backtrack draws with n_out = 1, u0 = Philox uniform (stream 0xFFFFFFF8, step `step`, index m0 + m);
+ *   picks[m] = that particle, out [G, out_cap, D] rows j < len[m] = its lineage through the pending steps; then
+ *   anc_row[m*P + p] = m*P + picks[m] for all p and flag[m] = 1 -- what clv_smc_gather(nsteps = 1, S = 0, a counter of 0)
+ *   takes to make the melody's rows copies of the picked one --, logW = -log P and len[m] = 0.  A melody with
+ *   pick_of[m] == 0 is not touched at all: none of its outputs is written.  final_pick != 0: the terminal draw, u0 from
+ *   stream 0xFFFFFFFD (clv_smc_backtrack's own at that step); only picks and out are written (anc_row, flag may be NULL).
+ *   A melody whose head / len lie outside the ring or whose len exceeds out_cap gets picks[m] = -1 and nothing else.
+ * No atomics, one owner per output element: bitwise reproducible.  CLV_EINVAL for a G, P, D, n, cap or out_cap of 0,
+ * P > 1024 and a NULL pointer other than the optional ones. */
+int clv_smc_resample_carry(int G, int P, int nsteps, int S, uint64_t seed, int64_t m0, double tau, const double* ell,
+                           double* logW, double* logZ, double* ess, int32_t* nres, int32_t* flag, int32_t* anc,
+                           const int32_t* step_dev, uint32_t t0, int carry, void* stream);
+int clv_smc_commit(int G, int P, int D, int n, const int32_t* anc, const uint8_t* hist, int cap, int32_t* pend_anc,
+                   uint8_t* pend_hist, int32_t* head, int32_t* len, int out_cap, int32_t* ncommit, uint8_t* out,
+                   void* stream);
+int clv_smc_collapse(int G, int P, int D, uint64_t seed, int64_t m0, uint32_t step, int final_pick, const int32_t* pick_of,
+                     double* logW, int cap, const int32_t* pend_anc, const uint8_t* pend_hist, const int32_t* head,
+                     int32_t* len, int out_cap, int32_t* picks, uint8_t* out, int32_t* anc_row, int32_t* flag, void* stream);
 
 /* --------------------------------------------------- voice-count constraints --
  * Sampling a frame given how many of its notes sound: the voices twins of clv_bernoulli_sample_clamped and
