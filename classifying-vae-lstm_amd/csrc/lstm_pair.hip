@@ -759,19 +759,33 @@ __device__ __forceinline__ void pair_bwd_chain(const PairBwdArgs& a, int wave, i
 
   auto matvec = [&](const float* dzs) {        // reduce-scattered: this lane's unit (or latent) total
     const float4* dp = reinterpret_cast<const float4*>(dzs + BW_CP * cs);
-    float dv[BW_CP];
+    f2 dv[BW_CP / 2];                    // the row slice as register PAIRS: (x, y) and (z, w) of every 16-byte read
 #pragma unroll
     for (int j = 0; j < BW_CP / 4; ++j) {
       float4 v;
       if (PAIR_ABL == 2) { asm volatile("; no read" : "=v"(v.x), "=v"(v.y), "=v"(v.z), "=v"(v.w)); }
-      else if (PAIR_ABL == 1 && j >= 3) { v = make_float4(dv[4 * (j - 3)], dv[4 * (j - 3) + 1], dv[4 * (j - 3) + 2], dv[4 * (j - 3) + 3]); }
+      else if (PAIR_ABL == 1 && j >= 3) { v = make_float4(dv[2 * (j - 3)][0], dv[2 * (j - 3)][1], dv[2 * (j - 3) + 1][0], dv[2 * (j - 3) + 1][1]); }
       else v = dp[j];
-      dv[4 * j] = v.x; dv[4 * j + 1] = v.y; dv[4 * j + 2] = v.z; dv[4 * j + 3] = v.w;
+      // The slice is consumed as broadcasts {x, x} into packed FMAs, which read one half of a register pair twice through
+      // op_sel.  Left to itself the compiler does that for x, y and z of every 16-byte read, but forms the w broadcast as
+      // a copy into the LOW register of a fresh pair whose high register is undefined: five copies per matvec, and the
+      // undefined half is still named by the instruction.  In the <G, 4, true> encoder chain it was the register rB.hh
+      // (a load requested one step earlier) is written to, so the wait insertion put vmcnt(0) in front of that FMA and
+      // drained the record set requested ahead in every second step.  The empty asm hands the compiler (x, y) and (z, w)
+      // as opaque 64-bit pairs, in place: w is then the high half of a pair like y, no copy, no undefined half
+      // (tools/pair_waits.py reads the compiled loops; DESIGN.md 8 item 6 iii).  The FMAs and their order are unchanged.
+      // Not `asm volatile`: a volatile asm orders the LDS reads between the statements, and the reads then come out
+      // interleaved with the FMAs, each behind its own wait (measured: the gain was gone, PERFLOG "Pair backward").
+      f2 lo = {v.x, v.y}, hi = {v.z, v.w};
+      if (4 * j < BW_CW) asm("" : "+v"(lo));
+      if (4 * j + 2 < BW_CW) asm("" : "+v"(hi));
+      dv[2 * j] = lo; dv[2 * j + 1] = hi;
     }
     f2 acc01 = {0.f, 0.f}, acc23 = {0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < BW_CW; ++c) {
-      const f2 dd = {dv[c], dv[c]};
+      const f2 p = dv[c >> 1];
+      const f2 dd = (c & 1) ? __builtin_shufflevector(p, p, 1, 1) : __builtin_shufflevector(p, p, 0, 0);
       acc01 = __builtin_elementwise_fma(dd, Ur[c][0], acc01);
       acc23 = __builtin_elementwise_fma(dd, Ur[c][1], acc23);
     }

@@ -702,11 +702,25 @@ __global__ __launch_bounds__(FAST_NT) void wn_fast_rescale_kernel(AdamFast f, fl
     for (int k = 0; k < 2; ++k) fpv[k] = *reinterpret_cast<const float4*>(ftile + 4 * (size_t)min(tid + FAST_NT * k, fn4 - 1));
   }
 #endif
+  // The walk over the partial rows (both bodies), in rounds of WALK loads requested together: the rows were written by the
+  // previous launch on other XCDs, so a load-wait-add loop of dynamic trip count pays one trip beyond this XCD's L2 per row
+  // (eleven in a row at configuration 3's 176 rows), and its first wait drains the tile rows above as well.  The loads are
+  // unconditional (row index clamped: the compiler can count them), a value beyond the range is replaced by +0.0f, and the
+  // adds stay in ascending k: sums of squares are never -0, so x + (+0) = x and the sums are bit for bit those of the plain
+  // loop (the argument of reduce_body.h's LO form).
+  constexpr int WALK = 12;
   float2 a = make_float2(0.f, 0.f);
   if (cx < n2)
-    for (int k = ry; k < f.nunits; k += 16) {
-      const float2 t = *reinterpret_cast<const float2*>(f.partC + (size_t)k * f.cols + 2 * cx);
-      a.x += t.x; a.y += t.y;
+    for (int k0 = ry; k0 < f.nunits; k0 += 16 * WALK) {
+      float2 t[WALK];
+#pragma unroll
+      for (int j = 0; j < WALK; ++j)
+        t[j] = *reinterpret_cast<const float2*>(f.partC + (size_t)min(k0 + 16 * j, f.nunits - 1) * f.cols + 2 * cx);
+#pragma unroll
+      for (int j = 0; j < WALK; ++j) {
+        const bool in = k0 + 16 * j < f.nunits;
+        a.x += in ? t[j].x : 0.f; a.y += in ? t[j].y : 0.f;
+      }
     }
   red[ry][cx] = a;
   __syncthreads();
