@@ -263,6 +263,8 @@ SIGNATURES = {
     "clv_key_track_smooth": (_i, [_i, _i, _p, _p, _p, _p, _d, _p, _p, _p, _p, _p]),
     "clv_roll_nearest_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "clv_roll_nearest": (_i, [_i] * 6 + [_i64] * 3 + [_p] * 7 + [_sz] + [_p] * 4),
+    "clv_roll_stats_column_count": (_i, [_i, _i]),
+    "clv_roll_stats": (_i, [_i] * 4 + [_i64] + [_p] * 5),
     "clv_bernoulli_sample": (_i, [_i64, _p, _p, _p, _p]),
     "clv_bernoulli_sample_clamped": (_i, [_i64, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "clv_dropout_rows": (_i, [_i, _i, _i, _p, _i, _p, _i, _f, _f, _p, _i, _p]),

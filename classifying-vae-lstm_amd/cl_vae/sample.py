@@ -9,8 +9,8 @@ if __package__ in (None, ''):
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vae import model as M  # noqa: E402
 from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, LIVE_FLAGS, MORPH_FLAGS, NOVELTY_FLAGS,  # noqa: E402
-                           RESUME_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, live_kwargs, morph_kwargs,
-                           novelty_check, parser_for, resume_kwargs, resuming, temperature_kwargs, voices_kwargs)
+                           RESUME_FLAGS, STATS_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, live_kwargs, morph_kwargs,
+                           novelty_check, parser_for, resume_kwargs, resuming, stats_check, temperature_kwargs, voices_kwargs)
 from clvae_amd.harmonize import (accompany, harmonize, live_harmonize, print_evidence, print_key_posterior,  # noqa: E402
                                  print_renewed, voice_constraints, voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
@@ -19,6 +19,7 @@ from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
 from clvae_amd.morph import morph  # noqa: E402
 from clvae_amd.novelty import audit_samples  # noqa: E402
+from clvae_amd import stats  # noqa: E402
 from clvae_amd.vary import vary  # noqa: E402
 
 
@@ -37,10 +38,12 @@ class Sampler:
         # --harmonize: windows of the seed frame and the t frames whose voice is kept
         self.data = PianoData(args.train_file, batch_size=1, seq_length=args.t + 1 if voice_of(args) else args.t,
                               squeeze_x=True)
+        self.keys = []          # --stats: the class every sample is generated under, None where no one label holds
 
     def pick_seed(self):
         """(first frame of a random test window, its key's one-hot or None with --infer_w); one np.random draw"""
         i = np.random.choice(range(len(self.data.x_test)))
+        self.keys.append(None if self.args.infer_w else int(self.data.test_song_keys[i]))
         w = None if self.args.infer_w else to_categorical(self.data.test_song_keys[i], self.margs['n_classes'])
         return self.data.x_test[i][0], w
 
@@ -57,6 +60,8 @@ class Sampler:
         if self.args.infer_w:
             ws = [M.sample_w(self.w_enc.predict(s[None, :]), add_noise=False) for s in seeds]
         resume = resume_kwargs(self.args, self.data.key_map, len(names), self.margs['n_classes'])
+        if getattr(self.args, 'modulate', None) is not None:
+            self.keys = None    # the label changes on the way
         if resume:              # --chunk / --modulate: the same call a chunk at a time
             rolls = generate_chunked(self.model, np.stack(seeds), self.args.t, np.vstack(ws), seed=getattr(self.args, 'seed', 0),
                                      z_prior=self.args.use_z_prior, **resume, **temperature_kwargs(self.args),
@@ -77,6 +82,8 @@ class Sampler:
         seeds, sources = np.stack([w[0] for w in wins]), np.stack([w[1:] for w in wins])
         particles = getattr(self.args, 'particles', None)
         infer_key = getattr(self.args, 'infer_key', None)
+        self.keys = (None if infer_key or self.args.infer_w or getattr(self.args, 'modulate', None) is not None
+                     else [int(self.data.test_song_keys[i]) for i in picks])
         if infer_key:           # --infer_key: the filter weighs the keys by the voice, a key per particle
             ws = None
             self.model.engine.cfg['w_log_var_prior'] = float(self.margs.get('w_log_var_prior', 0.0))
@@ -119,6 +126,8 @@ class Sampler:
         sources = np.stack([np.asarray(self.data.x_test[i]).reshape(self.args.t, -1) for i in picks])
         ws = None if self.args.infer_w else np.vstack([to_categorical(self.data.test_song_keys[i], self.margs['n_classes'])
                                                        for i in picks])
+        self.keys = (None if self.args.infer_w or getattr(self.args, 'to_key', None) is not None
+                     else [int(self.data.test_song_keys[i]) for i in picks])
         rolls = vary(self.model, sources, ws, to_key=getattr(self.args, 'to_key', None), key_map=self.data.key_map,
                      history=getattr(self.args, 'vary_history', 'own'), seed=getattr(self.args, 'seed', 0),
                      **temperature_kwargs(self.args), **count_clamp(self.args))
@@ -137,6 +146,7 @@ class Sampler:
             name_of = {idx: name for name, idx in self.data.key_map.items()}
             pool = pool[np.array([name_of[k] for k in self.data.test_song_keys]) == key]
         n = 2 * (len(names) // 2)
+        self.keys = None        # a mix of two labels
         if not n or not len(pool):
             return []
         picks = [np.random.choice(pool) for _ in range(n)]
@@ -194,6 +204,7 @@ def on_device(args):
 def sample(args):
     s = Sampler(args)
     novelty_check(args, s.margs['original_dim'])
+    stats_check(args, s.margs['original_dim'])
     names = ['%s_%d' % (args.run_name, i) for i in range(args.n)]
     if voice_of(args):
         rolls = s.harmonize_on_device(names)
@@ -204,6 +215,7 @@ def sample(args):
     else:
         rolls = s.many_on_device(names) if on_device(args) else [s.one(nm) for nm in names]
     audit_samples(rolls, args)          # --novelty: the rolls just written against the training songs
+    stats.audit_samples(rolls, args, keys=s.keys)       # --stats: their texture against the songs' 
     return rolls
 
 
@@ -214,4 +226,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vae.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + NOVELTY_FLAGS + LIVE_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + STATS_FLAGS + NOVELTY_FLAGS + LIVE_FLAGS).parse_args())

@@ -9,8 +9,8 @@ if __package__ in (None, ''):
 import clvae_amd  # noqa: E402,F401
 from clvae_amd.cl_vrnn import model as M  # noqa: E402
 from clvae_amd.cli import (DEVICE_LOOP_FLAGS, GIBBS_FLAGS, HARMONIZE_FLAGS, LIVE_FLAGS, MORPH_FLAGS, NOVELTY_FLAGS,  # noqa: E402
-                           RESUME_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, live_kwargs, morph_kwargs,
-                           novelty_check, parser_for, resume_kwargs, resuming, temperature_kwargs, voices_kwargs)
+                           RESUME_FLAGS, STATS_FLAGS, TEMPERATURE_FLAGS, VARY_FLAGS, VOICES_FLAGS, gibbs_kwargs, live_kwargs, morph_kwargs,
+                           novelty_check, parser_for, resume_kwargs, resuming, stats_check, temperature_kwargs, voices_kwargs)
 from clvae_amd.harmonize import (accompany, harmonize, live_harmonize, print_evidence, print_key_posterior,  # noqa: E402
                                  print_renewed, voice_constraints, voice_counts)
 from clvae_amd.stream import generate_chunked  # noqa: E402
@@ -19,6 +19,7 @@ from clvae_amd.utils.model_utils import to_categorical  # noqa: E402
 from clvae_amd.utils.pianoroll import PianoData  # noqa: E402
 from clvae_amd.morph import morph  # noqa: E402
 from clvae_amd.novelty import audit_samples  # noqa: E402
+from clvae_amd import stats  # noqa: E402
 from clvae_amd.vary import vary  # noqa: E402
 
 
@@ -32,11 +33,21 @@ def seed_windows(P, key, n):
     return picks[:n]
 
 
-def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None):
+def one_label(args):
+    """whether every sample is generated under the one label of its seed window: not with an inferred label, a label that
+    changes on the way (--modulate, --to_key) or a mix of two (--morph)"""
+    return not (args.infer_w or getattr(args, 'infer_key', None) or getattr(args, 'modulate', None) is not None
+                or getattr(args, 'to_key', None) is not None or getattr(args, 'morph', None) is not None)
+
+
+def gen_samples(P, dec_model, w_enc_model, z_enc_model, args, margs, model=None, keys_out=None):
     """Seed windows -> generated continuations; writes <run>_<j>.mid and the seed as <run><j>_seed_<i>.mid.
-    With `model` the frame loops of all seeds run together on the device (Philox noise)."""
+    With `model` the frame loops of all seeds run together on the device (Philox noise).  keys_out: a list that receives
+    the class every sample is generated under, where one label holds (--stats)."""
     half_speed = 'jsb' in args.train_file.lower()
     picks = seed_windows(P, args.c, args.n)
+    if keys_out is not None and one_label(args):
+        keys_out.extend(int(P.test_song_keys[i]) for i in picks)
     label_of = lambda i: None if args.infer_w else to_categorical(P.test_song_keys[i], margs['n_classes'])
     voice = getattr(args, 'harmonize', None)
     if voice:
@@ -182,8 +193,11 @@ def sample(args):
         temperature_kwargs(args)) or resuming(args) or (
         bool(getattr(args, 'device_loop', False)) and not getattr(args, 'host_loop', False))
     novelty_check(args, margs['original_dim'])
-    rolls = gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None)
+    stats_check(args, margs['original_dim'])
+    keys = []
+    rolls = gen_samples(P, dec, w_enc, z_enc, args, margs, model=model if on_device else None, keys_out=keys)
     audit_samples(rolls, args)          # --novelty: the rolls just written against the training songs
+    stats.audit_samples(rolls, args, keys=keys or None)         # --stats: their texture against the songs' 
     return rolls
 
 
@@ -194,4 +208,4 @@ def build_parser():
 if __name__ == '__main__':
     sample(parser_for('cl_vrnn.sample',
                       DEVICE_LOOP_FLAGS + HARMONIZE_FLAGS + TEMPERATURE_FLAGS + VARY_FLAGS + MORPH_FLAGS
-                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + NOVELTY_FLAGS + LIVE_FLAGS).parse_args())
+                      + RESUME_FLAGS + VOICES_FLAGS + GIBBS_FLAGS + STATS_FLAGS + NOVELTY_FLAGS + LIVE_FLAGS).parse_args())

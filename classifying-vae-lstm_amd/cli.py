@@ -224,6 +224,25 @@ def novelty_check(args, width):
                          % width)
 
 
+# roll statistics audit (not in the reference): the texture of the rolls a sampling tool writes against the songs'
+STATS_FLAGS = [
+    Flag(('--stats',), ON, None, "audit the samples' texture: per sample the histograms of pitch, scale degree, voices, "
+                                 'intervals, note lengths, change between frames, outer-voice steps and span (integer counts on '
+                                 "the device), compared with the training split's songs and, as a baseline, the test split's"),
+    Flag(('--stats_max_duration',), int, None, 'with --stats: note lengths are counted up to this many frames, longer notes '
+                                               'in the last bin (1..64, default 32)'),
+]
+STATS_MAX_DURATION = 32
+
+
+def stats_check(args, width):
+    """--stats compares 88-key rolls with the data set's songs: SystemExit for a model whose samples are not such rolls (as
+    novelty_check)"""
+    if getattr(args, 'stats', False) and int(width) != 88:
+        raise SystemExit("--stats compares 88-key rolls with the training songs: not for a model whose frames are %d wide"
+                         % width)
+
+
 def gibbs_kwargs(args):
     """--sweeps as keyword arguments of harmonize: empty without the flag (also for parsers without it)"""
     k = getattr(args, 'sweeps', None)
@@ -308,7 +327,8 @@ class _Parser(argparse.ArgumentParser):
     --harmonize or --host_loop, --to_key / --vary_history only with --vary, --morph >= 1 and not with --harmonize, --vary or
     --host_loop, --chunk >= 1 and a well-formed --modulate, neither with --particles, --vary, --morph or --host_loop, a
     well-formed --voices LO[:HI] and not with --host_loop, --live >= 1 only with --particles and not with --sweeps,
-    --infer_key, --chunk, --modulate, --vary, --morph or --host_loop, --max_lag >= 0 only with --live, --novelty >= 1, --novelty_transpose in 0..12 and only with --novelty"""
+    --infer_key, --chunk, --modulate, --vary, --morph or --host_loop, --max_lag >= 0 only with --live, --novelty >= 1, --novelty_transpose in 0..12 and only with --novelty,
+    --stats_max_duration in 1..64 and only with --stats (without the flag it is 32)"""
 
     def parse_known_args(self, args=None, namespace=None):
         ns, rest = super().parse_known_args(args, namespace)
@@ -392,6 +412,13 @@ class _Parser(argparse.ArgumentParser):
             self.error('--novelty_transpose must be in 0..12')
         if novelty is None and getattr(ns, 'novelty_transpose', 0):
             self.error('--novelty_transpose needs --novelty')
+        if hasattr(ns, 'stats_max_duration'):
+            lmax = ns.stats_max_duration
+            if lmax is not None and not getattr(ns, 'stats', False):
+                self.error('--stats_max_duration needs --stats')
+            if lmax is not None and not 1 <= lmax <= 64:
+                self.error('--stats_max_duration must be in 1..64')
+            ns.stats_max_duration = STATS_MAX_DURATION if lmax is None else lmax
         temper = temperature_kwargs(ns)
         if temper:
             from .engine_generate import temper_args

@@ -977,6 +977,26 @@ def roll_nearest(Nq, Nc, W, hop, S, D, Fq, Fc, Wq, q_roll, q_off, c_roll, c_off,
     return workspace
 
 
+def roll_stats_columns(D, Lmax):
+    """S, the columns of one piece's row of roll_stats' table (clv_roll_stats_column_count); 0 for D outside 1..116 or Lmax
+    outside 1..64"""
+    return int(_lib.lib().clv_roll_stats_column_count(int(D), int(Lmax)))
+
+
+def roll_stats(N, D, Lmax, low, F, roll, off, tonic, table):
+    """the texture histograms of N pieces (clv_roll_stats): roll [>= F, D] uint8, any non-zero byte a sounding
+    note; off [N+1] int64 on the device, off[0] = 0, off[N] = F; tonic [N] int32 (0..11, -1: unknown, counted as 0) or
+    None; low the MIDI number of note 0; table [>= N, roll_stats_columns(D, Lmax)] int64 is overwritten with the sections
+    pitch, degree, voices, interval, duration, change, top_step, bottom_step, span of every piece."""
+    N, F = int(N), int(F)
+    S = roll_stats_columns(D, Lmax)
+    if F > (roll.shape[0] if roll is not None else 0) or off.numel() < N + 1 or table.numel() < N * S \
+            or (tonic is not None and tonic.numel() < N):
+        raise _lib.ClvError("roll_stats: N or F name more rows than the tensors hold")
+    check(_lib.lib().clv_roll_stats(N, int(D), int(Lmax), int(low), F, _ptr(roll), _ptr(off), _ptr(tonic), _ptr(table),
+                                    _stream()), "clv_roll_stats")
+
+
 class Graph:
     """Capture the kernels enqueued inside the ``with`` block on the current stream; replay with launch()."""
 

@@ -144,7 +144,8 @@ typedef struct clv_frame_proj {
  *   610  sampling follows the 600 rule: _clamped / _tempered / _resume took over clv_*_generate, _vary_latents took over
  *        clv_*_vary
  *        (still 610: + clv_smc_resample_carry / clv_smc_commit / clv_smc_collapse, the filter stream's additions; no existing
- *        entry point changed) */
+ *        entry point changed)
+ *        (still 610: + clv_roll_stats / clv_roll_stats_column_count, the roll statistics audit; no existing entry point changed) */
 #define CLV_ABI_VERSION 610
 int clv_version(void);
 /* number of visible HIP devices whose arch is gfx950 (0 => the product must fail loudly) */
@@ -1201,6 +1202,41 @@ int clv_roll_nearest(int Nq, int Nc, int W, int hop, int S, int D, int64_t Fq, i
                      const uint8_t* q_roll, const int64_t* q_off, const uint8_t* c_roll, const int64_t* c_off,
                      const int64_t* qwin_off, const int32_t* exclude, void* workspace, size_t workspace_bytes,
                      int32_t* dist, int32_t* shift, int64_t* cframe, void* stream);
+
+/* --------------------------------------------------------- roll statistics --
+ * The texture of a batch of pieces as integer histograms, one row per piece: does a sample look like the
+ * corpus?
+ *
+ * clv_roll_stats.  roll [F, D] is a uint8 roll in the novelty audit's layout (any non-zero byte: the note sounds), the
+ * pieces one after another; off [N+1] (device int64) holds the first frame of every piece, off[0] = 0, nondecreasing,
+ * off[N] = F; tonic [N] (device int32, or NULL: all 0) the pitch class 0..11 of every piece's key, -1 (or any other value
+ * outside 0..11) for unknown, which counts as 0; low is the MIDI number of note 0 (21 for this project's rolls).
+ * table [N, S] int64, S = clv_roll_stats_column_count(D, Lmax), is OVERWRITTEN, never accumulated into.  With f_0 .. f_{P-1}
+ * the frames of piece n as sets of notes, V = CLV_STATS_VOICES, C = CLV_STATS_CHANGE, M = CLV_STATS_STEP, row n holds these
+ * sections in this order:
+ *   pitch        D      frames in which note d sounds
+ *   degree       12     sounding cells by (d + low - tonic_n) mod 12; with tonic 0 the pitch class, C = 0
+ *   voices       V+1    frames by min(|f_t|, V); bin 0 counts the empty frames
+ *   interval     D      bin k >= 1: pairs of notes k semitones apart that sound in the same frame; bin 0 stays 0
+ *   duration     Lmax   notes by length: a note is a maximal run of consecutive frames OF THIS PIECE in which note d sounds,
+ *                       bin min(len, Lmax) - 1; a run cut by the piece's end counts with the length it has
+ *   change       C+1    for t >= 1: min(|f_t xor f_{t-1}|, C); P - 1 entries for a piece of P >= 1 frames
+ *   top_step     2M+1   for t >= 1 with f_t and f_{t-1} both non-empty: the highest note of f_t minus the highest of f_{t-1},
+ *                       clamped to -M .. M, bin = step + M
+ *   bottom_step  2M+1   the same for the lowest note
+ *   span         D      non-empty frames by highest minus lowest note
+ * Nothing is ever counted across a piece boundary; a piece of 0 frames has an all-zero row.  All results are exact integers,
+ * summed with integer atomics: a row does not depend on the other pieces of the batch, their order, or how the frames are
+ * tiled over workgroups.  A memset of the table and one launch on `stream`.
+ * CLV_EINVAL before the call touches an argument or the device unless 1 <= N <= 2^20, 1 <= D <= 116, 1 <= Lmax <= 64,
+ * 0 <= low <= 127, F >= 0, off and table not NULL, roll not NULL when F > 0.  clv_roll_stats_column_count is the sum of the
+ * bins, 3 D + Lmax + 12 + (V + 1) + (C + 1) + 2 (2 M + 1), and 0 for a D or Lmax outside those ranges. */
+#define CLV_STATS_VOICES 16
+#define CLV_STATS_CHANGE 16
+#define CLV_STATS_STEP 24
+int clv_roll_stats_column_count(int D, int Lmax);
+int clv_roll_stats(int N, int D, int Lmax, int low, int64_t F, const uint8_t* roll, const int64_t* off,
+                   const int32_t* tonic, int64_t* table, void* stream);
 
 /* ----------------------------------------------------------------- graphs --
  * thin wrappers so a host without HIP bindings can capture a step once and
